@@ -14,6 +14,11 @@ Inputs (octree, triangles, textures) are resident in HBM before timing.
     python bench.py [--gpus N --steps K --warmup W]   (N > 1: spawns N rank processes)
     torchrun --nproc-per-node N bench.py --gpus N ...
 
+Such a run sets up, warms up, times the K steps and prints the line.  --full
+adds the legs that take runs of their own (CPU baseline and its bit-for-bit
+check, per-ray counters, rocprofv3 PMC roofline, max_depth+1, host output);
+--dump-outputs DIR writes the last timed frame as DIR/image.npy.
+
 Rank 0 prints ONE JSON line on stdout; diagnostics go to stderr.
 """
 import argparse
@@ -193,7 +198,7 @@ def run_pmc(a, save_dir=""):
     env = dict(os.environ, TMPDIR="/tmp")
     for k in ("RANK", "LOCAL_RANK", "WORLD_SIZE", "LOCAL_WORLD_SIZE", "MASTER_ADDR", "MASTER_PORT"):
         env.pop(k, None)
-    child = [sys.executable, os.path.abspath(__file__), "--no-cpu", "--no-counters", "--no-pmc", "--no-d9",
+    child = [sys.executable, os.path.abspath(__file__), "--full", "--no-cpu", "--no-counters", "--no-pmc", "--no-d9",
              "--frames-in-flight", "1", "--frames-in-flight-secondary", "1", "--frames-in-flight-trace", "1",
              "--warmup", "0", "--steps",
              str(a.steps), *workload_args(a)]
@@ -337,6 +342,21 @@ def roofline_from_pmc(pmc, kernel, single_ms, out_bytes, ref_bytes, launch_ms=No
     return out
 
 
+def dump_outputs(out_dir, arrays, budget=60 * 2 ** 20):
+    """--dump-outputs: each array of the last timed step as out_dir/<name>.npy
+    (float32 / float64; the whole 1080p image is 24.9 MB, a 4K one 99.5 MB: an
+    array over its share of `budget` bytes is cut to a fixed seeded sample of
+    its elements, in index order, so the files stay under 64 MB in all)."""
+    os.makedirs(out_dir, exist_ok=True)
+    for name, arr in arrays.items():
+        arr = np.ascontiguousarray(arr)
+        if arr.nbytes > budget // len(arrays):
+            n = budget // len(arrays) // arr.itemsize
+            idx = np.sort(np.random.default_rng(20190722).choice(arr.size, size=n, replace=False))
+            arr = arr.reshape(-1)[idx]
+        np.save(os.path.join(out_dir, name + ".npy"), arr)
+
+
 def cpu_info():
     """nproc, usable CPUs (affinity), the cgroup CPU quota and the model."""
     n = os.cpu_count() or 1
@@ -426,6 +446,16 @@ def parse():
                    help="CPU-baseline workers; 0 = hardware_concurrency (os.cpu_count()), as the reference's "
                         "thread pool; at most 64 are ever busy (render_mt posts 64 tile tasks)")
     p.add_argument("--cpu-frames", type=int, default=5, help="CPU-baseline frames timed after 1 warm-up (>= 5)")
+    p.add_argument("--full", action="store_true",
+                   help="also run everything beside the headline figure: the CPU baseline (with its bit-for-bit "
+                        "check of the GPU frames), the per-ray counters, the rocprofv3 PMC passes (roofline), "
+                        "the max_depth+1 and host-output lines, the one-launch time and --mode trace's light map "
+                        "alone; --no-cpu / --no-counters / --no-pmc / --no-d9 then drop single legs.  Without "
+                        "--full a run sets up, warms up, times the steps and prints the line (those fields null)")
+    p.add_argument("--dump-outputs", default="", metavar="DIR",
+                   help="rank 0 writes what the last timed step computed as DIR/<name>.npy: image.npy (the "
+                        "frame's float32 image as the caller of the device entry point receives it) and, for "
+                        "--mode trace, light_hits.npy (the light pass's hit count)")
     p.add_argument("--no-cpu", action="store_true")
     p.add_argument("--no-counters", action="store_true")
     p.add_argument("--no-pmc", action="store_true", help="skip the live rocprofv3 PMC passes (roofline)")
@@ -474,6 +504,8 @@ def parse():
                    help="launcher check only: form the process group (gloo), count the ranks, print one line; "
                         "no GPU is used")
     a = p.parse_args()
+    if not a.full:
+        a.no_cpu = a.no_counters = a.no_pmc = a.no_d9 = True
     trace = a.mode == "trace"
     a.width = a.width or (1024 if trace else 1920)
     a.height = a.height or (1024 if trace else 1080)
@@ -557,6 +589,8 @@ def abi_multi(a):
     torch.cuda.synchronize()
     elapsed = time.perf_counter() - t_start
     span = float(np.mean([x.elapsed_time(y) for x, y in ev]))
+    if a.dump_outputs:
+        dump_outputs(a.dump_outputs, {"image": imgs[(a.steps - 1) % 2].cpu().numpy()})
     last = (a.steps - 1) % a.poses
     tree = vrt.VoxelOctree(sd, a.depth, device=0)
     ref = torch.zeros_like(imgs[0])
@@ -809,7 +843,8 @@ def main():
         if trace:
             # the whole main() frame: light map + filter beside the view's
             # primary march, then the cones (vrt_trace_frame_device)
-            tree.trace_frame_device(light_cam, light_film, cam, film, rk, nr, layout, ptr_, res, s.cuda_stream)
+            cur["light_hits"] = tree.trace_frame_device(light_cam, light_film, cam, film, rk, nr, layout, ptr_, res,
+                                                        s.cuda_stream)
         else:
             tree.render_tiles_device(cam, film, rk, nr, layout, ptr_, s.cuda_stream)
 
@@ -921,7 +956,13 @@ def main():
         elapsed, elapsed_local, host_enq = timed_run()
     # render launch span (HIP events on its stream), ms
     kms = kms_w if rehearse else np.array([s.elapsed_time(e) for s, e in ev])
-    if trace:  # the light map alone (blocking build), for reference beside the overlapped frame
+    if rank == 0 and a.dump_outputs:
+        # before any further leg renders into these buffers again
+        outs = {"image": imgs[(a.steps - 1) % nfl].cpu().numpy()}
+        if trace:
+            outs["light_hits"] = np.array([cur["light_hits"]], np.float64)
+        dump_outputs(a.dump_outputs, outs)
+    if trace and a.full:  # the light map alone (blocking build), for reference beside the overlapped frame
         for _ in range(4):
             torch.cuda.synchronize()
             t0_ = time.perf_counter()
@@ -1248,12 +1289,12 @@ def main():
                            "mode": a.mode, "width": a.width, "height": a.height, "light_n": a.light_n,
                            "max_depth": a.depth, "tris": sd.ntri,
                            "parallelism": f"replicated light map, screen tiles x{world}"},
-                "light_ms_mean": round(float(np.mean(light_ms)), 3),
+                "light_ms_mean": round(float(np.mean(light_ms)), 3) if light_ms else None,
                 "frame_span_ms_mean": round(float(kms.mean()), 3),
                 "note": "one vrt_trace_frame_device call per frame: light pass + sort + filter on the scene "
                         "stream beside the view's primary march on the frame stream, then the cone-traced "
                         "shading (every rank builds the whole light map; the render is sharded); "
-                        "light_ms_mean = vrt_lightmap_build alone, measured separately",
+                        "light_ms_mean = vrt_lightmap_build alone, measured separately (--full)",
                 "roofline": roof,
                 "roofline_per_kernel": trace_kernels,
                 "cpu_baseline": cpu,

@@ -8,9 +8,9 @@
 # usage: tools/collect.sh [--no-tests]
 cd "${GRAFT_REPO_ROOT:-$(dirname "$0")/..}"
 rm -rf gpurun_out/pmc_bench gpurun_out/pmc_4k gpurun_out/pmc_sec gpurun_out/pmc_trace
-B="python -u bench.py"
+B="python -u bench.py --full"
 exec bash tools/check_call.sh "$@" \
-  "drv|500|$B --gpus 1 --steps 20 --warmup 5" \
+  "drv|500|python -u bench.py --gpus 1 --steps 20 --warmup 5" \
   "bench|500|$B --pmc-save gpurun_out/pmc_bench" \
   "bench_4k|500|$B --width 3840 --height 2160 --depth 9 --pmc-save gpurun_out/pmc_4k" \
   "bench_sec|700|$B --mode secondary --pmc-save gpurun_out/pmc_sec" \

@@ -11,4 +11,4 @@ bash tools/gpu_steps.sh \
   "tests_d|900|python -u -m pytest tests -m gpu -k 'trace or compaction or secondary or c5' -v --timeout 300 --timeout-method thread" \
   "ab_tr|400|python -u tools/ab.py build/ab/libvrt_base.so $L --mode trace --rounds 6" \
   "ab_st|500|python -u tools/ab.py $L build/ab/libvrt_t0.so build/ab/libvrt_t24.so build/ab/libvrt_t48.so build/ab/libvrt_base.so --mode secondary --rounds 4" \
-  "trace|400|python -u bench.py --mode trace --no-cpu --steps 32"
+  "trace|400|python -u bench.py --full --mode trace --no-cpu --steps 32"

@@ -11,5 +11,5 @@ bash tools/check_call.sh \
   "diag|200|python -u tools/diag_phases.py build/ab/libvrt_diag.so" \
   "ab_tr|400|python -u tools/ab.py build/ab/libvrt_base.so $L --mode trace --rounds 6" \
   "ab_st|500|python -u tools/ab.py $L build/ab/libvrt_t0.so build/ab/libvrt_t24.so build/ab/libvrt_t48.so build/ab/libvrt_base.so --mode secondary --rounds 4" \
-  "trace|400|python -u bench.py --mode trace --no-cpu --steps 32" \
+  "trace|400|python -u bench.py --full --mode trace --no-cpu --steps 32" \
   "sec|400|python -u bench.py --mode secondary --no-cpu --no-pmc"
