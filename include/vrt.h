@@ -296,6 +296,10 @@ int vrt_device_selftest(int device, const double *mt_in, double *mt_out,
  * as it does a pixel with a ray off the fast walk. */
 #define VRT_TEST_SEC_DEFER 128
 #define VRT_TEST_VIRTUAL_RANKS_N(n) (VRT_TEST_VIRTUAL_RANKS | ((n) << 8))
+/* VRT_TEST_SMALL_BATCH_CHUNK (the next free bit: bits 8..15 hold the virtual
+ * rank count) makes vrt_trace_batch[_device] work in chunks of 200 rays, so
+ * the chunk seams are reached by small batches. */
+#define VRT_TEST_SMALL_BATCH_CHUNK 0x10000
 int vrt_set_test_flags(int flags);
 /* The current vrt_set_test_flags value (so a caller can restore it). */
 int vrt_test_flags(void);
@@ -316,8 +320,9 @@ int vrt_secondary_spill_stats(vrt_scene *s, int64_t stats[7]);
 /* Device bytes the scene holds beyond its octree, triangles and textures
  * (vrt_scene_info().device_bytes): per-call scratch kept between calls --
  * config 5's compaction queues (*spill_bytes, may be NULL), the light-map
- * build's scratch and light-map sets, the trace records, the host-output
- * image, the tabled tile deals of multi-rank calls (4 B per tile of the
+ * build's scratch and light-map sets, the trace records (the frames' and
+ * the batched trace's one chunk share them), the device staging of the
+ * host-array batched trace, the host-output image, the tabled tile deals of multi-rank calls (4 B per tile of the
  * rank). */
 int vrt_scene_scratch_bytes(vrt_scene *s, int64_t *bytes, int64_t *spill_bytes);
 
@@ -422,6 +427,43 @@ int vrt_trace_frame_device(vrt_scene *s, const vrt_camera *light_cam,
                            const vrt_film *film, float min_voxel, int rank,
                            int nranks, int image_layout, float *d_out,
                            void *stream, int64_t *hits);
+
+/* ---- batched trace() / cone_trace over the caller's rays and points -------
+ * The reference's per-ray entry points beside ray_march, as its
+ * LightProbe::gather_light uses them: the driver's trace(root, ray, 5, true)
+ * (VRT/main.cc:10-30) and gi::cone_trace(root, isect, min_voxel_size)
+ * (VRT/voxel_octree.cc:313-330), on the scene's current light map
+ * (vrt_lightmap_build / vrt_trace_frame_device; VRT_E_INVALID without one).
+ * min_voxel <= 0: the scene's Res.  n == 0 is VRT_OK and touches nothing. */
+/* jql::ISect (hit point, normal) as gi::cone_trace takes it */
+typedef struct { float hit_p[3]; float normal[3]; } vrt_isect;
+
+/* optional per-ray outputs of vrt_trace_batch; any pointer may be NULL */
+typedef struct {
+        vrt_hit *hits;     /* n: exactly what vrt_ray_march_batch writes */
+        float *indirect;   /* 3n: cone_trace(root, isect, min_voxel) */
+        float *direct;     /* 3n: leaf->compute_illum(-ray.d) */
+        float *albedo;     /* 3n: get_albedo(isect) */
+} vrt_trace_parts;
+
+/* rgb[3i..] = trace(root, rays[i], 5, true): the sky lerp on a miss, else
+ * get_albedo * (cone_trace + compute_illum(-d)).  Rays are taken as they are
+ * (already constructed, as vrt_ray_march_batch takes them).  On a miss the
+ * three float parts are +0 and hits holds the miss record.  Host arrays. */
+int vrt_trace_batch(vrt_scene *s, const vrt_ray *rays, int64_t n, float min_voxel,
+                    float *rgb /* 3n */, const vrt_trace_parts *parts /* may be NULL */);
+/* Device-resident variant: every array in HBM (d_parts is a host struct of
+ * device pointers), enqueued on `stream`, no host synchronisation; ordered
+ * with frames in flight on other streams through the light-map set's event.
+ * Scratch (one chunk of 64-B records) does not grow with n. */
+int vrt_trace_batch_device(vrt_scene *s, const vrt_ray *d_rays, int64_t n, float min_voxel,
+                           float *d_rgb, const vrt_trace_parts *d_parts, void *stream);
+/* rgb[3i..] = gi::cone_trace(root, isects[i], min_voxel) for every element,
+ * whatever the point and normal are (there is no notion of a miss). */
+int vrt_cone_trace_batch(vrt_scene *s, const vrt_isect *isects, int64_t n, float min_voxel,
+                         float *rgb /* 3n */);
+int vrt_cone_trace_batch_device(vrt_scene *s, const vrt_isect *d_isects, int64_t n,
+                                float min_voxel, float *d_rgb, void *stream);
 
 /* ---- output (VRT/stb_image_write.h:178,723-757) ------------------------- */
 /* Byte-identical to stbi_write_hdr: returns 1 on success, 0 on failure. */

@@ -53,6 +53,16 @@ class Hit(C.Structure):
                 ("hit_p", C.c_float * 3), ("normal", C.c_float * 3)]
 
 
+class ISect(C.Structure):
+    _fields_ = [("hit_p", C.c_float * 3), ("normal", C.c_float * 3)]
+
+
+class TraceParts(C.Structure):
+    """vrt_trace_parts: host or device pointers (any may be NULL)."""
+    _fields_ = [("hits", C.c_void_p), ("indirect", C.c_void_p), ("direct", C.c_void_p),
+                ("albedo", C.c_void_p)]
+
+
 class SceneInfo(C.Structure):
     _fields_ = [("nodes", C.c_int64), ("internal", C.c_int64),
                 ("leaves", C.c_int64), ("nonempty_leaves", C.c_int64),
@@ -119,6 +129,10 @@ SIGNATURES = {
                                               C.c_int, _P, _P, _P]),
     "vrt_ray_march_batch": (C.c_int, [_P, C.POINTER(Ray), C.c_int64, C.POINTER(Hit)]),
     "vrt_ray_march_batch_device": (C.c_int, [_P, _P, C.c_int64, _P, _P]),
+    "vrt_trace_batch": (C.c_int, [_P, C.POINTER(Ray), C.c_int64, C.c_float, f32p, C.POINTER(TraceParts)]),
+    "vrt_trace_batch_device": (C.c_int, [_P, _P, C.c_int64, C.c_float, _P, C.POINTER(TraceParts), _P]),
+    "vrt_cone_trace_batch": (C.c_int, [_P, C.POINTER(ISect), C.c_int64, C.c_float, f32p]),
+    "vrt_cone_trace_batch_device": (C.c_int, [_P, _P, C.c_int64, C.c_float, _P, _P]),
     "vrt_device_selftest": (C.c_int, [C.c_int, f64p, f64p, f32p, i32p, C.c_int64]),
     "vrt_write_hdr": (C.c_int, [C.c_char_p, C.c_int, C.c_int, C.c_int, f32p]),
     "stbi_write_hdr": (C.c_int, [C.c_char_p, C.c_int, C.c_int, C.c_int, f32p]),

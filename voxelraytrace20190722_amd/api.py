@@ -5,6 +5,7 @@ Names follow the reference (VRT/x = VoxelRayTrace20190722/x):
   Film(w, h, nx, ny)                                                 VRT/camera.h:24-39
   ray_march_init(scene, max_depth) -> VoxelOctree                    VRT/voxel_octree.h:85-86
   ray_march(tree, rays)                                              VRT/voxel_octree.h:87-89
+  trace(tree, rays) / cone_trace(tree, hit_p, normal)                VRT/main.cc:10-30, voxel_octree.cc:313-330
   render(tree, cam, film)     the per-pixel loop of VRT/main.cc:118-123 (primary shading)
   intersect_triangle3 / tri_box_overlap                              VRT/raytri.h:5, tribox2.h:6
   write_hdr                                                          VRT/stb_image_write.h:178
@@ -506,6 +507,64 @@ class VoxelOctree:
               "vrt_trace_frame_device")
         return hits.value
 
+    # ---- batched trace() / cone_trace over the caller's rays and points ----
+    def trace(self, rays, min_voxel=0.0, parts=False):
+        """Batched trace(root, ray, 5, true) (VRT/main.cc:10-30) over (n, 8) rays
+        {o, d, tmin, tmax}, taken as they are -> rgb (n, 3).  parts=True also
+        returns a dict: ray_march's hit / tri / voxel / hit_p / normal and the
+        terms indirect (cone_trace), direct (compute_illum(-d)) and albedo
+        (all +0 on a miss; rgb = albedo * (indirect + direct))."""
+        rays = np.asarray(rays, np.float32)
+        if rays.ndim != 2 or rays.shape[1] != 8:
+            raise ValueError(f"rays must be (n, 8) {{o, d, tmin, tmax}}, got {rays.shape}")
+        rays = np.ascontiguousarray(rays)
+        n = rays.shape[0]
+        rgb = np.zeros((n, 3), np.float32)
+        pc, hits, ind, dr, alb = None, None, None, None, None
+        if parts:
+            hits = np.zeros((n, 9), np.uint32)
+            ind, dr, alb = (np.zeros((n, 3), np.float32) for _ in range(3))
+            pc = _ffi.TraceParts(hits.ctypes.data, ind.ctypes.data, dr.ctypes.data, alb.ctypes.data)
+        check(lib().vrt_trace_batch(self.h, rays.ctypes.data_as(C.POINTER(_ffi.Ray)), n, float(min_voxel),
+                                    ptr(rgb, _ffi.f32p), None if pc is None else C.byref(pc)),
+              "vrt_trace_batch")
+        if not parts:
+            return rgb
+        return rgb, {"hit": hits[:, 0].astype(np.int32), "tri": hits[:, 1].view(np.int32).copy(),
+                     "voxel": hits[:, 2].copy(), "hit_p": hits[:, 3:6].view(np.float32).copy(),
+                     "normal": hits[:, 6:9].view(np.float32).copy(), "indirect": ind, "direct": dr,
+                     "albedo": alb}
+
+    def cone_trace(self, hit_p, normal, min_voxel=0.0):
+        """Batched gi::cone_trace(root, isect, min_voxel) (VRT/voxel_octree.cc:
+        313-330) at (n, 3) points with (n, 3) normals -> (n, 3)."""
+        hit_p, normal = np.asarray(hit_p, np.float32), np.asarray(normal, np.float32)
+        if hit_p.ndim != 2 or hit_p.shape[1] != 3 or normal.shape != hit_p.shape:
+            raise ValueError(f"hit_p and normal must both be (n, 3), got {hit_p.shape} and {normal.shape}")
+        isects = np.ascontiguousarray(np.concatenate([hit_p, normal], axis=1))
+        n = isects.shape[0]
+        rgb = np.zeros((n, 3), np.float32)
+        check(lib().vrt_cone_trace_batch(self.h, isects.ctypes.data_as(C.POINTER(_ffi.ISect)), n,
+                                         float(min_voxel), ptr(rgb, _ffi.f32p)), "vrt_cone_trace_batch")
+        return rgb
+
+    def trace_device(self, d_rays_ptr, n, d_rgb_ptr, min_voxel=0.0, d_hits_ptr=None, d_indirect_ptr=None,
+                     d_direct_ptr=None, d_albedo_ptr=None, stream_ptr=None):
+        """vrt_trace_batch_device: raw device pointers (n vrt_ray in, 3n floats
+        out, optional vrt_hit / 3n-float parts), enqueued on the stream."""
+        pc = _ffi.TraceParts(d_hits_ptr, d_indirect_ptr, d_direct_ptr, d_albedo_ptr)
+        check(lib().vrt_trace_batch_device(self.h, C.c_void_p(d_rays_ptr), int(n), float(min_voxel),
+                                           C.c_void_p(d_rgb_ptr), C.byref(pc),
+                                           None if stream_ptr is None else C.c_void_p(stream_ptr)),
+              "vrt_trace_batch_device")
+
+    def cone_trace_device(self, d_isects_ptr, n, d_rgb_ptr, min_voxel=0.0, stream_ptr=None):
+        """vrt_cone_trace_batch_device: n vrt_isect {hit_p, normal} in, 3n floats out."""
+        check(lib().vrt_cone_trace_batch_device(self.h, C.c_void_p(d_isects_ptr), int(n), float(min_voxel),
+                                                C.c_void_p(d_rgb_ptr),
+                                                None if stream_ptr is None else C.c_void_p(stream_ptr)),
+              "vrt_cone_trace_batch_device")
+
 
 class MultiOctree:
     """The octree replicated on every device of a mask, with an RCCL
@@ -591,6 +650,16 @@ def ray_march_init(scene, max_depth, device=0):
 def ray_march(tree, rays):
     """gi::ray_march over a batch of rays (VRT/voxel_octree.cc:131-188)."""
     return tree.ray_march(rays)
+
+
+def trace(tree, rays, min_voxel=0.0, parts=False):
+    """The driver's trace(root, ray, 5, true) (VRT/main.cc:10-30), batched."""
+    return tree.trace(rays, min_voxel, parts)
+
+
+def cone_trace(tree, hit_p, normal, min_voxel=0.0):
+    """gi::cone_trace(root, isect, min_voxel_size) (VRT/voxel_octree.h), batched."""
+    return tree.cone_trace(hit_p, normal, min_voxel)
 
 
 def render(tree, cam, film, **kw):
@@ -756,6 +825,7 @@ TEST_STREAM_LEFTOVER = 16  # include/vrt.h VRT_TEST_STREAM_LEFTOVER
 TEST_LIGHT_TAIL = 32  # include/vrt.h VRT_TEST_LIGHT_TAIL
 TEST_PRIM_TAIL = 64  # include/vrt.h VRT_TEST_PRIM_TAIL
 TEST_SEC_DEFER = 128  # include/vrt.h VRT_TEST_SEC_DEFER
+TEST_SMALL_BATCH_CHUNK = 0x10000  # include/vrt.h VRT_TEST_SMALL_BATCH_CHUNK
 
 
 def set_test_flags(flags):

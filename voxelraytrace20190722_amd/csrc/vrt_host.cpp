@@ -414,6 +414,11 @@ struct vrt_scene {
         // kept between calls (grown as needed)
         void *d_rays = nullptr, *d_hits = nullptr, *h_rays = nullptr, *h_hits = nullptr;
         int64_t rays_cap = 0;
+        // vrt_trace_batch / vrt_cone_trace_batch (host arrays): one chunk's
+        // inputs and outputs on the device and their pinned staging, kept
+        // between calls (grown as needed, never beyond one chunk)
+        void *d_tb = nullptr, *h_tb = nullptr;
+        size_t tb_bytes = 0;
         // every entry point that launches work on the scene holds mu (one
         // host thread at a time; device work on several streams is ordered
         // by the events above)
@@ -1110,6 +1115,10 @@ extern "C" void vrt_scene_destroy(vrt_scene *s)
                         (void)hipHostFree(s->h_rays);
                 if (s->h_hits)
                         (void)hipHostFree(s->h_hits);
+                if (s->d_tb)
+                        (void)hipFree(s->d_tb);
+                if (s->h_tb)
+                        (void)hipHostFree(s->h_tb);
                 if (s->stream)
                         (void)hipStreamDestroy(s->stream);
         }
@@ -2014,7 +2023,7 @@ extern "C" int vrt_scene_scratch_bytes(vrt_scene *s, int64_t *bytes, int64_t *sp
         for (int k = 0; k < 2; ++k)
                 if (s->d_spill[k])
                         sp += (int64_t)spill_set_bytes(s->spill_cap[k], s->spill_px[k]);
-        int64_t t = sp + (int64_t)s->light_bytes + (int64_t)s->ho.bytes;
+        int64_t t = sp + (int64_t)s->light_bytes + (int64_t)s->ho.bytes + (int64_t)s->tb_bytes;
         for (const TraceSet &ts : s->ts) {
                 if (ts.lm)
                         t += (int64_t)lm_set_bytes(s->nodes.size());
@@ -2371,11 +2380,12 @@ static int trace_ok(vrt_scene *s, float min_voxel)
         return VRT_OK;
 }
 
-static int trace_scratch(vrt_scene *s, int set, const TraceParams &tp, TraceParams *out)
+// nslots records: a frame's tiles_this_rank * 256 samples, or one chunk of a
+// batched trace (the set serves one user at a time, so they share the block)
+static int trace_scratch_n(vrt_scene *s, int set, const TraceParams &tp, size_t nslots, TraceParams *out)
 {
         *out = tp;
         TraceSet &t = s->ts[set];
-        const size_t nslots = (size_t)tp.r.tiles_this_rank * 256;
         // the cone step table and its length (at fixed offsets: the table
         // outlives calls with other tile counts), the primary pass's 64-B
         // records, its deferred-sample count (512 B) and list
@@ -2406,6 +2416,11 @@ static int trace_scratch(vrt_scene *s, int set, const TraceParams &tp, TracePara
         out->tail_n = reinterpret_cast<unsigned int *>(b + head + nslots * 64);
         out->tail = reinterpret_cast<uint32_t *>(b + head + nslots * 64 + 512);
         return VRT_OK;
+}
+
+static int trace_scratch(vrt_scene *s, int set, const TraceParams &tp, TraceParams *out)
+{
+        return trace_scratch_n(s, set, tp, (size_t)tp.r.tiles_this_rank * 256, out);
 }
 
 // After launch_trace_prim returned success: the step table it was asked to
@@ -2471,11 +2486,20 @@ static void split_bounds(float maxdist, const float *up, float *bound)
         std::memcpy(last, bound, sizeof last);
 }
 
+static void fill_trace_light(vrt_scene *s, int set, float min_voxel, TraceParams *tp);
+
 static void fill_trace_params(vrt_scene *s, int set, const vrt_camera *cam, const vrt_film *film, float min_voxel,
                               int rank, int nranks, TraceParams *tp)
 {
         std::memset(tp, 0, sizeof *tp);
         fill_render_params(s, cam, film, rank, nranks, &tp->r);
+        fill_trace_light(s, set, min_voxel, tp);
+}
+
+// the cone march's part of TraceParams: the set's light map and the
+// distances (no camera: the batched calls fill only this and the scene)
+static void fill_trace_light(vrt_scene *s, int set, float min_voxel, TraceParams *tp)
+{
         if (!(min_voxel > 0.f))
                 vrt_scene_min_voxel(s, 0, &min_voxel);
         tp->lm = s->ts[set].lm;
@@ -2711,6 +2735,214 @@ extern "C" int vrt_ray_march_batch(vrt_scene *s, const vrt_ray *rays,
         HIPCHK(hipStreamSynchronize(s->stream));
         par_memcpy(hits, s->h_hits, (size_t)n * sizeof(vrt_hit));
         return VRT_OK;
+}
+
+// ---- batched trace() / cone_trace (vrt_trace_batch, vrt_cone_trace_batch) --
+// Records per chunk of vrt_trace_batch: the scratch (64 B each, in the
+// light-map set's record block) is bounded by it whatever n is.
+constexpr int64_t kBatchChunk = (int64_t)1 << 20;
+
+static int64_t batch_chunk()
+{
+        return (g_test_flags.load() & VRT_TEST_SMALL_BATCH_CHUNK) ? 200 : kBatchChunk;
+}
+
+// One batched call on stream st over device arrays (caller holds s->mu, the
+// device is set, a light map exists): the current set's light map and step
+// table, taken and released through the set's event like a frame.  io.rays
+// set: trace(); io.isects set: cone_trace.
+static int batch_enqueue(vrt_scene *s, const BatchIO &io, float min_voxel, hipStream_t st)
+{
+        const int set = s->lm_cur;
+        TraceParams tp0, tp;
+        std::memset(&tp0, 0, sizeof tp0);
+        tp0.r.sc = s->dev;
+        tp0.r.test_flags = g_test_flags.load();
+        fill_trace_light(s, set, min_voxel, &tp0);
+        const int64_t chunk = batch_chunk();
+        const size_t nslots = io.rays ? (size_t)std::min(io.n, chunk) : 0;
+        if (int rc = trace_scratch_n(s, set, tp0, nslots, &tp))
+                return rc;
+        if (int rc = ts_acquire(s, set, st))
+                return rc;
+        (void)hipGetLastError();  // a leftover error of an earlier call is not this launch's
+        const hipError_t e = io.rays ? launch_trace_batch(tp, io, chunk, st) : launch_cones_batch(tp, io, st);
+        if (e != hipSuccess) {
+                (void)ts_release(s, set, st);
+                return fail(VRT_E_DEVICE, "batched trace launch failed: %s", hipGetErrorString(e));
+        }
+        if (tp.build_steps) {  // k_cone_steps is enqueued (steps_commit)
+                s->ts[set].steps_key[0] = tp.mindist;
+                s->ts[set].steps_key[1] = tp.maxdist;
+        }
+        return ts_release(s, set, st);
+}
+
+// n == 0 is VRT_OK whatever the scene is (*empty: nothing to do); only then
+// does a host-only scene count
+static int batch_args_ok(vrt_scene *s, const void *in, int64_t n, const void *rgb, bool *empty)
+{
+        *empty = false;
+        if (!s || n < 0)
+                return fail(VRT_E_INVALID, "bad argument");
+        if (n == 0) {
+                *empty = true;
+                return VRT_OK;
+        }
+        if (need_device(s))
+                return VRT_E_NODEVICE;
+        if (!in || !rgb)
+                return fail(VRT_E_INVALID, "null argument");
+        return VRT_OK;
+}
+
+extern "C" int vrt_trace_batch_device(vrt_scene *s, const vrt_ray *d_rays, int64_t n, float min_voxel,
+                                      float *d_rgb, const vrt_trace_parts *d_parts, void *stream)
+{
+        bool empty;
+        if (int rc = batch_args_ok(s, d_rays, n, d_rgb, &empty))
+                return rc;
+        if (empty)
+                return VRT_OK;
+        if (int rc = trace_ok(s, min_voxel))
+                return rc;
+        std::lock_guard<std::mutex> lk(s->mu);
+        if (s->lm_cur < 0)
+                return fail(VRT_E_INVALID, "no light map: call vrt_lightmap_build first");
+        HIPCHK(hipSetDevice(s->device));
+        BatchIO io{};
+        io.rays = reinterpret_cast<const float *>(d_rays);
+        io.n = n;
+        io.rgb = d_rgb;
+        if (d_parts) {
+                io.hits = reinterpret_cast<uint32_t *>(d_parts->hits);
+                io.indirect = d_parts->indirect;
+                io.direct = d_parts->direct;
+                io.albedo = d_parts->albedo;
+        }
+        return batch_enqueue(s, io, min_voxel, static_cast<hipStream_t>(stream));
+}
+
+extern "C" int vrt_cone_trace_batch_device(vrt_scene *s, const vrt_isect *d_isects, int64_t n, float min_voxel,
+                                           float *d_rgb, void *stream)
+{
+        bool empty;
+        if (int rc = batch_args_ok(s, d_isects, n, d_rgb, &empty))
+                return rc;
+        if (empty)
+                return VRT_OK;
+        if (int rc = trace_ok(s, min_voxel))
+                return rc;
+        std::lock_guard<std::mutex> lk(s->mu);
+        if (s->lm_cur < 0)
+                return fail(VRT_E_INVALID, "no light map: call vrt_lightmap_build first");
+        HIPCHK(hipSetDevice(s->device));
+        BatchIO io{};
+        io.isects = reinterpret_cast<const float *>(d_isects);
+        io.n = n;
+        io.rgb = d_rgb;
+        return batch_enqueue(s, io, min_voxel, static_cast<hipStream_t>(stream));
+}
+
+// the host-array calls' staging: `bytes` on the device and pinned (caller
+// holds s->mu; used on the scene's stream only)
+static int batch_staging(vrt_scene *s, size_t bytes)
+{
+        if (bytes <= s->tb_bytes)
+                return VRT_OK;
+        HIPCHK(hipStreamSynchronize(s->stream));
+        if (s->d_tb)
+                (void)hipFree(s->d_tb);
+        if (s->h_tb)
+                (void)hipHostFree(s->h_tb);
+        s->d_tb = s->h_tb = nullptr;
+        s->tb_bytes = 0;
+        HIPCHK(hipMalloc(&s->d_tb, bytes));
+        HIPCHK(hipHostMalloc(&s->h_tb, bytes, hipHostMallocDefault));
+        s->tb_bytes = bytes;
+        return VRT_OK;
+}
+
+// Host arrays: chunk by chunk through the staging (in: `in_sz` bytes per
+// element at offset 0; out: the requested arrays behind it, out_sz[k] bytes
+// per element each), one host sync per chunk.
+static int batch_host(vrt_scene *s, const void *in, size_t in_sz, bool rays, int64_t n, float min_voxel,
+                      void *const out[5], const size_t out_sz[5])
+{
+        const int64_t m = std::min(n, batch_chunk());
+        size_t per = in_sz;
+        for (int k = 0; k < 5; ++k)
+                per += out[k] ? out_sz[k] : 0;
+        if (int rc = batch_staging(s, (size_t)m * per))
+                return rc;
+        char *d = static_cast<char *>(s->d_tb), *h = static_cast<char *>(s->h_tb);
+        for (int64_t b = 0; b < n; b += m) {
+                const int64_t c = std::min(m, n - b);
+                par_memcpy(h, static_cast<const char *>(in) + (size_t)b * in_sz, (size_t)c * in_sz);
+                HIPCHK(hipMemcpyAsync(d, h, (size_t)c * in_sz, hipMemcpyHostToDevice, s->stream));
+                BatchIO io{};
+                (rays ? io.rays : io.isects) = reinterpret_cast<const float *>(d);
+                io.n = c;
+                size_t off = (size_t)m * in_sz, o5[5] = {};
+                for (int k = 0; k < 5; ++k) {
+                        o5[k] = off;
+                        off += out[k] ? (size_t)m * out_sz[k] : 0;
+                }
+                io.rgb = reinterpret_cast<float *>(d + o5[0]);
+                io.hits = out[1] ? reinterpret_cast<uint32_t *>(d + o5[1]) : nullptr;
+                io.indirect = out[2] ? reinterpret_cast<float *>(d + o5[2]) : nullptr;
+                io.direct = out[3] ? reinterpret_cast<float *>(d + o5[3]) : nullptr;
+                io.albedo = out[4] ? reinterpret_cast<float *>(d + o5[4]) : nullptr;
+                if (int rc = batch_enqueue(s, io, min_voxel, s->stream))
+                        return rc;
+                HIPCHK(hipMemcpyAsync(h + (size_t)m * in_sz, d + (size_t)m * in_sz, off - (size_t)m * in_sz,
+                                      hipMemcpyDeviceToHost, s->stream));
+                HIPCHK(hipStreamSynchronize(s->stream));
+                for (int k = 0; k < 5; ++k)
+                        if (out[k])
+                                par_memcpy(static_cast<char *>(out[k]) + (size_t)b * out_sz[k], h + o5[k],
+                                           (size_t)c * out_sz[k]);
+        }
+        return VRT_OK;
+}
+
+extern "C" int vrt_trace_batch(vrt_scene *s, const vrt_ray *rays, int64_t n, float min_voxel, float *rgb,
+                               const vrt_trace_parts *parts)
+{
+        static_assert(sizeof(vrt_isect) == 24, "vrt_isect layout");
+        bool empty;
+        if (int rc = batch_args_ok(s, rays, n, rgb, &empty))
+                return rc;
+        if (empty)
+                return VRT_OK;
+        if (int rc = trace_ok(s, min_voxel))
+                return rc;
+        std::lock_guard<std::mutex> lk(s->mu);
+        if (s->lm_cur < 0)
+                return fail(VRT_E_INVALID, "no light map: call vrt_lightmap_build first");
+        HIPCHK(hipSetDevice(s->device));
+        void *const out[5] = { rgb, parts ? parts->hits : nullptr, parts ? parts->indirect : nullptr,
+                               parts ? parts->direct : nullptr, parts ? parts->albedo : nullptr };
+        const size_t out_sz[5] = { 12, sizeof(vrt_hit), 12, 12, 12 };
+        return batch_host(s, rays, sizeof(vrt_ray), true, n, min_voxel, out, out_sz);
+}
+
+extern "C" int vrt_cone_trace_batch(vrt_scene *s, const vrt_isect *isects, int64_t n, float min_voxel, float *rgb)
+{
+        bool empty;
+        if (int rc = batch_args_ok(s, isects, n, rgb, &empty))
+                return rc;
+        if (empty)
+                return VRT_OK;
+        if (int rc = trace_ok(s, min_voxel))
+                return rc;
+        std::lock_guard<std::mutex> lk(s->mu);
+        if (s->lm_cur < 0)
+                return fail(VRT_E_INVALID, "no light map: call vrt_lightmap_build first");
+        HIPCHK(hipSetDevice(s->device));
+        void *const out[5] = { rgb, nullptr, nullptr, nullptr, nullptr };
+        const size_t out_sz[5] = { 12, sizeof(vrt_hit), 12, 12, 12 };
+        return batch_host(s, isects, sizeof(vrt_isect), false, n, min_voxel, out, out_sz);
 }
 
 extern "C" int vrt_device_selftest(int device, const double *mt_in,

@@ -485,6 +485,19 @@ struct TraceParams {
 // is flagged (-1) and the march computes its steps inline.
 constexpr int kConeSteps = 1024;
 
+// One launch of the batched trace() / cone_trace (vrt_trace_batch,
+// vrt_cone_trace_batch): device pointers, n elements.  rays = vrt_ray (8
+// floats each) or isects = vrt_isect (6 floats each); hits = vrt_hit records
+// (9 words each); hits and the three float parts may be null.
+struct BatchIO {
+        const float *rays;
+        const float *isects;
+        int64_t n;
+        float *rgb;
+        uint32_t *hits;
+        float *indirect, *direct, *albedo;
+};
+
 // GPU octree build (vrt_build.hip): the host build's
 // arrays, produced on `device` and copied back.
 struct DeviceBuild {
@@ -575,6 +588,10 @@ hipError_t launch_lm_level(const NodeRec *nodes, int64_t begin, int64_t end, LMR
 hipError_t launch_trace(const TraceParams &p, hipStream_t st);
 hipError_t launch_trace_prim(const TraceParams &p, hipStream_t st);
 hipError_t launch_cones(const TraceParams &p, hipStream_t st);
+// the batched trace(): io.n rays in chunks of `chunk` records (p.rec), and
+// the batched cone_trace; both build the step table first when p.build_steps
+hipError_t launch_trace_batch(const TraceParams &p, const BatchIO &io, int64_t chunk, hipStream_t st);
+hipError_t launch_cones_batch(const TraceParams &p, const BatchIO &io, hipStream_t st);
 // per-node cone-descent records and the light map's finiteness flag
 hipError_t launch_lm_aux(const NodeRec *nodes, const LMRec *lm, int64_t n, float4 *cc, uint32_t *bad,
                          hipStream_t st);

@@ -4546,6 +4546,158 @@ __global__ __launch_bounds__(64, VRT_CONES_WAVES_PER_EU) void k_cones_film(Trace
         }
 }
 
+// ---- batched trace() / cone_trace over caller-supplied rays and points ----
+// Phase 1 of vrt_trace_batch: trace()'s ray_march + get_albedo over
+// arbitrary rays, one ray per lane as k_ray_march (degenerate rays take the
+// exact path), writing the sample record of trace_prim_record at slot = the
+// ray's index in the chunk and, when asked, the vrt_hit k_ray_march writes.
+// Reads no light map.
+template <bool kR64>
+__global__ __launch_bounds__(kBlock) void k_trace_batch_prim(TraceParams p, BatchIO io)
+{
+        __shared__ uint2 stk[kStack * kBlock];
+        const int tid = threadIdx.x;
+        const int64_t i = (int64_t)blockIdx.x * kBlock + tid;
+        if (i >= io.n)
+                return;
+        const float *rr = io.rays + 8 * i;
+        const RayK r = make_rayk(mk3(rr[0], rr[1], rr[2]), mk3(rr[3], rr[4], rr[5]), rr[6], rr[7]);
+        MarchResult m;
+        ray_march_dispatch<false, kBlock, true, kR64>(p.r.sc, r, stk + tid, nullptr, nullptr, m);
+        trace_prim_record(p, r, m, i);
+        if (io.hits) {
+                uint32_t *o = io.hits + 9 * i;
+                if (m.hit) {
+                        // the record's normal: hit_albedo's, the operations of
+                        // k_ray_march's
+                        const float4 nr = p.rec[4 * i + 1];
+                        o[0] = 1;
+                        o[1] = m.tri;
+                        o[2] = p.r.sc.node_vox[m.node];
+                        o[3] = __float_as_uint(m.hp.x);
+                        o[4] = __float_as_uint(m.hp.y);
+                        o[5] = __float_as_uint(m.hp.z);
+                        o[6] = __float_as_uint(nr.x);
+                        o[7] = __float_as_uint(nr.y);
+                        o[8] = __float_as_uint(nr.z);
+                } else {
+                        o[0] = 0;
+                        o[1] = 0xFFFFFFFFu;
+                        o[2] = 0xFFFFFFFFu;
+                        for (int q = 3; q < 9; ++q)
+                                o[q] = 0;
+                }
+        }
+}
+
+// Phase 2, and all of vrt_cone_trace_batch (kIsect: the hit point and normal
+// come from the caller's vrt_isect array, every element is marched, and rgb
+// is cone_trace's sum alone).  A batch has no tile of neighbouring samples
+// and may be a few thousand rays, so a lane takes one (ray, cone): lane =
+// 6 * r + c, kBatchRays rays per wave, lanes 60-63 idle.  The lane remakes the
+// basis and its cone direction with cone_trace_rec's operations (the same
+// values) and calls cone_march; the ray's first lane then sums the six
+// results by cross-lane reads in cone order from zero, as cone_trace does
+// (VRT/voxel_octree.cc:313-330), adds the direct term and forms trace()'s
+// get_albedo * (indirect + direct) (VRT/main.cc:22-27).  A miss keeps its
+// sky colour and +0 parts.
+constexpr int kBatchRays = 10;
+#ifndef VRT_BATCH_WAVES_PER_EU
+#define VRT_BATCH_WAVES_PER_EU 8
+#endif
+template <bool kIsect>
+__global__ __launch_bounds__(64, VRT_BATCH_WAVES_PER_EU) void k_cones_batch(TraceParams p, BatchIO io)
+{
+        const float hx[6] = { 0.000000f, 0.000000f, 0.823639f, 0.509037f, -0.509037f, -0.823639f };
+        const float hy[6] = { 0.000000f, 0.866025f, 0.267617f, -0.700629f, -0.700629f, 0.267617f };
+        const float hz[6] = { 1.0f, 0.5f, 0.5f, 0.5f, 0.5f, 0.5f };
+        const float hw[6] = { 0.25f, 0.15f, 0.15f, 0.15f, 0.15f, 0.15f };
+        const int lane = threadIdx.x;
+        const int rl = lane / 6, c = lane - 6 * rl;  // lanes 60-63: rl == kBatchRays
+        const int64_t i = (int64_t)blockIdx.x * kBatchRays + rl;
+        const bool live = rl < kBatchRays && i < io.n;
+        bool hit = false;
+        f3 cm = mk3(0.f, 0.f, 0.f);
+        if (live) {
+                f3 hp, n;
+                if (kIsect) {
+                        const float *q = io.isects + 6 * i;
+                        hp = mk3(q[0], q[1], q[2]);
+                        n = mk3(q[3], q[4], q[5]);
+                        hit = true;
+                } else {
+                        const float4 r0 = p.rec[4 * i];
+                        hp = mk3(r0.x, r0.y, r0.z);
+                        hit = r0.w != 0.f;
+                        n = hp;
+                        if (hit) {
+                                const float4 r1 = p.rec[4 * i + 1];
+                                n = mk3(r1.x, r1.y, r1.z);
+                        }
+                }
+                if (hit) {
+                        const float sg = (0.0f > n.z) ? -1.0f : 1.0f;
+                        const float a0 = -1.0f / (sg + n.z);
+                        const float a1 = n.x * n.y * a0;
+                        const f3 t = mk3(1.0f + sg * n.x * n.x * a0, sg * a1, -sg * n.x);
+                        const f3 bb = mk3(a1, sg + n.y * n.y * a0, -n.y);
+                        f3 r = mk3(0.f, 0.f, 0.f);
+                        r = r + t * hx[c];
+                        r = r + bb * hy[c];
+                        r = r + n * hz[c];
+                        const f3 cd = normalize(r);
+                        cm = cone_march(p, hp, cd);
+                }
+        }
+        // every lane is back here: the six cones of the ray, in cone order
+        const int l0 = lane - c;
+        f3 diffuse = mk3(0.f, 0.f, 0.f);
+#pragma unroll
+        for (int j = 0; j < 6; ++j) {
+                const int src = (l0 + j) & 63;
+                const f3 cj = mk3(__shfl(cm.x, src, 64), __shfl(cm.y, src, 64), __shfl(cm.z, src, 64));
+                diffuse = diffuse + cj * hw[j];
+        }
+        if (!live || c != 0)
+                return;
+        float *o = io.rgb + 3 * i;
+        if (kIsect) {
+                o[0] = diffuse.x;
+                o[1] = diffuse.y;
+                o[2] = diffuse.z;
+                return;
+        }
+        const float4 r2 = p.rec[4 * i + 2];
+        f3 col = mk3(r2.x, r2.y, r2.z), direct = mk3(0.f, 0.f, 0.f), albedo = direct;
+        if (hit) {
+                const float4 r3 = p.rec[4 * i + 3];
+                direct = compute_illum(p.lm, __float_as_uint(r3.x), mk3(r3.y, r3.z, r3.w));
+                const f3 lsum = diffuse + direct;
+                albedo = col;
+                col = mk3(r2.x * lsum.x, r2.y * lsum.y, r2.z * lsum.z);
+        } else {
+                diffuse = mk3(0.f, 0.f, 0.f);
+        }
+        o[0] = col.x;
+        o[1] = col.y;
+        o[2] = col.z;
+        if (io.indirect) {
+                io.indirect[3 * i + 0] = diffuse.x;
+                io.indirect[3 * i + 1] = diffuse.y;
+                io.indirect[3 * i + 2] = diffuse.z;
+        }
+        if (io.direct) {
+                io.direct[3 * i + 0] = direct.x;
+                io.direct[3 * i + 1] = direct.y;
+                io.direct[3 * i + 2] = direct.z;
+        }
+        if (io.albedo) {
+                io.albedo[3 * i + 0] = albedo.x;
+                io.albedo[3 * i + 1] = albedo.y;
+                io.albedo[3 * i + 2] = albedo.z;
+        }
+}
+
 // VRT_LIGHT_DIAG builds: the per-wave records of the last light pass
 hipError_t light_diag_copy(void *host, size_t bytes)
 {
@@ -4640,6 +4792,52 @@ hipError_t launch_cones(const TraceParams &p, hipStream_t st)
                 return hipSuccess;
         const int64_t nslots = (int64_t)p.r.tiles_this_rank * 256;
         hipLaunchKernelGGL(k_cones_film, dim3((unsigned)(nslots / 64)), dim3(64), 0, st, p);
+        return hipGetLastError();
+}
+
+// vrt_trace_batch: io.n rays in chunks of `chunk` (p.rec holds one chunk's
+// records; the chunks follow one another on the stream): the step table when
+// p.build_steps, then per chunk the primary march and the cones.
+hipError_t launch_trace_batch(const TraceParams &p, const BatchIO &io, int64_t chunk, hipStream_t st)
+{
+        if (io.n <= 0)
+                return hipSuccess;
+        if (p.build_steps)
+                hipLaunchKernelGGL(k_cone_steps, dim3(1), dim3(64), 0, st, p);
+        for (int64_t b = 0; b < io.n; b += chunk) {
+                BatchIO c = io;
+                c.n = std::min(chunk, io.n - b);
+                c.rays = io.rays + 8 * b;
+                c.rgb = io.rgb + 3 * b;
+                c.hits = io.hits ? io.hits + 9 * b : nullptr;
+                c.indirect = io.indirect ? io.indirect + 3 * b : nullptr;
+                c.direct = io.direct ? io.direct + 3 * b : nullptr;
+                c.albedo = io.albedo ? io.albedo + 3 * b : nullptr;
+                hipLaunchKernelGGL(p.r.sc.wide_leaves ? k_trace_batch_prim<true> : k_trace_batch_prim<false>,
+                                   dim3((unsigned)((c.n + kBlock - 1) / kBlock)), dim3(kBlock), 0, st, p, c);
+                hipLaunchKernelGGL(k_cones_batch<false>, dim3((unsigned)((c.n + kBatchRays - 1) / kBatchRays)),
+                                   dim3(64), 0, st, p, c);
+        }
+        return hipGetLastError();
+}
+
+// vrt_cone_trace_batch: no records, so no chunk scratch; the launches are
+// split only to keep the grid below 2^31 workgroups.
+hipError_t launch_cones_batch(const TraceParams &p, const BatchIO &io, hipStream_t st)
+{
+        if (io.n <= 0)
+                return hipSuccess;
+        if (p.build_steps)
+                hipLaunchKernelGGL(k_cone_steps, dim3(1), dim3(64), 0, st, p);
+        const int64_t chunk = (int64_t)kBatchRays << 26;
+        for (int64_t b = 0; b < io.n; b += chunk) {
+                BatchIO c = io;
+                c.n = std::min(chunk, io.n - b);
+                c.isects = io.isects + 6 * b;
+                c.rgb = io.rgb + 3 * b;
+                hipLaunchKernelGGL(k_cones_batch<true>, dim3((unsigned)((c.n + kBatchRays - 1) / kBatchRays)),
+                                   dim3(64), 0, st, p, c);
+        }
         return hipGetLastError();
 }
 
