@@ -126,6 +126,10 @@ int vrt_scene_create_ex(const vrt_scene_desc *desc, int max_depth, int device,
                         int flags, vrt_scene **out);
 void vrt_scene_destroy(vrt_scene *s);
 int vrt_scene_info(const vrt_scene *s, vrt_scene_info_t *info);
+/* Bytes per leaf record of the scene's device format: 48 (vertices as
+ * floats; the primary walks cull such a leaf's records by per-record boxes)
+ * or 64 (scenes with >= 8 records per non-empty leaf on average). */
+int vrt_scene_ref_format(const vrt_scene *s, int32_t *record_bytes);
 /* Non-empty leaves sorted by voxel id; tris = concatenated leaf lists in
  * insertion (input) order.  Sizes from vrt_scene_info. */
 int vrt_scene_leaves(const vrt_scene *s, uint32_t *voxel, uint32_t *count,

@@ -45,6 +45,8 @@ def main():
     ap.add_argument("--light-n", type=int, default=2048, help="--mode trace: light film side (VRT/main.cc:79)")
     ap.add_argument("--spp", type=int, default=64)
     ap.add_argument("--no-check", action="store_true", help="timing-only variants (images may differ)")
+    ap.add_argument("--per-pose", action="store_true",
+                    help="primary / secondary single launches: also each pose's median launch time per variant")
     ap.add_argument("--ranks", type=int, default=1,
                     help="primary mode: time every rank's share of an N-rank frame separately (launch by launch; "
                          "per pose the slowest rank counts, as in an N-GPU step), images re-assembled with each "
@@ -95,6 +97,7 @@ def main():
     tprs = [L.vrt_tiles_per_rank(C.byref(film), R) for L in libs]
     packs = [torch.zeros((R, tpr * 192), dtype=torch.float32, device=dev) for tpr in tprs]
     times = {p: [] for p in a.libs}
+    pose_times = {p: [] for p in a.libs}  # --per-pose: per round, every pose's launch
     ref = None
     for r in range(a.rounds + 1):
         for vi, (L, h, p) in enumerate(zip(libs, scenes, a.libs)):
@@ -149,6 +152,7 @@ def main():
                 times[p].append(sum(max(s.elapsed_time(e) for s, e in pe) for pe in evs) / len(evs))
             elif r > 0:  # round 0 = warm-up + parity
                 times[p].append(sum(s.elapsed_time(e) for s, e in evs) / len(evs))
+                pose_times[p].append([s.elapsed_time(e) for s, e in evs])
     base = np.median(times[a.libs[0]])
     out = {}
     for p in a.libs:
@@ -156,6 +160,9 @@ def main():
         out[os.path.basename(p)] = {"median_ms": round(float(np.median(t)), 4), "min_ms": round(float(t.min()), 4),
                                     "speedup": round(float(base / np.median(t)), 3),
                                     "mrays": round(a.width * a.height * 4 / np.median(t) / 1e3, 1)}
+        if a.per_pose and pose_times[p]:
+            out[os.path.basename(p)]["per_pose_ms"] = [round(float(v), 4)
+                                                       for v in np.median(np.array(pose_times[p]), axis=0)]
     print(json.dumps(out, indent=1))
 
 

@@ -101,6 +101,7 @@ SIGNATURES = {
     "vrt_scene_create_ex": (C.c_int, [C.POINTER(SceneDesc), C.c_int, C.c_int, C.c_int, C.POINTER(_P)]),
     "vrt_scene_destroy": (None, [_P]),
     "vrt_scene_info": (C.c_int, [_P, C.POINTER(SceneInfo)]),
+    "vrt_scene_ref_format": (C.c_int, [_P, i32p]),
     "vrt_scene_leaves": (C.c_int, [_P, u32p, u32p, i32p]),
     "vrt_scene_nodes": (C.c_int, [_P, f32p, u32p, u32p]),
     "vrt_camera_init": (C.c_int, [C.c_float, f32p, f32p, f32p, C.c_float, C.c_float,

@@ -312,6 +312,14 @@ class VoxelOctree:
     def root_box(self):
         return (np.array(self.info.root_min[:], np.float32), np.array(self.info.root_max[:], np.float32))
 
+    @property
+    def ref_record_bytes(self):
+        """Bytes per leaf record of the device format (vrt_scene_ref_format):
+        48, or 64 for scenes with large leaves."""
+        v = C.c_int32()
+        check(lib().vrt_scene_ref_format(self.h, C.byref(v)), "vrt_scene_ref_format")
+        return v.value
+
     def nodes(self):
         """The flattened octree as uploaded: (boxes (n,6) f32, word a, word b) per
         node in BFS child-block order."""

@@ -717,6 +717,73 @@ static size_t align_up(size_t x) { return (x + 255) & ~(size_t)255; }
 // lie in the root box, so the same bound holds.  Nodes with no triangle below
 // them (never visited by the content-masked walk), and every node of a scene
 // whose extent is not finite and positive (no skip), carry their voxel box.
+static void march_nodes(vrt_scene *s, const vrt_scene_desc *d, std::vector<XNodeRec> &xn);
+
+// The float box [l - eps, h + eps] rounded outward: the one enlargement of a
+// triangle box, shared by DevScene::xnodes and the per-record boxes (RefBox).
+static void enlarged_box(const double l[3], const double h[3], double eps, float bl[3], float bh[3])
+{
+        for (int k = 0; k < 3; ++k) {
+                float fl = (float)(l[k] - eps), fh = (float)(h[k] + eps);
+                if ((double)fl > l[k] - eps)
+                        fl = std::nextafter(fl, -HUGE_VALF);
+                if ((double)fh < h[k] + eps)
+                        fh = std::nextafter(fh, HUGE_VALF);
+                bl[k] = fl;
+                bh[k] = fh;
+        }
+}
+
+// The root box's largest extent: lb_eps = 2^-16 * it, and the skips are on
+// (lb_reach >= 0) only when it is finite and positive.
+static float scene_extent(const vrt_scene *s)
+{
+        float ext = 0.f;
+        for (int k = 0; k < 3; ++k)
+                ext = std::max(ext, s->info.root_max[k] - s->info.root_min[k]);
+        return ext;
+}
+
+// Does the scene carry the per-record boxes (RefBox, vrt_internal.h)?
+static bool has_ref_boxes(const vrt_scene *s)
+{
+        const float ext = scene_extent(s);
+        return VRT_LEAF_CULL && !s->wide_leaves && ext > 0.f && std::isfinite(ext);
+}
+
+// The per-record boxes in device order: out[n - 1 - j] = the box of record
+// j's triangle, the box march_nodes gives a leaf holding that triangle alone
+// (a triangle with a NaN coordinate gets the inverted infinite box, which
+// the line test keeps; intersect_triangle3 then rejects it as it always
+// does).  Only for has_ref_boxes() scenes.
+static void ref_boxes(const vrt_scene *s, const vrt_scene_desc *d, std::vector<RefBox> &out)
+{
+        const size_t n = s->ref_tri.size();
+        const double eps = std::ldexp((double)scene_extent(s), -16);
+        out.resize(n);
+        for (size_t j = 0; j < n; ++j) {
+                const float *p = d->pos + 9 * (size_t)s->ref_tri[j];
+                double l[3] = { HUGE_VAL, HUGE_VAL, HUGE_VAL }, h[3] = { -HUGE_VAL, -HUGE_VAL, -HUGE_VAL };
+                bool nan = false;
+                for (int v = 0; v < 3; ++v)
+                        for (int k = 0; k < 3; ++k) {
+                                nan = nan || std::isnan(p[3 * v + k]);
+                                l[k] = std::min(l[k], (double)p[3 * v + k]);
+                                h[k] = std::max(h[k], (double)p[3 * v + k]);
+                        }
+                RefBox rb{};
+                if (nan) {
+                        for (int k = 0; k < 3; ++k) {
+                                rb.bmin[k] = HUGE_VALF;
+                                rb.bmax[k] = -HUGE_VALF;
+                        }
+                } else {
+                        enlarged_box(l, h, eps, rb.bmin, rb.bmax);
+                }
+                out[n - 1 - j] = rb;
+        }
+}
+
 static void march_nodes(vrt_scene *s, const vrt_scene_desc *d, std::vector<XNodeRec> &xn)
 {
         const size_t nn = s->nodes.size();
@@ -729,11 +796,9 @@ static void march_nodes(vrt_scene *s, const vrt_scene_desc *d, std::vector<XNode
                         xn[i].tmax[k] = s->nodes[i].bmax[k];
                 }
         }
-        float ext = 0.f;
-        for (int k = 0; k < 3; ++k) {
-                ext = std::max(ext, s->info.root_max[k] - s->info.root_min[k]);
+        const float ext = scene_extent(s);
+        for (int k = 0; k < 3; ++k)
                 s->dev.lb_center[k] = 0.5f * (s->info.root_min[k] + s->info.root_max[k]);
-        }
         s->dev.lb_reach = 16.f * ext;
         if (!(ext > 0.f) || !std::isfinite(ext)) {
                 s->dev.lb_reach = -1.f;  // never skip
@@ -768,20 +833,7 @@ static void march_nodes(vrt_scene *s, const vrt_scene_desc *d, std::vector<XNode
                 const double *l = &lo[3 * i], *h = &hi[3 * i];
                 if (!(l[0] <= h[0]))
                         continue;  // no triangle below this node
-                float bl[3], bh[3];
-                for (int k = 0; k < 3; ++k) {
-                        float fl = (float)(l[k] - eps), fh = (float)(h[k] + eps);
-                        if ((double)fl > l[k] - eps)
-                                fl = std::nextafter(fl, -HUGE_VALF);
-                        if ((double)fh < h[k] + eps)
-                                fh = std::nextafter(fh, HUGE_VALF);
-                        bl[k] = fl;
-                        bh[k] = fh;
-                }
-                for (int k = 0; k < 3; ++k) {
-                        xn[i].tmin[k] = bl[k];
-                        xn[i].tmax[k] = bh[k];
-                }
+                enlarged_box(l, h, eps, xn[i].tmin, xn[i].tmax);
         }
 }
 
@@ -796,7 +848,11 @@ static int upload(vrt_scene *s, const vrt_scene_desc *d)
         const void *refs_host = s->wide_leaves ? (const void *)s->refs64.data() : (const void *)s->refs48.data();
         const size_t refs_bytes = s->wide_leaves ? s->refs64.size() * sizeof(RefRec64)
                                                  : s->refs48.size() * sizeof(RefRec48);
-        const size_t sz_refs = std::max<size_t>(64, refs_bytes);
+        // the per-record boxes lie directly below the records (RefBox): the
+        // region is [pad | boxes, last record's first | records]
+        const bool rboxes = has_ref_boxes(s);
+        const size_t sz_rbox = rboxes ? align_up((s->ref_tri.size() + kRefBoxPad) * sizeof(RefBox)) : 0;
+        const size_t sz_refs = sz_rbox + std::max<size_t>(64, refs_bytes);
         const size_t sz_pos = std::max<size_t>(1, s->tri_pos.size()) * sizeof(TriPos);
         const size_t sz_attr = std::max<size_t>(1, s->tri_attr.size()) * sizeof(TriAttr);
         const size_t sz_mats = s->mats.size() * sizeof(MatRec);
@@ -818,7 +874,7 @@ static int upload(vrt_scene *s, const vrt_scene_desc *d)
         HIPCHK(hipMemcpy(base + off[0], s->nodes.data(), sz_nodes, hipMemcpyHostToDevice));
         HIPCHK(hipMemcpy(base + off[1], s->node_vox.data(), sz_vox, hipMemcpyHostToDevice));
         if (refs_bytes)
-                HIPCHK(hipMemcpy(base + off[2], refs_host, refs_bytes, hipMemcpyHostToDevice));
+                HIPCHK(hipMemcpy(base + off[2] + sz_rbox, refs_host, refs_bytes, hipMemcpyHostToDevice));
         if (!s->tri_pos.empty())
                 HIPCHK(hipMemcpy(base + off[3], s->tri_pos.data(), s->tri_pos.size() * sizeof(TriPos), hipMemcpyHostToDevice));
         if (!s->tri_attr.empty())
@@ -830,7 +886,7 @@ static int upload(vrt_scene *s, const vrt_scene_desc *d)
                 HIPCHK(hipMemcpy(base + off[7], d->tex_data, (size_t)s->tex_bytes, hipMemcpyHostToDevice));
         s->dev.nodes = reinterpret_cast<const NodeRec *>(base + off[0]);
         s->dev.node_vox = reinterpret_cast<const uint32_t *>(base + off[1]);
-        s->dev.refs = base + off[2];
+        s->dev.refs = base + off[2] + sz_rbox;
         s->dev.tri_pos = reinterpret_cast<const TriPos *>(base + off[3]);
         s->dev.tri_attr = reinterpret_cast<const TriAttr *>(base + off[4]);
         s->dev.mats = reinterpret_cast<const MatRec *>(base + off[5]);
@@ -844,6 +900,12 @@ static int upload(vrt_scene *s, const vrt_scene_desc *d)
                 if (sz_xnodes)
                         HIPCHK(hipMemcpy(base + off[9], xn.data(), sz_xnodes, hipMemcpyHostToDevice));
                 s->dev.xnodes = reinterpret_cast<const XNodeRec *>(base + off[9]);
+        }
+        if (rboxes && !s->ref_tri.empty()) {
+                std::vector<RefBox> rb;
+                ref_boxes(s, d, rb);
+                const size_t nb = rb.size() * sizeof(RefBox);
+                HIPCHK(hipMemcpy(base + off[2] + sz_rbox - nb, rb.data(), nb, hipMemcpyHostToDevice));
         }
         HIPCHK(persistent_blocks(&s->dev.persist_blocks, &s->dev.sec_blocks));
         s->dev.grid_div = 1;
@@ -1130,6 +1192,14 @@ extern "C" int vrt_scene_info(const vrt_scene *s, vrt_scene_info_t *info)
         if (!s || !info)
                 return fail(VRT_E_INVALID, "null argument");
         *info = s->info;
+        return VRT_OK;
+}
+
+extern "C" int vrt_scene_ref_format(const vrt_scene *s, int32_t *record_bytes)
+{
+        if (!s || !record_bytes)
+                return fail(VRT_E_INVALID, "null argument");
+        *record_bytes = s->wide_leaves ? (int32_t)sizeof(RefRec64) : (int32_t)sizeof(RefRec48);
         return VRT_OK;
 }
 

@@ -63,6 +63,42 @@ struct alignas(16) RefRec64 {
 };
 static_assert(sizeof(RefRec64) == 64, "RefRec64 must be 64 B");
 
+// Leaf-record cull of the finite-slab walk (VRT_LEAF_CULL, RefRec48 scenes):
+// one box per leaf record -- record j's triangle's box enlarged by lb_eps and
+// rounded outward, the box march_nodes gives a one-triangle leaf (both come
+// from enlarged_box(), vrt_host.cpp) -- so a leaf's records are first tested
+// by the fp32 line test on dense, independently loadable boxes and only the
+// survivors take the dependent 48-B load and the fp64 triangle test.  A
+// record whose box the line misses is one intersect_triangle3 rejects
+// (DevScene::xnodes' argument for a single triangle), and survivors are
+// tested in leaf order, so ray_march_isect's first minimum is unchanged.
+// The array lies directly below DevScene::refs and grows downward: record
+// j's box is ((const RefBox *)refs)[-1 - j].  No pointer is added to
+// DevScene, so its layout -- and the code of every kernel that does not
+// cull -- stays as it was.  Built only for RefRec48 scenes with lb_reach >=
+// 0 (lanes cull only under leaf_box_ok, which lb_reach < 0 never grants).
+// VRT_LEAF_CULL_BOX: bytes per box, 32 (two 16-B loads) or 24 (three 8-B
+// loads); see DESIGN.md appendix for the A/B.
+#ifndef VRT_LEAF_CULL
+#define VRT_LEAF_CULL 1
+#endif
+#ifndef VRT_LEAF_CULL_BOX
+#define VRT_LEAF_CULL_BOX 24
+#endif
+static_assert(VRT_LEAF_CULL_BOX == 24 || VRT_LEAF_CULL_BOX == 32, "VRT_LEAF_CULL_BOX");
+struct alignas(VRT_LEAF_CULL_BOX == 32 ? 16 : 8) RefBox {
+        float bmin[3];
+        float bmax[3];
+#if VRT_LEAF_CULL_BOX == 32
+        uint32_t pad[2];
+#endif
+};
+static_assert(sizeof(RefBox) == VRT_LEAF_CULL_BOX, "RefBox size");
+// Spare boxes below the last record's: the cull loop loads a leaf's boxes in
+// groups and a group may run past the last leaf's end (never used, only
+// loaded), so the array is allocated with this many more.
+constexpr int kRefBoxPad = 7;
+
 // Shading attributes of one triangle (64 B): normalised vertex normals
 // (Triangle::Triangle, VRT/voxel_octree.cc:426), uvs, material id.
 struct alignas(16) TriAttr {

@@ -829,6 +829,92 @@ __device__ __forceinline__ bool leaf_box_ok(const DevScene &sc, const RayK &r)
                fabsf(r.o.z - sc.lb_center[2]) <= sc.lb_reach;
 }
 
+// The culling leaf loop of the finite-slab walk (RefRec48 scenes, rays under
+// leaf_box_ok; RefBox in vrt_internal.h): the leaf's records in blocks of 32,
+// ascending.  Pass 1 tests the block's record boxes with line_meets_box,
+// kG boxes' loads issued together (the boxes are dense and their addresses
+// known up front, unlike the chain of 48-B record loads), and keeps one mask
+// bit per survivor; pass 2 runs mt_record on the survivors, lowest bit
+// first.  A culled record is one intersect_triangle3 rejects, and the
+// survivors are tested in leaf order, so the first strict minimum -- and with
+// it (tri, u, v, hit) -- is leaf_isect_v2's.
+// `cull` is wave-uniform: off (rays beyond lb_reach, or no lane's leaf holds
+// VRT_LEAF_CULL_MIN records) every record survives and the loop is
+// leaf_isect_v2's; one loop serves both, so the walk holds one copy of the
+// triangle test and its registers.  VRT_LEAF_CULL_GROUP: kG.  A/B in
+// DESIGN.md's appendix.
+#ifndef VRT_LEAF_CULL_MIN
+#define VRT_LEAF_CULL_MIN 4
+#endif
+#ifndef VRT_LEAF_CULL_GROUP
+#define VRT_LEAF_CULL_GROUP 4
+#endif
+constexpr uint32_t kCullBlock = 32;
+static_assert(VRT_LEAF_CULL_GROUP >= 1 && kCullBlock % VRT_LEAF_CULL_GROUP == 0 &&
+                      VRT_LEAF_CULL_GROUP <= kRefBoxPad + 1,
+              "VRT_LEAF_CULL_GROUP");
+__device__ __forceinline__ void load_ref_box(const RefBox *__restrict__ q, float bmin[3], float bmax[3])
+{
+#if VRT_LEAF_CULL_BOX == 32
+        const float4 a = reinterpret_cast<const float4 *>(q)[0];
+        const float2 b = reinterpret_cast<const float2 *>(q)[2];
+        bmin[0] = a.x, bmin[1] = a.y, bmin[2] = a.z;
+        bmax[0] = a.w, bmax[1] = b.x, bmax[2] = b.y;
+#else
+        const float2 a = reinterpret_cast<const float2 *>(q)[0];
+        const float2 b = reinterpret_cast<const float2 *>(q)[1];
+        const float2 c = reinterpret_cast<const float2 *>(q)[2];
+        bmin[0] = a.x, bmin[1] = a.y, bmin[2] = b.x;
+        bmax[0] = b.y, bmax[1] = c.x, bmax[2] = c.y;
+#endif
+}
+__device__ __forceinline__ bool leaf_isect_cull(const void *__restrict__ refs, uint32_t first, uint32_t n,
+                                                const RayK &r, MarchResult &m, bool cull)
+{
+        constexpr uint32_t kG = VRT_LEAF_CULL_GROUP;
+        const RefRec48 *__restrict__ recs = static_cast<const RefRec48 *>(refs);
+        // record j's box: boxes[-j] (the boxes grow downward from refs)
+        const RefBox *__restrict__ boxes = static_cast<const RefBox *>(refs) - 1;
+        bool any = false;
+        float best = 0.f, best_t = 0.f;
+        // `first` and `n` advance block by block: one live counter per lane
+        // fewer than a block offset beside them
+#pragma unroll 1
+        do {
+                const uint32_t nb = min(n, kCullBlock);
+                uint32_t mask = cull ? 0u : 0xFFFFFFFFu >> (kCullBlock - nb);
+#pragma unroll 1
+                for (uint32_t k = 0; cull && k < nb; k += kG) {
+                        float bmn[kG][3], bmx[kG][3];
+                        // one address, kG constant offsets; past the leaf's end
+                        // the group reads the next leaf's boxes, or the array's
+                        // kRefBoxPad spare boxes (their mask bits stay clear)
+                        const RefBox *__restrict__ bk = boxes - (ptrdiff_t)(first + k);
+#pragma unroll
+                        for (uint32_t g = 0; g < kG; ++g)
+                                load_ref_box(bk - (ptrdiff_t)g, bmn[g], bmx[g]);
+#pragma unroll
+                        for (uint32_t g = 0; g < kG; ++g) {
+                                const bool keep = line_meets_box(bmn[g], bmx[g], r) && k + g < nb;
+                                mask |= (uint32_t)keep << (k + g);
+                        }
+                }
+#pragma unroll 1
+                while (mask) {
+                        const uint32_t j = (uint32_t)__builtin_ctz(mask);
+                        mask &= mask - 1u;
+                        const float4 *q = reinterpret_cast<const float4 *>(recs + first + j);
+                        const float4 q0 = q[0], q1 = q[1], q2 = q[2];
+                        mt_record<false>(q0, q1, q2, double2{}, double2{}, double2{}, r, any, best, best_t, m);
+                }
+                first += nb;
+                n -= nb;
+        } while (n);
+        if (any)
+                m.hp = r.o + r.d * best_t;
+        return any;
+}
+
 // gi::ray_march (VRT/voxel_octree.cc:131-188).  stk_* are this lane's LDS
 // stack columns (stride kBlock).  The finite-slab fast walk (kStd == 2)
 // reads DevScene::xnodes and skips a node whose triangles' box the ray's
@@ -836,7 +922,9 @@ __device__ __forceinline__ bool leaf_box_ok(const DevScene &sc, const RayK &r)
 // finds no record).
 // kBudget > 0: the walk gives up (m.deferred) before a leaf that would take
 // its triangle tests past kBudget; a caller re-walks such a ray elsewhere.
-template <bool kCount, bool kFast, int kS, int kStd, int kUni, bool kR64, int kBudget = 0>
+// kCullAsk: the finite-slab walk of a RefRec48 scene tests a leaf's records
+// through leaf_isect_cull (the primary render's and k_ray_march's walks).
+template <bool kCount, bool kFast, int kS, int kStd, int kUni, bool kR64, int kBudget = 0, bool kCullAsk = false>
 __device__ __forceinline__ void ray_march(const DevScene &sc, const RayK &r,
                                           uint2 *stk,
                                           uint32_t *stk_aux,
@@ -853,6 +941,7 @@ __device__ __forceinline__ void ray_march(const DevScene &sc, const RayK &r,
         uint32_t a, b;
         constexpr bool kLB = kFast && kStd == 2 && !kCount;
         constexpr bool kNB = kLB;  // every visited node by its triangle box
+        constexpr bool kCull = VRT_LEAF_CULL && kCullAsk && kLB && !kR64;
         const NodeRec *__restrict__ nodes = sc.nodes;  // kNB: xnodes instead
         const bool lbok = kLB && __all(leaf_box_ok(sc, r));  // wave-uniform: held in SGPRs
         load_node(sc.nodes, 0, bmin, bmax, a, b);
@@ -1006,7 +1095,12 @@ __device__ __forceinline__ void ray_march(const DevScene &sc, const RayK &r,
                         ++dg_lp;
                         dg_tri += nref;
                 }
-                const bool lh = leaf_isect<kCount, kUni, kR64>(sc, b, nref, r, m);
+                bool lh;
+                if (kCull)
+                        lh = leaf_isect_cull(sc.refs, b, nref, r, m,
+                                             lbok && __any(nref >= (uint32_t)VRT_LEAF_CULL_MIN));
+                else
+                        lh = leaf_isect<kCount, kUni, kR64>(sc, b, nref, r, m);
 #if VRT_PHASE_STAMPS
                 d_tleaf += __builtin_amdgcn_s_memtime() - d_t1;
 #endif
@@ -1105,14 +1199,14 @@ __device__ __forceinline__ bool fin_ok(const RayK &r)
                fabsf(r.dinv.z) <= 0x1p64f;
 }
 
-template <bool kCount, int kS, int kUni, bool kR64, int kBudget = 0>
+template <bool kCount, int kS, int kUni, bool kR64, int kBudget = 0, bool kCullAsk = false>
 __device__ __forceinline__ void ray_march_dispatch(const DevScene &sc, const RayK &r,
                                                    uint2 *sb, uint32_t *sa, uint32_t *pr,
                                                    MarchResult &m)
 {
         if (__all(sc.fast_ok && fast_ok(r))) {
                 if (!kCount && __all(fin_ok(r)))
-                        ray_march<kCount, true, kS, 2, kUni, kR64, kBudget>(sc, r, sb, sa, pr, m);
+                        ray_march<kCount, true, kS, 2, kUni, kR64, kBudget, kCullAsk>(sc, r, sb, sa, pr, m);
                 else
                         ray_march<kCount, true, kS, 0, kUni, kR64, kBudget>(sc, r, sb, sa, pr, m);
         } else
@@ -1868,7 +1962,7 @@ __device__ __forceinline__ bool render_unit(const RenderParams &p, int k, int wa
                 if (lane_now() == 0)
                         atomicAdd(&g_phase[21], d_m0 - d_r0);
 #endif
-                ray_march<false, true, kS, kFastStd, true, kR64>(p.sc, r, stk, nullptr, nullptr, m);
+                ray_march<false, true, kS, kFastStd, true, kR64, 0, true>(p.sc, r, stk, nullptr, nullptr, m);
 #if VRT_PHASE_STAMPS
                 d_m1 = __builtin_amdgcn_s_memtime();
                 if (lane_now() == 0)
@@ -2163,7 +2257,7 @@ __global__ __launch_bounds__(kBlock) void k_ray_march(DevScene sc,
         const RayK r = make_rayk(mk3(rr[0], rr[1], rr[2]), mk3(rr[3], rr[4], rr[5]),
                                  rr[6], rr[7]);
         MarchResult m;
-        ray_march_dispatch<false, kBlock, true, kR64>(sc, r, stk + tid, nullptr, nullptr, m);
+        ray_march_dispatch<false, kBlock, true, kR64, 0, true>(sc, r, stk + tid, nullptr, nullptr, m);
         uint32_t *o = out + 9 * i;
         if (m.hit) {
                 f3 nrm;
@@ -4870,6 +4964,11 @@ bool build_flag(const char *name, int64_t *value)
                 { "VRT_DEAL_SPAN", VRT_DEAL_SPAN },
                 { "VRT_LIGHT_BUDGET", VRT_LIGHT_BUDGET },
                 { "VRT_PRIM_BUDGET", VRT_PRIM_BUDGET },
+                { "VRT_LEAF_CULL", VRT_LEAF_CULL },
+                { "VRT_LEAF_CULL_BOX", VRT_LEAF_CULL_BOX },
+                { "VRT_LEAF_CULL_GROUP", VRT_LEAF_CULL_GROUP },
+                { "VRT_LEAF_CULL_MIN", VRT_LEAF_CULL_MIN },
+                { "VRT_LEAF_CULL_BLOCK", kCullBlock },
         };
         for (const auto &f : kFlags)
                 if (std::strcmp(f.name, name) == 0) {
