@@ -346,6 +346,23 @@ int vrt_device_selftest_order(int device, const float *dist,
                               const int32_t *len, int64_t m, int32_t stride,
                               int32_t *argmin);
 
+/* The walk's chain order (the travorder order of a node's hit children from
+ * the ray's octant alone) on arbitrary expansions.  Per case
+ * i: cases[21i..21i+20] = node box min, max, ray origin, direction, root box
+ * min, max, ord_wmin (the scene constant, vrt_scene_chain_spacing) ->
+ * out[6i..6i+5] = {hit mask of the 8 children, sorted order | count << 24,
+ * chain order | count << 24, general-form chain order | count << 24, flags
+ * (1 the ray passes the criterion, 2 the hit set is a chain, 4 the same by
+ * the general form, 8 the ray meets the finite-slab walk's preconditions),
+ * the walk's own expansion with its wave votes | count << 24}; order words
+ * hold `count` 3-bit fields, first child in bits 0-2. */
+int vrt_device_selftest_chain(int device, const float *cases, int64_t n,
+                              uint32_t *out);
+
+/* The scene's chain-order constant: per axis the smallest spacing of the two
+ * child centres over its internal nodes; zeros = the chain order is off. */
+int vrt_scene_chain_spacing(const vrt_scene *s, float out[3]);
+
 /* ---- multi-device frame (render_mt, VRT/camera.h:42-68,
  * over the GPUs of one node) --------------------------------------------------
  * One handle for the scene replicated on every device of `device_mask` (bit d

@@ -147,6 +147,8 @@ SIGNATURES = {
     "vrt_scene_scratch_bytes": (C.c_int, [_P, i64p, i64p]),
     "vrt_device_selftest_order": (C.c_int, [C.c_int, f32p, u32p, C.c_int64, u32p, f32p, i32p, C.c_int64,
                                             C.c_int32, i32p]),
+    "vrt_device_selftest_chain": (C.c_int, [C.c_int, f32p, C.c_int64, u32p]),
+    "vrt_scene_chain_spacing": (C.c_int, [_P, f32p]),
     "vrt_write_hdr_mem": (C.c_int64, [C.c_int, C.c_int, C.c_int, f32p, u8p, C.c_int64]),
     "vrt_rgbe_device": (C.c_int, [_P, C.c_int, C.c_int, C.c_int, _P, _P]),
     "vrt_write_hdr_rgbe": (C.c_int, [C.c_char_p, C.c_int, C.c_int, u8p]),

@@ -313,6 +313,14 @@ class VoxelOctree:
         return (np.array(self.info.root_min[:], np.float32), np.array(self.info.root_max[:], np.float32))
 
     @property
+    def chain_spacing(self):
+        """The chain order's scene constant (vrt_scene_chain_spacing): per axis
+        the smallest child-centre spacing of the internal nodes, zeros = off."""
+        w = np.zeros(3, np.float32)
+        check(lib().vrt_scene_chain_spacing(self.h, ptr(w, _ffi.f32p)), "vrt_scene_chain_spacing")
+        return w
+
+    @property
     def ref_record_bytes(self):
         """Bytes per leaf record of the device format (vrt_scene_ref_format):
         48, or 64 for scenes with large leaves."""
@@ -809,6 +817,20 @@ def device_selftest_order(dist, hit_mask, depth=None, lengths=None, device=0):
                                           ptr(orders, _ffi.u32p), ptr(dep, _ffi.f32p), ptr(ln, _ffi.i32p), m,
                                           stride, ptr(am, _ffi.i32p)), "vrt_device_selftest_order")
     return orders, am
+
+
+def device_selftest_chain(cases, device=0):
+    """The walk's chain-order code on arbitrary expansions
+    (vrt_device_selftest_chain): cases (n, 21) f32 = node box min, max, ray
+    origin, direction, root box min, max, ord_wmin -> (n, 6) u32 {hit mask,
+    sorted order | count << 24, chain order | count << 24, general-form chain
+    order | count << 24, flags, the walk's own expansion | count << 24}."""
+    cases = np.ascontiguousarray(np.asarray(cases, np.float32).reshape(-1, 21))
+    n = cases.shape[0]
+    out = np.zeros((n, 6), np.uint32)
+    check(lib().vrt_device_selftest_chain(device, ptr(cases, _ffi.f32p), n, ptr(out, _ffi.u32p)),
+          "vrt_device_selftest_chain")
+    return out
 
 
 def build_id():

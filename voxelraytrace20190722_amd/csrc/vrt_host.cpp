@@ -394,6 +394,9 @@ struct vrt_scene {
         // device
         void *d_mem = nullptr;
         DevScene dev{};
+        // chain order: per axis the smallest spacing of the
+        // two child centres over the internal nodes, 0 = off (chain_spacing)
+        float ord_wmin[3] = {};
         hipStream_t stream = nullptr;
         hipEvent_t ev0 = nullptr, ev1 = nullptr;
         bool timed = false;
@@ -837,6 +840,50 @@ static void march_nodes(vrt_scene *s, const vrt_scene_desc *d, std::vector<XNode
         }
 }
 
+// vrt_scene::ord_wmin: per axis the minimum over the internal nodes of
+// cm[k][1] - cm[k][0], the child centres exactly as expand_v2 makes them
+// (float operations, no contraction), the difference taken in double (exact)
+// and rounded down to float.  All zero (the chain order is off) unless the
+// scene is fast_ok, every value is finite and positive and every centre lies
+// in the root box (the bound |centre - o| <= R_k of chain_criterion).
+static void chain_spacing(vrt_scene *s)
+{
+        for (int k = 0; k < 3; ++k)
+                s->ord_wmin[k] = 0.f;
+        if (!s->dev.fast_ok || s->nodes.empty())
+                return;
+        double w[3] = { HUGE_VAL, HUGE_VAL, HUGE_VAL };
+        bool any = false, ok = true;
+        const NodeRec &root = s->nodes[0];
+        for (const NodeRec &nr : s->nodes) {
+                if (nr.a & kLeafBit)
+                        continue;
+                any = true;
+                for (int k = 0; k < 3; ++k) {
+                        const float h = (nr.bmax[k] - nr.bmin[k]) / 2.0f;
+                        const float a0 = nr.bmin[k];
+                        const float b = nr.bmin[k] + h;
+                        const float c = b + h;
+                        const float c0 = (a0 + b) * .5f;
+                        const float c1 = (b + c) * .5f;
+                        w[k] = std::min(w[k], (double)c1 - (double)c0);
+                        ok = ok && c0 >= root.bmin[k] && c0 <= root.bmax[k] && c1 >= root.bmin[k] &&
+                             c1 <= root.bmax[k];  // false for NaN
+                }
+        }
+        float f[3];
+        for (int k = 0; k < 3; ++k) {
+                ok = ok && any && std::isfinite(w[k]) && w[k] > 0.0;
+                f[k] = (float)w[k];
+                if (ok && (double)f[k] > w[k])
+                        f[k] = std::nextafter(f[k], 0.f);
+                ok = ok && f[k] > 0.f;
+        }
+        if (ok)
+                for (int k = 0; k < 3; ++k)
+                        s->ord_wmin[k] = f[k];
+}
+
 static int upload(vrt_scene *s, const vrt_scene_desc *d)
 {
         int rc = check_device(s->device);
@@ -921,6 +968,7 @@ static int upload(vrt_scene *s, const vrt_scene_desc *d)
                 s->dev.fast_ok = ok ? 1 : 0;
                 s->dev.wide_leaves = s->wide_leaves ? 1 : 0;
         }
+        chain_spacing(s);
         s->info.device_bytes = (int64_t)tot;
         HIPCHK(hipStreamCreateWithFlags(&s->stream, hipStreamNonBlocking));
         HIPCHK(hipEventCreate(&s->ev0));
@@ -1407,7 +1455,7 @@ static int render_launch(vrt_scene *s, RenderParams &p, bool instrumented, hipSt
                         return rc;
         }
         int waves = 0, units[8];
-        const hipError_t e = launch_render(p, instrumented, st, &waves, units);
+        const hipError_t e = launch_render(p, instrumented, st, &waves, units, s->ord_wmin);
         if (e != hipSuccess) {
                 if (slot >= 0)
                         queue_reset(s, slot, st);
@@ -2761,7 +2809,7 @@ extern "C" int vrt_ray_march_batch_device(vrt_scene *s, const vrt_ray *d_rays,
         if (!s || (n > 0 && (!d_rays || !d_hits)) || n < 0)
                 return fail(VRT_E_INVALID, "bad argument");
         HIPCHK(hipSetDevice(s->device));
-        HIPCHK(launch_ray_march(s->dev, d_rays, n, d_hits, static_cast<hipStream_t>(stream)));
+        HIPCHK(launch_ray_march(s->dev, d_rays, n, d_hits, static_cast<hipStream_t>(stream), s->ord_wmin));
         return VRT_OK;
 }
 
@@ -2800,7 +2848,7 @@ extern "C" int vrt_ray_march_batch(vrt_scene *s, const vrt_ray *rays,
         }
         par_memcpy(s->h_rays, rays, (size_t)n * sizeof(vrt_ray));
         HIPCHK(hipMemcpyAsync(s->d_rays, s->h_rays, (size_t)n * sizeof(vrt_ray), hipMemcpyHostToDevice, s->stream));
-        HIPCHK(launch_ray_march(s->dev, s->d_rays, n, s->d_hits, s->stream));
+        HIPCHK(launch_ray_march(s->dev, s->d_rays, n, s->d_hits, s->stream, s->ord_wmin));
         HIPCHK(hipMemcpyAsync(s->h_hits, s->d_hits, (size_t)n * sizeof(vrt_hit), hipMemcpyDeviceToHost, s->stream));
         HIPCHK(hipStreamSynchronize(s->stream));
         par_memcpy(hits, s->h_hits, (size_t)n * sizeof(vrt_hit));
@@ -3042,6 +3090,34 @@ extern "C" int vrt_device_selftest(int device, const double *mt_in,
                 HIPCHK(hipMemcpy(mt_out, b.p, (size_t)n * 4 * 8, hipMemcpyDeviceToHost));
         if (sat_in)
                 HIPCHK(hipMemcpy(sat_out, d.p, (size_t)n * 4, hipMemcpyDeviceToHost));
+        return VRT_OK;
+}
+
+extern "C" int vrt_device_selftest_chain(int device, const float *cases, int64_t n, uint32_t *out)
+{
+        if (n < 0 || (n > 0 && (!cases || !out)))
+                return fail(VRT_E_INVALID, "bad argument");
+        if (int rc = check_device(device))
+                return rc;
+        if (n == 0)
+                return VRT_OK;
+        HIPCHK(hipSetDevice(device));
+        DevBuf din, dout;
+        HIPCHK(hipMalloc(&din.p, (size_t)n * 21 * sizeof(float)));
+        HIPCHK(hipMalloc(&dout.p, (size_t)n * 6 * sizeof(uint32_t)));
+        HIPCHK(hipMemcpy(din.p, cases, (size_t)n * 21 * sizeof(float), hipMemcpyHostToDevice));
+        HIPCHK(launch_selftest_chain(static_cast<float *>(din.p), n, static_cast<uint32_t *>(dout.p), nullptr));
+        HIPCHK(hipDeviceSynchronize());
+        HIPCHK(hipMemcpy(out, dout.p, (size_t)n * 6 * sizeof(uint32_t), hipMemcpyDeviceToHost));
+        return VRT_OK;
+}
+
+extern "C" int vrt_scene_chain_spacing(const vrt_scene *s, float out[3])
+{
+        if (!s || !out)
+                return fail(VRT_E_INVALID, "null argument");
+        for (int k = 0; k < 3; ++k)
+                out[k] = s->ord_wmin[k];
         return VRT_OK;
 }
 

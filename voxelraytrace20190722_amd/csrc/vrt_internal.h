@@ -569,14 +569,16 @@ int64_t camera_defer_bound(const CamParams &c);
 // *q_waves = the failing adds each slice counter receives (the waves
 // launched that visit it), slice_units[x] = the units of slice x (all 0 when
 // no work queue was used), for the queue bases
+// ord_wmin: the scene's child-centre spacings of the chain order (3 floats,
+// vrt_scene::ord_wmin; nullptr or zeros = sort every expansion)
 hipError_t launch_render(const RenderParams &p, bool instrumented,
-                         hipStream_t st, int *q_waves, int slice_units[8]);
+                         hipStream_t st, int *q_waves, int slice_units[8], const float *ord_wmin = nullptr);
 // resident blocks of the persistent render / secondary kernels on the
 // current device
 hipError_t persistent_blocks(int *render_blocks, int *sec_blocks);
 bool secondary_uses_queue(const DevScene &sc);
 hipError_t launch_ray_march(const DevScene &sc, const void *d_rays,
-                            int64_t n, void *d_hits, hipStream_t st);
+                            int64_t n, void *d_hits, hipStream_t st, const float *ord_wmin = nullptr);
 hipError_t launch_unpack(int nx, int ny, int ntx, int nty, int nranks,
                          int tiles_per_rank, const float *src, float *dst,
                          hipStream_t st);
@@ -639,6 +641,9 @@ hipError_t launch_rgbe(const float *img, int64_t npx, int comp, uint8_t *out, hi
 hipError_t launch_selftest_order(const float *dist, const uint32_t *hm, int64_t n, uint32_t *out,
                                  const float *depth, const int32_t *len, int64_t m, int32_t stride,
                                  int32_t *argmin, hipStream_t st);
+// per case: in[21i..] = node box min, max, ray o, d, root box min, max,
+// ord_wmin -> out[6i..] (k_selftest_chain)
+hipError_t launch_selftest_chain(const float *in, int64_t n, uint32_t *out, hipStream_t st);
 hipError_t launch_selftest(const double *mt_in, double *mt_out,
                            const float *sat_in, int32_t *sat_out, int64_t n,
                            hipStream_t st);

@@ -338,6 +338,107 @@ __device__ __forceinline__ uint32_t net4_order(DistOf dist_of, uint32_t hm)
         return (id[0] & 7u) | ((id[1] & 7u) << 3) | ((id[2] & 7u) << 6) | ((id[3] & 7u) << 9);
 }
 
+// ---------------------------------------------------------------------------
+// Chain order (VRT_CHAIN_ORDER): the travorder order of a node's
+// hit children without their distances.  With s = the mask of the ray's
+// negative direction components in child-index bit order (x = bit 2), child
+// ci's canonical code is ci ^ s: 0 is the octant the ray enters first on
+// every axis.  Two children are comparable when one code contains the other;
+// the contained one has the smaller key dot(d, centre - o) by a sum of terms
+// |d_k| * (centre spacing on axis k), all of one sign.  When chain_criterion
+// holds that gap exceeds the fp32 rounding of the two keys, so the
+// reference's float sort must order a set of pairwise comparable children (a
+// chain: at most 4, strictly growing codes) by code.  A set that is no chain
+// is reported (valid = false) and ordered by the sort as before.
+// ---------------------------------------------------------------------------
+#ifndef VRT_CHAIN_ORDER
+#define VRT_CHAIN_ORDER 1
+#endif
+
+// The ray's octant mask.
+__device__ __forceinline__ uint32_t chain_signs(const RayK &r)
+{
+        return ((__float_as_uint(r.d.x) >> 31) << 2) | ((__float_as_uint(r.d.y) >> 31) << 1) |
+               (__float_as_uint(r.d.z) >> 31);
+}
+
+// The same, remade where it is used: opaque, so not hoisted out of the walk's
+// loop and held across it.
+__device__ __forceinline__ uint32_t chain_signs_now(const RayK &r)
+{
+        uint32_t x = __float_as_uint(r.d.x), y = __float_as_uint(r.d.y), z = __float_as_uint(r.d.z);
+        asm volatile("" : "+v"(x), "+v"(y), "+v"(z));
+        return ((x >> 31) << 2) | ((y >> 31) << 1) | (z >> 31);
+}
+
+// Per ray: does the smallest key gap of two comparable children, min_k |d_k|
+// * wmin_k (wmin: the scene's smallest child-centre spacing per axis, 0 =
+// off), exceed 16 * 2^-24 * T, T = sum_k |d_k| * R_k >= every sum of |key
+// terms| (R_k = the origin's largest distance to the root box's planes on
+// axis k; the child centres lie in the root box)?  Each key is within
+// 5 * 2^-24 * T of its exact value; T >= 2^-100 keeps the
+// underflow of a key term (< 2^-149, denormals are kept) far below that.
+__device__ __forceinline__ bool chain_criterion(const float rmin[3], const float rmax[3], const RayK &r,
+                                                const float wmin[3])
+{
+        const float oo[3] = { r.o.x, r.o.y, r.o.z };
+        const float dd[3] = { r.d.x, r.d.y, r.d.z };
+        float T = 0.0f, gap = 0.0f;
+#pragma unroll
+        for (int k = 0; k < 3; ++k) {
+                const float ad = fabsf(dd[k]);
+                const float R = fmaxf(fabsf(rmin[k] - oo[k]), fabsf(rmax[k] - oo[k]));
+                T += ad * R;
+                const float g = ad * wmin[k];
+                gap = k ? fminf(gap, g) : g;
+        }
+        return gap > 0x1p-20f * T && T >= 0x1p-100f;  // false for NaN
+}
+
+// At most 2 hit children (i0 < i1): i1 goes first iff i0 lies on the far side
+// on every axis where they differ.
+__device__ __forceinline__ uint32_t chain_order2(uint32_t hm, uint32_t s, bool &valid)
+{
+        const uint32_t i0 = (uint32_t)__builtin_ctz(hm | 0x100u);
+        const uint32_t m1 = hm & (hm - 1u);
+        const uint32_t i1 = (uint32_t)__builtin_ctz(m1 | 0x100u);
+        const uint32_t x = (i0 ^ i1) & 7u;
+        const uint32_t a = (i0 ^ s) & x;
+        const bool two = m1 != 0u;
+        valid = !two | (a == 0u) | (a == x);
+        const bool sw = two & (a == x);
+        return sw ? (i1 | ((i0 & 7u) << 3)) : ((i0 & 7u) | ((i1 & 7u) << 3));
+}
+
+// Any number of hit children: the canonical mask hc (bit ci ^ s = bit ci of
+// hm; xor by 4 / 2 / 1 swaps its nibbles / bit pairs / bits) is a chain iff
+// it holds at most one one-bit code (1, 2, 4), at most one two-bit code (3,
+// 5, 6), and no complementary pair of them (1|6, 2|5, 4|3: the only
+// one-bit / two-bit pairs that are not nested); 0 and 7 are comparable with
+// every code.  Nested codes grow numerically, so the order is hc's set bits
+// from the lowest.  Fields past the count are unspecified.
+__device__ __forceinline__ uint32_t chain_order4(uint32_t hm, uint32_t s, bool &valid)
+{
+        uint32_t hc = hm;
+        uint32_t t = ((hc & 0x0Fu) << 4) | (hc >> 4);
+        hc = (s & 4u) ? t : hc;
+        t = ((hc & 0x33u) << 2) | ((hc >> 2) & 0x33u);
+        hc = (s & 2u) ? t : hc;
+        t = ((hc & 0x55u) << 1) | ((hc >> 1) & 0x55u);
+        hc = (s & 1u) ? t : hc;
+        const uint32_t l1 = hc & 0x16u, l2 = hc & 0x68u;
+        const uint32_t bad = (l1 & (l1 - 1u)) | (l2 & (l2 - 1u)) | (hc & (__brev(hc) >> 24) & 0x16u);
+        valid = bad == 0u;
+        uint32_t order = 0;
+#pragma unroll
+        for (int k = 0; k < 4; ++k) {
+                const uint32_t c = (uint32_t)__builtin_ctz(hc | 0x100u);
+                order |= ((c ^ s) & 7u) << (3 * k);
+                hc &= hc - 1u;
+        }
+        return order;
+}
+
 // Expand an internal node with box [bmin,bmax]: slab-test its 8 children
 // (boxes from split()'s exact arithmetic) and return the hit children in
 // travorder order, 3 bits each (first child in bits 0-2); cnt = number.
@@ -443,10 +544,17 @@ __device__ __forceinline__ uint32_t expand_v1(const float bmin[3],
 // from t1 >= tmin when t0 <= t1, and neither endpoint can be +inf), i.e.
 // max(t0, tmin) <= t1: tmin is folded into one axis's near distances once
 // per expansion, leaving max3, min3 and one compare per child.
-template <int kStd>  // 0 or 2
+// kChain (kStd == 2 only): when the wave's rays all pass chain_criterion
+// (chain_on, wave-uniform; cs = chain_signs) the hit children are ordered by
+// chain_order2 / chain_order4, and only an expansion in which some lane's hit
+// set is no chain computes the centres and sorts, for the whole wave.
+// kRecs: the octant mask is remade per expansion (the walk: one VGPR fewer
+// across the leaf loop) instead of taken from cs.
+template <int kStd, bool kChain = false, bool kRecs = false>  // kStd: 0 or 2
 __device__ __forceinline__ uint32_t expand_v2(const float bmin[3], const float bmax[3], const RayK &r, int &cnt,
-                                              uint32_t content)
+                                              uint32_t content, bool chain_on = false, uint32_t cs = 0)
 {
+        static_assert(!kChain || kStd == 2, "the chain order is the finite-slab walk's");
         const float oo[3] = { r.o.x, r.o.y, r.o.z };
         const float dd[3] = { r.d.x, r.d.y, r.d.z };
         const float di[3] = { r.dinv.x, r.dinv.y, r.dinv.z };
@@ -457,8 +565,10 @@ __device__ __forceinline__ uint32_t expand_v2(const float bmin[3], const float b
                 const float a0 = bmin[k];
                 const float b = bmin[k] + h;
                 const float c = b + h;
-                cm[k][0] = (a0 + b) * .5f;  // child centres (AABB::center)
-                cm[k][1] = (b + c) * .5f;
+                if (!kChain) {
+                        cm[k][0] = (a0 + b) * .5f;  // child centres (AABB::center)
+                        cm[k][1] = (b + c) * .5f;
+                }
                 if (!kStd) {  // eager: cheaper in registers for the secondary-ray kernels
                         cm[k][0] = dd[k] * (cm[k][0] - oo[k]);
                         cm[k][1] = dd[k] * (cm[k][1] - oo[k]);
@@ -499,6 +609,26 @@ __device__ __forceinline__ uint32_t expand_v2(const float bmin[3], const float b
         cnt = n;
         if (__all(n <= 1))
                 return (uint32_t)__builtin_ctz(hm | 0x100u) & 7u;  // one or no hit child: nothing to order
+        if (kChain) {
+                if (chain_on) {
+                        bool valid;
+                        if (kRecs)
+                                cs = chain_signs_now(r);
+                        const uint32_t ord = __all(n <= 2) ? chain_order2(hm, cs, valid) : chain_order4(hm, cs, valid);
+                        if (__all(valid))
+                                return ord;
+                }
+                // the sort's centres, from the same operations as above
+#pragma unroll
+                for (int k = 0; k < 3; ++k) {
+                        const float h = (bmax[k] - bmin[k]) / 2.0f;
+                        const float a0 = bmin[k];
+                        const float b = bmin[k] + h;
+                        const float c = b + h;
+                        cm[k][0] = (a0 + b) * .5f;
+                        cm[k][1] = (b + c) * .5f;
+                }
+        }
         // travorder distances dot(d, centre - o), finished only when some
         // lane orders >= 2 children (camera rays, kStd)
         float q[3][2];
@@ -526,14 +656,15 @@ __device__ __forceinline__ uint32_t expand_v2(const float bmin[3], const float b
         return net4_order(dist_of, hm);
 }
 
-template <bool kFullPos, bool kFast, int kStd = 0>
+template <bool kFullPos, bool kFast, int kStd = 0, bool kChain = false>
 __device__ __forceinline__ uint32_t expand(const float bmin[3],
                                            const float bmax[3],
                                            const RayK &r, int &cnt,
-                                           uint32_t &full_pos, uint32_t content)
+                                           uint32_t &full_pos, uint32_t content, bool chain_on = false,
+                                           uint32_t cs = 0)
 {
         if (kFast && !kFullPos)
-                return expand_v2<kStd>(bmin, bmax, r, cnt, content);
+                return expand_v2<kStd, kChain, kChain>(bmin, bmax, r, cnt, content, chain_on, cs);
         return expand_v1<kFullPos, kFast>(bmin, bmax, r, cnt, full_pos, content);
 }
 
@@ -924,12 +1055,19 @@ __device__ __forceinline__ bool leaf_isect_cull(const void *__restrict__ refs, u
 // its triangle tests past kBudget; a caller re-walks such a ray elsewhere.
 // kCullAsk: the finite-slab walk of a RefRec48 scene tests a leaf's records
 // through leaf_isect_cull (the primary render's and k_ray_march's walks).
-template <bool kCount, bool kFast, int kS, int kStd, int kUni, bool kR64, int kBudget = 0, bool kCullAsk = false>
+// kChainAsk: the finite-slab walk orders the hit children by the chain order
+// (expand_v2<2, true>) when every ray of the wave passes chain_criterion with
+// the scene's centre spacings cw (the same two walks).
+struct ChainW {
+        float wmin[3];  // vrt_scene's ord_wmin; 0 = off
+};
+template <bool kCount, bool kFast, int kS, int kStd, int kUni, bool kR64, int kBudget = 0, bool kCullAsk = false,
+          bool kChainAsk = false>
 __device__ __forceinline__ void ray_march(const DevScene &sc, const RayK &r,
                                           uint2 *stk,
                                           uint32_t *stk_aux,
                                           uint32_t *path_rem,
-                                          MarchResult &m)
+                                          MarchResult &m, float cw0 = 0.0f, float cw1 = 0.0f, float cw2 = 0.0f)
 {
         m.hit = false;
         m.deferred = false;
@@ -942,9 +1080,17 @@ __device__ __forceinline__ void ray_march(const DevScene &sc, const RayK &r,
         constexpr bool kLB = kFast && kStd == 2 && !kCount;
         constexpr bool kNB = kLB;  // every visited node by its triangle box
         constexpr bool kCull = VRT_LEAF_CULL && kCullAsk && kLB && !kR64;
+        constexpr bool kChain = VRT_CHAIN_ORDER && kChainAsk && kLB;
         const NodeRec *__restrict__ nodes = sc.nodes;  // kNB: xnodes instead
         const bool lbok = kLB && __all(leaf_box_ok(sc, r));  // wave-uniform: held in SGPRs
         load_node(sc.nodes, 0, bmin, bmax, a, b);
+        // wave-uniform for the whole walk (bmin / bmax: the root box), voted
+        // by every lane that entered, before any leaves
+        bool chain_on = false;
+        if (kChain) {
+                const float wmin[3] = { cw0, cw1, cw2 };
+                chain_on = __all(chain_criterion(bmin, bmax, r, wmin));
+        }
         if (!aabb_isect(bmin, bmax, r.o, r.dinv, r.tmin, r.tmax))
                 return;
         if (a & kLeafBit) {
@@ -958,7 +1104,8 @@ __device__ __forceinline__ void ray_march(const DevScene &sc, const RayK &r,
         }
         int cnt;
         uint32_t fpos;
-        uint32_t order = expand<kCount, kFast, kStd>(bmin, bmax, r, cnt, fpos, kCount ? 0xFFu : b);
+        const uint32_t cs = 0u;  // remade per expansion (expand_v2's kRecs)
+        uint32_t order = expand<kCount, kFast, kStd, kChain>(bmin, bmax, r, cnt, fpos, kCount ? 0xFFu : b, chain_on, cs);
         uint32_t base = a;
         uint32_t depth = 1;  // depth of the node whose children we walk
         uint32_t nexp = 1;
@@ -1037,7 +1184,8 @@ __device__ __forceinline__ void ray_march(const DevScene &sc, const RayK &r,
                                                 stk_aux[sp * kS] = fpos | (depth << 24);
                                         ++sp;
                                 }
-                                order = expand<kCount, kFast, kStd>(bmin, bmax, r, cnt, fpos, kCount ? 0xFFu : b);
+                                order = expand<kCount, kFast, kStd, kChain>(bmin, bmax, r, cnt, fpos, kCount ? 0xFFu : b,
+                                                                            chain_on, cs);
 #if VRT_PHASE_STAMPS
                                 {
                                         const uint32_t ld = wave_lead();
@@ -1199,14 +1347,16 @@ __device__ __forceinline__ bool fin_ok(const RayK &r)
                fabsf(r.dinv.z) <= 0x1p64f;
 }
 
-template <bool kCount, int kS, int kUni, bool kR64, int kBudget = 0, bool kCullAsk = false>
+template <bool kCount, int kS, int kUni, bool kR64, int kBudget = 0, bool kCullAsk = false, bool kChainAsk = false>
 __device__ __forceinline__ void ray_march_dispatch(const DevScene &sc, const RayK &r,
                                                    uint2 *sb, uint32_t *sa, uint32_t *pr,
-                                                   MarchResult &m)
+                                                   MarchResult &m, float cw0 = 0.0f, float cw1 = 0.0f,
+                                                   float cw2 = 0.0f)
 {
         if (__all(sc.fast_ok && fast_ok(r))) {
                 if (!kCount && __all(fin_ok(r)))
-                        ray_march<kCount, true, kS, 2, kUni, kR64, kBudget, kCullAsk>(sc, r, sb, sa, pr, m);
+                        ray_march<kCount, true, kS, 2, kUni, kR64, kBudget, kCullAsk, kChainAsk>(sc, r, sb, sa, pr, m,
+                                                                                                 cw0, cw1, cw2);
                 else
                         ray_march<kCount, true, kS, 0, kUni, kR64, kBudget>(sc, r, sb, sa, pr, m);
         } else
@@ -1894,7 +2044,8 @@ constexpr int kRenderBlock = 64;
 // caller defers the unit to k_render_defer.
 template <bool kCount, bool kR64, int kS, bool kSamples = true, bool kFastOnly = false>
 __device__ __forceinline__ bool render_unit(const RenderParams &p, int k, int wave, int lane, uint2 *stk,
-                                            uint32_t *stk_aux, uint32_t *path_rem)
+                                            uint32_t *stk_aux, uint32_t *path_rem, float cw0 = 0.0f, float cw1 = 0.0f,
+                                            float cw2 = 0.0f)
 {
         // the lane id is re-read per unit (volatile asm: not hoisted out of
         // a persistent loop), so its derived per-lane constants are
@@ -1962,7 +2113,8 @@ __device__ __forceinline__ bool render_unit(const RenderParams &p, int k, int wa
                 if (lane_now() == 0)
                         atomicAdd(&g_phase[21], d_m0 - d_r0);
 #endif
-                ray_march<false, true, kS, kFastStd, true, kR64, 0, true>(p.sc, r, stk, nullptr, nullptr, m);
+                ray_march<false, true, kS, kFastStd, true, kR64, 0, true, true>(p.sc, r, stk, nullptr, nullptr, m, cw0, cw1,
+                                                                                cw2);
 #if VRT_PHASE_STAMPS
                 d_m1 = __builtin_amdgcn_s_memtime();
                 if (lane_now() == 0)
@@ -2122,7 +2274,7 @@ constexpr int kPersistHelp = 2;
 #define VRT_PERSIST_WAVES_PER_EU 6
 #endif
 template <bool kFastOnly>
-__global__ __launch_bounds__(kPersistBlock, VRT_PERSIST_WAVES_PER_EU) void k_render_p(RenderParams p)
+__global__ __launch_bounds__(kPersistBlock, VRT_PERSIST_WAVES_PER_EU) void k_render_p(RenderParams p, ChainW cw)
 {
         __shared__ uint2 stk[kStack * kPersistBlock];
         const int tid = threadIdx.x, lane = tid & 63;
@@ -2151,7 +2303,7 @@ __global__ __launch_bounds__(kPersistBlock, VRT_PERSIST_WAVES_PER_EU) void k_ren
                         const uint32_t dg_u0 = (uint32_t)__builtin_amdgcn_s_memrealtime();
 #endif
                         const bool done = render_unit<false, false, kPersistBlock, false, kFastOnly>(
-                                p, kq >> 2, kq & 3, lane, stk + tid, nullptr, nullptr);
+                                p, kq >> 2, kq & 3, lane, stk + tid, nullptr, nullptr, cw.wmin[0], cw.wmin[1], cw.wmin[2]);
 #if VRT_UNIT_DIAG
                         {
                                 const uint32_t dg_u1 = (uint32_t)__builtin_amdgcn_s_memrealtime();
@@ -2246,7 +2398,7 @@ template <bool kR64>
 __global__ __launch_bounds__(kBlock) void k_ray_march(DevScene sc,
                                                       const float *__restrict__ rays,
                                                       int64_t n,
-                                                      uint32_t *__restrict__ out)
+                                                      uint32_t *__restrict__ out, ChainW cw)
 {
         __shared__ uint2 stk[kStack * kBlock];
         const int tid = threadIdx.x;
@@ -2257,7 +2409,8 @@ __global__ __launch_bounds__(kBlock) void k_ray_march(DevScene sc,
         const RayK r = make_rayk(mk3(rr[0], rr[1], rr[2]), mk3(rr[3], rr[4], rr[5]),
                                  rr[6], rr[7]);
         MarchResult m;
-        ray_march_dispatch<false, kBlock, true, kR64, 0, true>(sc, r, stk + tid, nullptr, nullptr, m);
+        ray_march_dispatch<false, kBlock, true, kR64, 0, true, !kR64>(sc, r, stk + tid, nullptr, nullptr, m, cw.wmin[0],
+                                                                      cw.wmin[1], cw.wmin[2]);
         uint32_t *o = out + 9 * i;
         if (m.hit) {
                 f3 nrm;
@@ -3405,6 +3558,61 @@ __global__ void k_selftest_order(const float *__restrict__ dist, const uint32_t 
         }
 }
 
+// The walk's own chain-order code on arbitrary expansions.  Per
+// case i: in[21i..] = node box min, max, ray o, d (tmin = +0, tmax =
+// FLT_MAX), root box min, max, ord_wmin ->
+//   out[6i+0] the hit mask of the 8 children (all present)
+//   out[6i+1] expand_v2<2>'s sorted order | count << 24
+//   out[6i+2] the chain order of the form the walk takes for this count
+//             (chain_order2 up to 2 hit children, else chain_order4) | count << 24
+//   out[6i+3] chain_order4 | count << 24
+//   out[6i+4] bit 0 chain_criterion, bit 1 / 2 the set is a chain by the
+//             form of [2] / by chain_order4, bit 3 the ray meets the
+//             finite-slab walk's preconditions (fast_ok, fin_ok)
+//   out[6i+5] expand_v2<2, true> as the walk calls it (the wave's votes on
+//             the criterion and on the sets) | count << 24
+// order words hold the first `count` 3-bit fields only.
+__global__ void k_selftest_chain(const float *__restrict__ in, int64_t n, uint32_t *__restrict__ out)
+{
+        const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+        if (i >= n)
+                return;
+        const float *p = in + 21 * i;
+        const float bmin[3] = { p[0], p[1], p[2] }, bmax[3] = { p[3], p[4], p[5] };
+        const float rmin[3] = { p[12], p[13], p[14] }, rmax[3] = { p[15], p[16], p[17] };
+        const float wmin[3] = { p[18], p[19], p[20] };
+        const RayK r = make_rayk(mk3(p[6], p[7], p[8]), mk3(p[9], p[10], p[11]), 0.0f, kFltMax);
+        const bool pre = fast_ok(r) && fin_ok(r);
+        int cnt = 0;
+        const uint32_t sorted = expand_v2<2>(bmin, bmax, r, cnt, 0xFFu);
+        const uint32_t keep = cnt >= 8 ? 0xFFFFFFu : (1u << (3 * cnt)) - 1u;
+        uint32_t hm = 0;
+        for (int k = 0; k < cnt; ++k)
+                hm |= 1u << ((sorted >> (3 * k)) & 7u);
+        const uint32_t cs = chain_signs(r);
+        const bool crit = chain_criterion(rmin, rmax, r, wmin);
+        bool v2 = false, v4 = false;
+        const uint32_t o2 = chain_order2(hm, cs, v2);
+        const uint32_t o4 = chain_order4(hm, cs, v4);
+        int cnt_w = 0;
+        const uint32_t walk = expand_v2<2, true>(bmin, bmax, r, cnt_w, 0xFFu, __all(crit), cs);
+        const uint32_t c24 = (uint32_t)cnt << 24;
+        out[6 * i + 0] = hm;
+        out[6 * i + 1] = (sorted & keep) | c24;
+        out[6 * i + 2] = ((cnt <= 2 ? o2 : o4) & keep & 0xFFFu) | c24;
+        out[6 * i + 3] = (o4 & keep & 0xFFFu) | c24;
+        out[6 * i + 4] = (crit ? 1u : 0u) | ((cnt <= 2 ? v2 : v4) ? 2u : 0u) | (v4 ? 4u : 0u) | (pre ? 8u : 0u);
+        out[6 * i + 5] = (walk & keep) | ((uint32_t)cnt_w << 24);
+}
+
+hipError_t launch_selftest_chain(const float *in, int64_t n, uint32_t *out, hipStream_t st)
+{
+        if (n <= 0)
+                return hipSuccess;
+        hipLaunchKernelGGL(k_selftest_chain, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, in, n, out);
+        return hipGetLastError();
+}
+
 hipError_t launch_selftest_order(const float *dist, const uint32_t *hm, int64_t n, uint32_t *out,
                                  const float *depth, const int32_t *len, int64_t m, int32_t stride,
                                  int32_t *argmin, hipStream_t st)
@@ -3589,9 +3797,19 @@ hipError_t persistent_blocks(int *render_blocks, int *sec_blocks)
         return e;
 }
 
-hipError_t launch_render(const RenderParams &p, bool instrumented,
-                         hipStream_t st, int *q_waves, int slice_units[8])
+static ChainW chain_w(const float *ord_wmin)
 {
+        ChainW cw{};
+        if (ord_wmin)
+                for (int k = 0; k < 3; ++k)
+                        cw.wmin[k] = ord_wmin[k];
+        return cw;
+}
+
+hipError_t launch_render(const RenderParams &p, bool instrumented,
+                         hipStream_t st, int *q_waves, int slice_units[8], const float *ord_wmin)
+{
+        const ChainW cw = chain_w(ord_wmin);
         *q_waves = 0;
         for (int x = 0; x < 8; ++x)
                 slice_units[x] = 0;
@@ -3610,7 +3828,7 @@ hipError_t launch_render(const RenderParams &p, bool instrumented,
                 const int cap = std::max(8, p.nranks > 1 ? full - kCollectiveReserve : full);
                 const int g = std::min(cap, need);
                 if (kind == kRenderPersistFast) {
-                        hipLaunchKernelGGL(k_render_p<true>, dim3(g), dim3(kPersistBlock), 0, st, p);
+                        hipLaunchKernelGGL(k_render_p<true>, dim3(g), dim3(kPersistBlock), 0, st, p, cw);
                         if (hipError_t e = hipGetLastError())
                                 return e;
 #if VRT_UNIT_DIAG
@@ -3653,7 +3871,7 @@ hipError_t launch_render(const RenderParams &p, bool instrumented,
                                 hipLaunchKernelGGL(k_render_defer, dim3(gd), dim3(kPersistBlock), 0, st, p);
                         }
                 } else {
-                        hipLaunchKernelGGL(k_render_p<false>, dim3(g), dim3(kPersistBlock), 0, st, p);
+                        hipLaunchKernelGGL(k_render_p<false>, dim3(g), dim3(kPersistBlock), 0, st, p, cw);
                 }
                 // failing adds per slice counter: one from every wave of the
                 // kPersistHelp XCDs that visit it (g/8 blocks per XCD)
@@ -3671,7 +3889,7 @@ hipError_t launch_render(const RenderParams &p, bool instrumented,
 }
 
 hipError_t launch_ray_march(const DevScene &sc, const void *d_rays, int64_t n,
-                            void *d_hits, hipStream_t st)
+                            void *d_hits, hipStream_t st, const float *ord_wmin)
 {
         if (n <= 0)
                 return hipSuccess;
@@ -3679,7 +3897,7 @@ hipError_t launch_ray_march(const DevScene &sc, const void *d_rays, int64_t n,
         hipLaunchKernelGGL(sc.wide_leaves ? k_ray_march<true> : k_ray_march<false>, dim3((unsigned)grid),
                            dim3(kBlock), 0, st,
                            sc, static_cast<const float *>(d_rays), n,
-                           static_cast<uint32_t *>(d_hits));
+                           static_cast<uint32_t *>(d_hits), chain_w(ord_wmin));
         return hipGetLastError();
 }
 
@@ -4964,6 +5182,7 @@ bool build_flag(const char *name, int64_t *value)
                 { "VRT_DEAL_SPAN", VRT_DEAL_SPAN },
                 { "VRT_LIGHT_BUDGET", VRT_LIGHT_BUDGET },
                 { "VRT_PRIM_BUDGET", VRT_PRIM_BUDGET },
+                { "VRT_CHAIN_ORDER", VRT_CHAIN_ORDER },
                 { "VRT_LEAF_CULL", VRT_LEAF_CULL },
                 { "VRT_LEAF_CULL_BOX", VRT_LEAF_CULL_BOX },
                 { "VRT_LEAF_CULL_GROUP", VRT_LEAF_CULL_GROUP },
