@@ -304,6 +304,9 @@ int vrt_device_selftest(int device, const double *mt_in, double *mt_out,
  * rank count) makes vrt_trace_batch[_device] work in chunks of 200 rays, so
  * the chunk seams are reached by small batches. */
 #define VRT_TEST_SMALL_BATCH_CHUNK 0x10000
+/* VRT_TEST_SMALL_PROBE_CHUNK (the bit after it, unused before) makes
+ * vrt_probe_gather[_device] work in chunks of 2 probes. */
+#define VRT_TEST_SMALL_PROBE_CHUNK 0x20000
 int vrt_set_test_flags(int flags);
 /* The current vrt_set_test_flags value (so a caller can restore it). */
 int vrt_test_flags(void);
@@ -325,8 +328,8 @@ int vrt_secondary_spill_stats(vrt_scene *s, int64_t stats[7]);
  * (vrt_scene_info().device_bytes): per-call scratch kept between calls --
  * config 5's compaction queues (*spill_bytes, may be NULL), the light-map
  * build's scratch and light-map sets, the trace records (the frames' and
- * the batched trace's one chunk share them), the device staging of the
- * host-array batched trace, the host-output image, the tabled tile deals of multi-rank calls (4 B per tile of the
+ * the batched trace's and the probe gather's one chunk share them), the
+ * device staging of the host-array batched trace and probe gather, the host-output image, the tabled tile deals of multi-rank calls (4 B per tile of the
  * rank). */
 int vrt_scene_scratch_bytes(vrt_scene *s, int64_t *bytes, int64_t *spill_bytes);
 
@@ -485,6 +488,52 @@ int vrt_cone_trace_batch(vrt_scene *s, const vrt_isect *isects, int64_t n, float
                          float *rgb /* 3n */);
 int vrt_cone_trace_batch_device(vrt_scene *s, const vrt_isect *d_isects, int64_t n,
                                 float min_voxel, float *d_rgb, void *stream);
+
+/* ---- light probes (gi::LightProbe, gi::SG; VRT/voxel_octree.h:120-163,
+ * VRT/voxel_octree.cc:497-632) -------------------------------------------
+ * LightProbe::gather_light(root, res, light_dir, light_color) for many
+ * probes at once, on the scene's current light map: for each of the 14
+ * directions dirs_[i] (6 axes, then the 8 cube diagonals) and each sample
+ * point r_j the ray Ray{o, r_j + dirs_[i] * 2.6131f, r + res} (tmin = r +
+ * res, tmax = FLT_MAX) is marched; a miss adds light_color, a hit
+ * cone_trace(root, isect, res); the sum over the points, in point order from
+ * zero, divided by (float)npoints is the amplitude of sgs[14 p + i] =
+ * SG{litness, dirs_[i], 10}.  light_dir is unused by the reference and is
+ * not a parameter.  The marches record no albedo and no direct term. */
+#define VRT_PROBE_SGS 14
+#define VRT_PROBE_MAX_POINTS 1024
+typedef struct { float o[3]; float r; } vrt_probe;
+/* gi::SG: amplitude, axis (normalised by the constructor), sharpness */
+typedef struct { float a[3]; float d[3]; float s; } vrt_sg;
+
+/* The points LightProbe::LightProbe draws: jql::PCG{seed}, n (1..1024)
+ * calls of random_point_in_unit_sphere; pts = 3n floats.  seed 0xc01dbeef,
+ * n = 100: the reference's points (every probe has the same ones). */
+int vrt_probe_points(uint64_t seed, int n, float *pts);
+/* Host arrays.  min_voxel <= 0: the scene's Res.  points == NULL: the
+ * reference's 100 points (npoints is ignored); else npoints (1..1024) points
+ * of the caller's.  sgs: 14 n records.  terms (may be NULL): 3 * 14 *
+ * npoints * n floats, the value each ray added to litness, ray index
+ * (p * 14 + i) * npoints + j.  n == 0 is VRT_OK and touches nothing;
+ * VRT_E_INVALID without a light map.  Works in chunks of whole probes
+ * (about 2^20 rays): the scratch is the batched trace's record block and
+ * staging and does not grow with n. */
+int vrt_probe_gather(vrt_scene *s, const vrt_probe *probes, int64_t n, float min_voxel,
+                     const float light_color[3], const float *points, int npoints, vrt_sg *sgs,
+                     float *terms);
+/* Device-resident variant: d_probes, d_sgs, d_terms in HBM (points stays a
+ * host array: it travels in kernel arguments), enqueued on `stream` with no
+ * host synchronisation; ordered with frames in flight and trace batches
+ * through the light-map set's event, as vrt_trace_batch_device; reads the
+ * light map that is current when it is enqueued. */
+int vrt_probe_gather_device(vrt_scene *s, const vrt_probe *d_probes, int64_t n, float min_voxel,
+                            const float light_color[3], const float *points, int npoints,
+                            vrt_sg *d_sgs, float *d_terms, void *stream);
+/* LightProbe::eval on the host: rgb[(p * m + k) * 3 ..] = the sum over probe
+ * p's 14 lobes, in order from zero, of SG::eval(dirs[k]) = a * expf(s *
+ * (dot(dir, d) - 1)), with the C library's expf (the pinned contract, as the
+ * cone step table's log2f).  dirs: 3m floats, used as they are. */
+int vrt_probe_eval(const vrt_sg *sgs, int64_t n, const float *dirs, int64_t m, float *rgb);
 
 /* ---- output (VRT/stb_image_write.h:178,723-757) ------------------------- */
 /* Byte-identical to stbi_write_hdr: returns 1 on success, 0 on failure. */

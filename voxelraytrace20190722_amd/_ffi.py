@@ -63,6 +63,16 @@ class TraceParts(C.Structure):
                 ("albedo", C.c_void_p)]
 
 
+class Probe(C.Structure):
+    """vrt_probe: LightProbe's centre and radius."""
+    _fields_ = [("o", C.c_float * 3), ("r", C.c_float)]
+
+
+class SGRec(C.Structure):
+    """vrt_sg: gi::SG {a, d, s} (28 bytes)."""
+    _fields_ = [("a", C.c_float * 3), ("d", C.c_float * 3), ("s", C.c_float)]
+
+
 class SceneInfo(C.Structure):
     _fields_ = [("nodes", C.c_int64), ("internal", C.c_int64),
                 ("leaves", C.c_int64), ("nonempty_leaves", C.c_int64),
@@ -134,6 +144,11 @@ SIGNATURES = {
     "vrt_trace_batch_device": (C.c_int, [_P, _P, C.c_int64, C.c_float, _P, C.POINTER(TraceParts), _P]),
     "vrt_cone_trace_batch": (C.c_int, [_P, C.POINTER(ISect), C.c_int64, C.c_float, f32p]),
     "vrt_cone_trace_batch_device": (C.c_int, [_P, _P, C.c_int64, C.c_float, _P, _P]),
+    "vrt_probe_points": (C.c_int, [C.c_uint64, C.c_int, f32p]),
+    "vrt_probe_gather": (C.c_int, [_P, C.POINTER(Probe), C.c_int64, C.c_float, f32p, f32p, C.c_int,
+                                   C.POINTER(SGRec), f32p]),
+    "vrt_probe_gather_device": (C.c_int, [_P, _P, C.c_int64, C.c_float, f32p, f32p, C.c_int, _P, _P, _P]),
+    "vrt_probe_eval": (C.c_int, [C.POINTER(SGRec), C.c_int64, f32p, C.c_int64, f32p]),
     "vrt_device_selftest": (C.c_int, [C.c_int, f64p, f64p, f32p, i32p, C.c_int64]),
     "vrt_write_hdr": (C.c_int, [C.c_char_p, C.c_int, C.c_int, C.c_int, f32p]),
     "stbi_write_hdr": (C.c_int, [C.c_char_p, C.c_int, C.c_int, C.c_int, f32p]),

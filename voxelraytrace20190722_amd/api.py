@@ -581,6 +581,43 @@ class VoxelOctree:
                                                 None if stream_ptr is None else C.c_void_p(stream_ptr)),
               "vrt_cone_trace_batch_device")
 
+    # ---- light probes (LightProbe::gather_light, batched) ----
+    def probe_gather(self, probes, min_voxel=0.0, light_color=(1.0, 1.0, 1.0), points=None, terms=False):
+        """LightProbe::gather_light (VRT/voxel_octree.cc:592-618) for (n, 4)
+        probes {o, r} -> SGs as a dict a (n, 14, 3), d (n, 14, 3), s (n, 14).
+        points: (npoints, 3) sample points of the caller's (None: the
+        reference's 100).  terms=True also returns (n, 14, npoints, 3): what
+        each ray added to litness."""
+        probes = np.asarray(probes, np.float32)
+        if probes.ndim != 2 or probes.shape[1] != 4:
+            raise ValueError(f"probes must be (n, 4) {{o, r}}, got {probes.shape}")
+        probes = np.ascontiguousarray(probes)
+        pts, npts = _probe_points_arg(points)
+        lc = _f3(light_color)
+        n = probes.shape[0]
+        sgs = np.zeros((n, PROBE_SGS, 7), np.float32)
+        tm = np.zeros((n, PROBE_SGS, npts, 3), np.float32) if terms else None
+        check(lib().vrt_probe_gather(self.h, probes.ctypes.data_as(C.POINTER(_ffi.Probe)), n, float(min_voxel),
+                                     ptr(lc, _ffi.f32p), ptr(pts, _ffi.f32p), npts if pts is not None else 0,
+                                     sgs.ctypes.data_as(C.POINTER(_ffi.SGRec)), ptr(tm, _ffi.f32p)),
+              "vrt_probe_gather")
+        out = {"a": sgs[:, :, 0:3].copy(), "d": sgs[:, :, 3:6].copy(), "s": sgs[:, :, 6].copy()}
+        return (out, tm) if terms else out
+
+    def probe_gather_device(self, d_probes_ptr, n, d_sgs_ptr, min_voxel=0.0, light_color=(1.0, 1.0, 1.0),
+                            points=None, d_terms_ptr=None, stream_ptr=None):
+        """vrt_probe_gather_device: raw device pointers (n vrt_probe in, 14 n
+        vrt_sg out, optional 3 * 14 * npoints * n floats of terms), enqueued
+        on the stream; points stays a host array."""
+        pts, npts = _probe_points_arg(points)
+        lc = _f3(light_color)
+        check(lib().vrt_probe_gather_device(self.h, C.c_void_p(d_probes_ptr), int(n), float(min_voxel),
+                                            ptr(lc, _ffi.f32p), ptr(pts, _ffi.f32p),
+                                            npts if pts is not None else 0, C.c_void_p(d_sgs_ptr),
+                                            None if d_terms_ptr is None else C.c_void_p(d_terms_ptr),
+                                            None if stream_ptr is None else C.c_void_p(stream_ptr)),
+              "vrt_probe_gather_device")
+
 
 class MultiOctree:
     """The octree replicated on every device of a mask, with an RCCL
@@ -676,6 +713,88 @@ def trace(tree, rays, min_voxel=0.0, parts=False):
 def cone_trace(tree, hit_p, normal, min_voxel=0.0):
     """gi::cone_trace(root, isect, min_voxel_size) (VRT/voxel_octree.h), batched."""
     return tree.cone_trace(hit_p, normal, min_voxel)
+
+
+# ---- light probes (gi::SG, gi::LightProbe; VRT/voxel_octree.h:120-163) ----
+PROBE_SGS = 14  # include/vrt.h VRT_PROBE_SGS
+# LightProbe::dirs_ (VRT/voxel_octree.h:156-160): the 6 axes, the 8 diagonals
+PROBE_DIRS = np.array([(1, 0, 0), (0, 1, 0), (0, 0, 1), (-1, 0, 0), (0, -1, 0), (0, 0, -1), (1, 1, 1), (1, 1, -1),
+                       (1, -1, 1), (1, -1, -1), (-1, 1, 1), (-1, 1, -1), (-1, -1, 1), (-1, -1, -1)], np.float32)
+
+
+def probe_points(seed=0xc01dbeef, n=100):
+    """The sample points LightProbe::LightProbe draws (vrt_probe_points):
+    jql::PCG{seed}, n calls of random_point_in_unit_sphere -> (n, 3)."""
+    n = int(n)
+    pts = np.zeros((max(n, 0), 3), np.float32)
+    check(lib().vrt_probe_points(int(seed) & 0xFFFFFFFFFFFFFFFF, n, ptr(pts, _ffi.f32p)), "vrt_probe_points")
+    return pts
+
+
+def _probe_points_arg(points):
+    """(array or None, npoints) for the gather calls."""
+    if points is None:
+        return None, 100
+    pts = np.asarray(points, np.float32)
+    if pts.ndim != 2 or pts.shape[1] != 3:
+        raise ValueError(f"points must be (npoints, 3), got {pts.shape}")
+    return np.ascontiguousarray(pts), pts.shape[0]
+
+
+def probe_eval(sgs, dirs):
+    """LightProbe::eval (vrt_probe_eval): sgs = the dict probe_gather returns
+    (a, d (n, 14, 3), s (n, 14)), dirs (m, 3) -> (n, m, 3)."""
+    a, d, s = (np.asarray(sgs[k], np.float32) for k in ("a", "d", "s"))
+    if a.ndim != 3 or a.shape[1:] != (PROBE_SGS, 3) or d.shape != a.shape or s.shape != a.shape[:2]:
+        raise ValueError(f"sgs must hold a, d (n, 14, 3) and s (n, 14), got {a.shape}, {d.shape}, {s.shape}")
+    dirs = np.asarray(dirs, np.float32)
+    if dirs.ndim != 2 or dirs.shape[1] != 3:
+        raise ValueError(f"dirs must be (m, 3), got {dirs.shape}")
+    dirs = np.ascontiguousarray(dirs)
+    rec = np.ascontiguousarray(np.concatenate([a, d, s[:, :, None]], axis=2))
+    n, m = rec.shape[0], dirs.shape[0]
+    rgb = np.zeros((n, m, 3), np.float32)
+    check(lib().vrt_probe_eval(rec.ctypes.data_as(C.POINTER(_ffi.SGRec)), n, ptr(dirs, _ffi.f32p), m,
+                               ptr(rgb, _ffi.f32p)), "vrt_probe_eval")
+    return rgb
+
+
+class SG:
+    """gi::SG (VRT/voxel_octree.cc:497-508): amplitude a, axis d (normalised
+    by the library when it comes from a gather), sharpness s."""
+
+    def __init__(self, a, d, s):
+        self.a, self.d, self.s = _f3(a), _f3(d), np.float32(s)
+
+    def eval(self, dir):
+        """a * expf(s * (dot(dir, d) - 1)): one lobe through vrt_probe_eval
+        (the other 13 lobes of the record are zero and add +0)."""
+        sgs = {"a": np.zeros((1, PROBE_SGS, 3), np.float32), "d": np.zeros((1, PROBE_SGS, 3), np.float32),
+               "s": np.zeros((1, PROBE_SGS), np.float32)}
+        sgs["a"][0, 0], sgs["d"][0, 0], sgs["s"][0, 0] = self.a, self.d, self.s
+        return probe_eval(sgs, _f3(dir)[None, :])[0, 0]
+
+
+class LightProbe:
+    """gi::LightProbe(o, r) (VRT/voxel_octree.cc:530-632): gather_light fills
+    the 14 SGs on the GPU (one probe of VoxelOctree.probe_gather; gather many
+    probes with that call), eval sums them."""
+
+    def __init__(self, o, r):
+        self.o, self.r = _f3(o), np.float32(r)
+        self.sgs = None
+
+    def gather_light(self, tree, res, light_color):
+        probe = np.concatenate([self.o, [self.r]]).astype(np.float32)[None, :]
+        g = tree.probe_gather(probe, res, light_color)
+        self._rec = g
+        self.sgs = [SG(g["a"][0, i], g["d"][0, i], g["s"][0, i]) for i in range(PROBE_SGS)]
+        return self.sgs
+
+    def eval(self, dir):
+        if self.sgs is None:
+            raise ValueError("LightProbe.eval before gather_light")
+        return probe_eval(self._rec, _f3(dir)[None, :])[0, 0]
 
 
 def render(tree, cam, film, **kw):
@@ -856,6 +975,7 @@ TEST_LIGHT_TAIL = 32  # include/vrt.h VRT_TEST_LIGHT_TAIL
 TEST_PRIM_TAIL = 64  # include/vrt.h VRT_TEST_PRIM_TAIL
 TEST_SEC_DEFER = 128  # include/vrt.h VRT_TEST_SEC_DEFER
 TEST_SMALL_BATCH_CHUNK = 0x10000  # include/vrt.h VRT_TEST_SMALL_BATCH_CHUNK
+TEST_SMALL_PROBE_CHUNK = 0x20000  # include/vrt.h VRT_TEST_SMALL_PROBE_CHUNK
 
 
 def set_test_flags(flags):

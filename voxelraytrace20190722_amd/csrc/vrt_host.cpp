@@ -3063,6 +3063,237 @@ extern "C" int vrt_cone_trace_batch(vrt_scene *s, const vrt_isect *isects, int64
         return batch_host(s, isects, sizeof(vrt_isect), false, n, min_voxel, out, out_sz);
 }
 
+// ---- light probes (gi::LightProbe, gi::SG; VRT/voxel_octree.cc:497-632) ----
+// jql::PCG::operator() (VRT/graphics_math.h:839-853)
+static uint32_t pcg_next_host(uint64_t &s)
+{
+        s = s * 6364136223846793005ULL + 1442695040888963407ULL;
+        const uint32_t xorshift = (uint32_t)((s ^ (s >> 18u)) >> 27u);
+        const uint32_t shift = (uint32_t)(s >> 59u);
+        return (xorshift >> shift) | (xorshift << ((0u - shift) & 31u));
+}
+
+// libstdc++'s uniform_real_distribution<float>{-1, 1} over a 32-bit
+// generator: generate_canonical<float, 24> = float(g) / 2^32 (below 1), then
+// u * (1 - -1) + -1 -- the mapping the config-5 kernels use
+static float uniform_m11_host(uint64_t &s)
+{
+        float sum = 0.0f;
+        sum += (float)pcg_next_host(s) * 1.0f;
+        float ret = sum / 4294967296.0f;
+        if (ret >= 1.0f)
+                ret = 0.99999994f;  // nextafter(1.f, 0.f)
+        return (ret * (1.0f - -1.0f)) + -1.0f;
+}
+
+// jql::random_point_in_unit_sphere (VRT/graphics_math.h:1208-1216): three
+// draws in x, y, z order until length(r) < 1
+static void probe_points_host(uint64_t seed, int n, float *pts)
+{
+        uint64_t st = seed;
+        for (int i = 0; i < n; ++i)
+                for (;;) {
+                        const float x = uniform_m11_host(st);
+                        const float y = uniform_m11_host(st);
+                        const float z = uniform_m11_host(st);
+                        if (length(mk3(x, y, z)) < 1.f) {
+                                pts[3 * i + 0] = x;
+                                pts[3 * i + 1] = y;
+                                pts[3 * i + 2] = z;
+                                break;
+                        }
+                }
+}
+
+extern "C" int vrt_probe_points(uint64_t seed, int n, float *pts)
+{
+        if (!pts || n < 1 || n > kProbeMaxPoints)
+                return fail(VRT_E_INVALID, "bad argument: %d points (1..%d)", n, kProbeMaxPoints);
+        probe_points_host(seed, n, pts);
+        return VRT_OK;
+}
+
+// LightProbe::eval (VRT/voxel_octree.cc:626-632): the 14 lobes' SG::eval
+// a * expf(s * (dot(dir, d) - 1)) (:503-508) added in order from zero
+extern "C" int vrt_probe_eval(const vrt_sg *sgs, int64_t n, const float *dirs, int64_t m, float *rgb)
+{
+        static_assert(sizeof(vrt_sg) == 28, "vrt_sg layout");
+        static_assert(sizeof(vrt_probe) == 16, "vrt_probe layout");
+        static_assert(kProbeSGs == VRT_PROBE_SGS && kProbeMaxPoints == VRT_PROBE_MAX_POINTS, "vrt.h constants");
+        if (n < 0 || m < 0)
+                return fail(VRT_E_INVALID, "bad argument");
+        if (n == 0 || m == 0)
+                return VRT_OK;
+        if (!sgs || !dirs || !rgb)
+                return fail(VRT_E_INVALID, "null argument");
+        for (int64_t pi = 0; pi < n; ++pi)
+                for (int64_t k = 0; k < m; ++k) {
+                        const f3 dir = mk3(dirs[3 * k], dirs[3 * k + 1], dirs[3 * k + 2]);
+                        f3 lit = mk3(0.f, 0.f, 0.f);
+                        for (int i = 0; i < VRT_PROBE_SGS; ++i) {
+                                const vrt_sg &g = sgs[pi * VRT_PROBE_SGS + i];
+                                const float tmp = dot(dir, mk3(g.d[0], g.d[1], g.d[2]));
+                                const float e = expf(g.s * (tmp - 1));
+                                lit = lit + mk3(g.a[0], g.a[1], g.a[2]) * e;
+                        }
+                        float *o = rgb + (pi * m + k) * 3;
+                        o[0] = lit.x;
+                        o[1] = lit.y;
+                        o[2] = lit.z;
+                }
+        return VRT_OK;
+}
+
+// probes per chunk: 14 * npoints records each in the set's record block
+static int64_t probe_chunk(int npoints)
+{
+        if (g_test_flags.load() & VRT_TEST_SMALL_PROBE_CHUNK)
+                return 2;
+        return std::max<int64_t>(1, kBatchChunk / ((int64_t)kProbeSGs * npoints));
+}
+
+// One gather on stream st over device arrays (caller holds s->mu, the device
+// is set, a light map exists), as batch_enqueue: the current set's light
+// map, step table and record block, taken and released through its event.
+static int probe_enqueue(vrt_scene *s, const ProbeIO &io0, const float *host_points, float min_voxel,
+                         hipStream_t st)
+{
+        const int set = s->lm_cur;
+        TraceParams tp0, tp;
+        std::memset(&tp0, 0, sizeof tp0);
+        tp0.r.sc = s->dev;
+        tp0.r.test_flags = g_test_flags.load();
+        fill_trace_light(s, set, min_voxel, &tp0);
+        ProbeIO io = io0;
+        io.res = min_voxel;
+        if (!(io.res > 0.f))
+                vrt_scene_min_voxel(s, 0, &io.res);
+        const int64_t chunk = probe_chunk(io.npoints);
+        const size_t nslots = (size_t)std::min(io.n, chunk) * kProbeSGs * io.npoints;
+        if (int rc = trace_scratch_n(s, set, tp0, nslots, &tp))
+                return rc;
+        if (int rc = ts_acquire(s, set, st))
+                return rc;
+        (void)hipGetLastError();  // a leftover error of an earlier call is not this launch's
+        const hipError_t e = launch_probe_gather(tp, io, host_points, chunk, st);
+        if (e != hipSuccess) {
+                (void)ts_release(s, set, st);
+                return fail(VRT_E_DEVICE, "probe gather launch failed: %s", hipGetErrorString(e));
+        }
+        if (tp.build_steps) {  // k_cone_steps is enqueued (steps_commit)
+                s->ts[set].steps_key[0] = tp.mindist;
+                s->ts[set].steps_key[1] = tp.maxdist;
+        }
+        return ts_release(s, set, st);
+}
+
+// the arguments both variants share; *empty: n == 0, nothing to do
+static int probe_args_ok(vrt_scene *s, const void *probes, int64_t n, const float *light_color,
+                         const float *points, int npoints, const void *sgs, bool *empty)
+{
+        *empty = false;
+        if (!s || n < 0)
+                return fail(VRT_E_INVALID, "bad argument");
+        if (n == 0) {
+                *empty = true;
+                return VRT_OK;
+        }
+        if (need_device(s))
+                return VRT_E_NODEVICE;
+        if (!probes || !light_color || !sgs)
+                return fail(VRT_E_INVALID, "null argument");
+        if (points && (npoints < 1 || npoints > kProbeMaxPoints))
+                return fail(VRT_E_INVALID, "bad argument: %d points (1..%d)", npoints, kProbeMaxPoints);
+        return VRT_OK;
+}
+
+// the reference's own points (every LightProbe draws the same 100)
+static const float *probe_default_points()
+{
+        static const std::vector<float> pts = [] {
+                std::vector<float> v(300);
+                probe_points_host(0xc01dbeefULL, 100, v.data());
+                return v;
+        }();
+        return pts.data();
+}
+
+extern "C" int vrt_probe_gather_device(vrt_scene *s, const vrt_probe *d_probes, int64_t n, float min_voxel,
+                                       const float light_color[3], const float *points, int npoints,
+                                       vrt_sg *d_sgs, float *d_terms, void *stream)
+{
+        bool empty;
+        if (int rc = probe_args_ok(s, d_probes, n, light_color, points, npoints, d_sgs, &empty))
+                return rc;
+        if (empty)
+                return VRT_OK;
+        if (int rc = trace_ok(s, min_voxel))
+                return rc;
+        std::lock_guard<std::mutex> lk(s->mu);
+        if (s->lm_cur < 0)
+                return fail(VRT_E_INVALID, "no light map: call vrt_lightmap_build first");
+        HIPCHK(hipSetDevice(s->device));
+        ProbeIO io{};
+        io.probes = reinterpret_cast<const float *>(d_probes);
+        io.n = n;
+        io.npoints = points ? npoints : 100;
+        std::memcpy(io.light, light_color, sizeof io.light);
+        io.sgs = reinterpret_cast<float *>(d_sgs);
+        io.terms = d_terms;
+        return probe_enqueue(s, io, points ? points : probe_default_points(), min_voxel,
+                             static_cast<hipStream_t>(stream));
+}
+
+// Host arrays: chunk by chunk through the batched trace's staging (one
+// chunk's probes, SGs and terms), one host sync per chunk.
+extern "C" int vrt_probe_gather(vrt_scene *s, const vrt_probe *probes, int64_t n, float min_voxel,
+                                const float light_color[3], const float *points, int npoints, vrt_sg *sgs,
+                                float *terms)
+{
+        bool empty;
+        if (int rc = probe_args_ok(s, probes, n, light_color, points, npoints, sgs, &empty))
+                return rc;
+        if (empty)
+                return VRT_OK;
+        if (int rc = trace_ok(s, min_voxel))
+                return rc;
+        std::lock_guard<std::mutex> lk(s->mu);
+        if (s->lm_cur < 0)
+                return fail(VRT_E_INVALID, "no light map: call vrt_lightmap_build first");
+        HIPCHK(hipSetDevice(s->device));
+        const int np = points ? npoints : 100;
+        const float *pts = points ? points : probe_default_points();
+        const int64_t m = std::min(n, probe_chunk(np));
+        const size_t sg_sz = (size_t)kProbeSGs * sizeof(vrt_sg), tm_sz = terms ? (size_t)kProbeSGs * np * 12 : 0;
+        const size_t o_sg = (size_t)m * sizeof(vrt_probe), o_tm = o_sg + (size_t)m * sg_sz;
+        if (int rc = batch_staging(s, o_tm + (size_t)m * tm_sz))
+                return rc;
+        char *d = static_cast<char *>(s->d_tb), *h = static_cast<char *>(s->h_tb);
+        for (int64_t b = 0; b < n; b += m) {
+                const int64_t c = std::min(m, n - b);
+                std::memcpy(h, probes + b, (size_t)c * sizeof(vrt_probe));
+                HIPCHK(hipMemcpyAsync(d, h, (size_t)c * sizeof(vrt_probe), hipMemcpyHostToDevice, s->stream));
+                ProbeIO io{};
+                io.probes = reinterpret_cast<const float *>(d);
+                io.n = c;
+                io.npoints = np;
+                std::memcpy(io.light, light_color, sizeof io.light);
+                io.sgs = reinterpret_cast<float *>(d + o_sg);
+                io.terms = terms ? reinterpret_cast<float *>(d + o_tm) : nullptr;
+                if (int rc = probe_enqueue(s, io, pts, min_voxel, s->stream))
+                        return rc;
+                HIPCHK(hipMemcpyAsync(h + o_sg, d + o_sg, (size_t)c * sg_sz, hipMemcpyDeviceToHost, s->stream));
+                if (terms)
+                        HIPCHK(hipMemcpyAsync(h + o_tm, d + o_tm, (size_t)c * tm_sz, hipMemcpyDeviceToHost,
+                                              s->stream));
+                HIPCHK(hipStreamSynchronize(s->stream));
+                std::memcpy(reinterpret_cast<char *>(sgs) + (size_t)b * sg_sz, h + o_sg, (size_t)c * sg_sz);
+                if (terms)
+                        par_memcpy(reinterpret_cast<char *>(terms) + (size_t)b * tm_sz, h + o_tm, (size_t)c * tm_sz);
+        }
+        return VRT_OK;
+}
+
 extern "C" int vrt_device_selftest(int device, const double *mt_in,
                                    double *mt_out, const float *sat_in,
                                    int32_t *sat_out, int64_t n)

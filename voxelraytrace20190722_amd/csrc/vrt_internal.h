@@ -534,6 +534,23 @@ struct BatchIO {
         float *indirect, *direct, *albedo;
 };
 
+// One launch of the light-probe gather (vrt_probe_gather): n probes
+// {o xyz, r} and their outputs in device memory; `points` are the host's
+// npoints sample points (launch_probe_gather puts them on the device through
+// kernel arguments, behind the trace records: TraceParams::tail).
+constexpr int kProbeSGs = 14;
+constexpr int kProbeMaxPoints = 1024;
+struct ProbeIO {
+        const float *probes;  // n x 4
+        int64_t n;
+        int32_t npoints;
+        float res;            // the ray's tmin = r + res
+        float light[3];
+        float *sgs;           // 14 n vrt_sg (7 floats each)
+        float *terms;         // 3 * 14 * npoints * n floats, or null
+        const float *points;  // device: npoints x 3 (set by the launcher)
+};
+
 // GPU octree build (vrt_build.hip): the host build's
 // arrays, produced on `device` and copied back.
 struct DeviceBuild {
@@ -630,6 +647,11 @@ hipError_t launch_cones(const TraceParams &p, hipStream_t st);
 // the batched cone_trace; both build the step table first when p.build_steps
 hipError_t launch_trace_batch(const TraceParams &p, const BatchIO &io, int64_t chunk, hipStream_t st);
 hipError_t launch_cones_batch(const TraceParams &p, const BatchIO &io, hipStream_t st);
+// the light-probe gather: io.n probes in chunks of `chunk` probes (p.rec
+// holds 14 * npoints records per probe of a chunk, p.tail the points);
+// host_points = npoints x 3 floats on the host
+hipError_t launch_probe_gather(const TraceParams &p, const ProbeIO &io, const float *host_points, int64_t chunk,
+                               hipStream_t st);
 // per-node cone-descent records and the light map's finiteness flag
 hipError_t launch_lm_aux(const NodeRec *nodes, const LMRec *lm, int64_t n, float4 *cc, uint32_t *bad,
                          hipStream_t st);

@@ -5010,6 +5010,214 @@ __global__ __launch_bounds__(64, VRT_BATCH_WAVES_PER_EU) void k_cones_batch(Trac
         }
 }
 
+// ---- light probes: LightProbe::gather_light over many probes ----------------
+// gather_light (VRT/voxel_octree.cc:592-618) for n probes {o, r}: for each of
+// the 14 directions dirs_[i] (VRT/voxel_octree.h:156-160) and each sample
+// point r_j, Ray{o, r_j + dirs_[i] * 2.6131f, r + res} is marched; a miss
+// adds light_color, a hit cone_trace(root, isect, res); the sum over the
+// points in point order from zero, divided by (float)npoints, is the
+// amplitude of SG{litness, dirs_[i], 10}.  Ray g = (probe * 14 + i) * npoints
+// + j of a chunk has the record p.rec[4g .. 4g+3]: hit point | hit flag, the
+// normal, then the value the ray adds to litness.  Three launches per chunk,
+// no host round trip between them.
+
+// dirs_[i]: the 6 axes, then the 8 cube diagonals (x, y, z negative when bit
+// 2, 1, 0 of i - 6 is set); i is wave-uniform wherever this is called
+__device__ __forceinline__ f3 probe_dir(int i)
+{
+        if (i < 6) {
+                const float s = i < 3 ? 1.0f : -1.0f;
+                const int a = i < 3 ? i : i - 3;
+                return mk3(a == 0 ? s : 0.0f, a == 1 ? s : 0.0f, a == 2 ? s : 0.0f);
+        }
+        const int k = i - 6;
+        return mk3((k & 4) ? -1.0f : 1.0f, (k & 2) ? -1.0f : 1.0f, (k & 1) ? -1.0f : 1.0f);
+}
+
+// the sample points, 256 per launch through the kernel arguments: the call
+// is enqueued without a host copy the stream would have to wait for
+struct ProbePointsArg {
+        float v[3 * 256];
+};
+__global__ __launch_bounds__(256) void k_probe_points(ProbePointsArg a, float *__restrict__ dst, int cnt)
+{
+        const int t = blockIdx.x * 256 + threadIdx.x;
+        if (t < cnt)
+                dst[t] = a.v[t];
+}
+
+// March stage: a wave takes 64 consecutive points of one (probe, direction)
+// group, so the probe and the direction are wave-uniform (the probe comes by
+// scalar loads) and a lane adds its own point: the ray is made in registers.
+// ray_march as k_trace_batch_prim runs it (degenerate rays, a NaN direction
+// included, take the exact path); the record keeps the hit flag, the hit
+// point and ray_march's normal (k_ray_march's operations) -- no albedo, no
+// texture, no direct term.
+template <bool kR64>
+__global__ __launch_bounds__(kBlock) void k_probe_march(TraceParams p, ProbeIO io)
+{
+        __shared__ uint2 stk[kStack * kBlock];
+        const int tid = threadIdx.x;
+        const int wpg = (io.npoints + 63) >> 6;  // waves per group
+        const int64_t gw = (int64_t)blockIdx.x * (kBlock / 64) + (tid >> 6);
+        const int grp = __builtin_amdgcn_readfirstlane((int)(gw / wpg));
+        const int seg = __builtin_amdgcn_readfirstlane((int)(gw - (int64_t)grp * wpg));
+        const int j = seg * 64 + (tid & 63);
+        if (grp >= kProbeSGs * io.n || j >= io.npoints)
+                return;
+        const int pr = grp / kProbeSGs, i = grp - kProbeSGs * pr;
+        typedef const __attribute__((address_space(4))) float ConstF;
+        ConstF *pb = (ConstF *)io.probes + 4 * (int64_t)pr;
+        const f3 o = mk3(pb[0], pb[1], pb[2]);
+        const float tmin = pb[3] + io.res;
+        const float *pt = io.points + 3 * j;
+        const f3 rd = mk3(pt[0], pt[1], pt[2]) + probe_dir(i) * 2.6131f;
+        const RayK r = make_rayk(o, normalize(rd), tmin, kFltMax);
+        MarchResult m;
+        ray_march_dispatch<false, kBlock, true, kR64>(p.r.sc, r, stk + tid, nullptr, nullptr, m);
+        float4 *rec = p.rec + 4 * ((int64_t)grp * io.npoints + j);
+        if (m.hit) {
+                const TriAttr *ta = p.r.sc.tri_attr + m.tri;
+                const f3 n0 = mk3(ta->n[0], ta->n[1], ta->n[2]);
+                const f3 n1 = mk3(ta->n[3], ta->n[4], ta->n[5]);
+                const f3 n2 = mk3(ta->n[6], ta->n[7], ta->n[8]);
+                const float w = clampf(1.0f - m.u - m.v, 0, 1);
+                const f3 nrm = normalize((n0 * w + n1 * m.u) + n2 * m.v);
+                rec[0] = make_float4(m.hp.x, m.hp.y, m.hp.z, 1.f);
+                rec[1] = make_float4(nrm.x, nrm.y, nrm.z, 0.f);
+        } else {
+                rec[0] = make_float4(0.f, 0.f, 0.f, 0.f);
+        }
+}
+
+// Cone stage: a lane takes one (ray, cone) as k_cones_batch does (lane =
+// 6 * r + c, kBatchRays rays per wave), the six results are summed in cone
+// order from zero by the ray's first lane, which writes the ray's term:
+// cone_trace's sum on a hit, light_color on a miss (whose lanes march
+// nothing).
+__global__ __launch_bounds__(64, VRT_BATCH_WAVES_PER_EU) void k_probe_cones(TraceParams p, ProbeIO io)
+{
+        const float hx[6] = { 0.000000f, 0.000000f, 0.823639f, 0.509037f, -0.509037f, -0.823639f };
+        const float hy[6] = { 0.000000f, 0.866025f, 0.267617f, -0.700629f, -0.700629f, 0.267617f };
+        const float hz[6] = { 1.0f, 0.5f, 0.5f, 0.5f, 0.5f, 0.5f };
+        const float hw[6] = { 0.25f, 0.15f, 0.15f, 0.15f, 0.15f, 0.15f };
+        const int lane = threadIdx.x;
+        const int rl = lane / 6, c = lane - 6 * rl;  // lanes 60-63: rl == kBatchRays
+        const int64_t nrays = (int64_t)kProbeSGs * io.n * io.npoints;
+        const int64_t i = (int64_t)blockIdx.x * kBatchRays + rl;
+        const bool live = rl < kBatchRays && i < nrays;
+        bool hit = false;
+        f3 cm = mk3(0.f, 0.f, 0.f);
+        if (live) {
+                const float4 r0 = p.rec[4 * i];
+                hit = r0.w != 0.f;
+                if (hit) {
+                        const f3 hp = mk3(r0.x, r0.y, r0.z);
+                        const float4 r1 = p.rec[4 * i + 1];
+                        const f3 n = mk3(r1.x, r1.y, r1.z);
+                        const float sg = (0.0f > n.z) ? -1.0f : 1.0f;
+                        const float a0 = -1.0f / (sg + n.z);
+                        const float a1 = n.x * n.y * a0;
+                        const f3 t = mk3(1.0f + sg * n.x * n.x * a0, sg * a1, -sg * n.x);
+                        const f3 bb = mk3(a1, sg + n.y * n.y * a0, -n.y);
+                        f3 r = mk3(0.f, 0.f, 0.f);
+                        r = r + t * hx[c];
+                        r = r + bb * hy[c];
+                        r = r + n * hz[c];
+                        const f3 cd = normalize(r);
+                        cm = cone_march(p, hp, cd);
+                }
+        }
+        // every lane is back here: the six cones of the ray, in cone order
+        const int l0 = lane - c;
+        f3 diffuse = mk3(0.f, 0.f, 0.f);
+#pragma unroll
+        for (int j = 0; j < 6; ++j) {
+                const int src = (l0 + j) & 63;
+                const f3 cj = mk3(__shfl(cm.x, src, 64), __shfl(cm.y, src, 64), __shfl(cm.z, src, 64));
+                diffuse = diffuse + cj * hw[j];
+        }
+        if (!live || c != 0)
+                return;
+        const f3 term = hit ? diffuse : mk3(io.light[0], io.light[1], io.light[2]);
+        p.rec[4 * i + 2] = make_float4(term.x, term.y, term.z, 0.f);
+        if (io.terms) {
+                io.terms[3 * i + 0] = term.x;
+                io.terms[3 * i + 1] = term.y;
+                io.terms[3 * i + 2] = term.z;
+        }
+}
+
+// Ordered reduction: one lane per (probe, direction) adds the group's terms
+// in point order from zero, one fp32 add per component and point (the
+// reference's order: no tree, no scan, no atomics), divides by
+// (float)npoints (operator/=: a division per component) and writes
+// SG{litness, normalize(dirs_[i]), 10}.
+__global__ __launch_bounds__(256) void k_probe_reduce(TraceParams p, ProbeIO io)
+{
+        const int64_t g = (int64_t)blockIdx.x * 256 + threadIdx.x;
+        if (g >= (int64_t)kProbeSGs * io.n)
+                return;
+        const float4 *t = p.rec + 4 * g * io.npoints + 2;
+        f3 lit = mk3(0.f, 0.f, 0.f);
+        // eight terms are loaded together (independent loads in flight), then
+        // added one after the other in point order
+        for (int j0 = 0; j0 < io.npoints; j0 += 8) {
+                float4 v[8];
+#pragma unroll
+                for (int k = 0; k < 8; ++k)
+                        v[k] = t[4 * (int64_t)min(j0 + k, io.npoints - 1)];
+#pragma unroll
+                for (int k = 0; k < 8; ++k)
+                        if (j0 + k < io.npoints)
+                                lit = lit + mk3(v[k].x, v[k].y, v[k].z);
+        }
+        const float fn = (float)io.npoints;
+        const f3 d = normalize(probe_dir((int)(g % kProbeSGs)));
+        float *o = io.sgs + 7 * g;
+        o[0] = lit.x / fn;
+        o[1] = lit.y / fn;
+        o[2] = lit.z / fn;
+        o[3] = d.x;
+        o[4] = d.y;
+        o[5] = d.z;
+        o[6] = 10.f;
+}
+
+hipError_t launch_probe_gather(const TraceParams &p, const ProbeIO &io, const float *host_points, int64_t chunk,
+                               hipStream_t st)
+{
+        if (io.n <= 0)
+                return hipSuccess;
+        if (p.build_steps)
+                hipLaunchKernelGGL(k_cone_steps, dim3(1), dim3(64), 0, st, p);
+        float *dpts = reinterpret_cast<float *>(p.tail);
+        for (int b = 0; b < io.npoints; b += 256) {
+                ProbePointsArg a;
+                const int cnt = 3 * std::min(256, io.npoints - b);
+                std::memcpy(a.v, host_points + 3 * b, sizeof(float) * cnt);
+                hipLaunchKernelGGL(k_probe_points, dim3((unsigned)((cnt + 255) / 256)), dim3(256), 0, st, a,
+                                   dpts + 3 * b, cnt);
+        }
+        const int64_t wpg = (io.npoints + 63) / 64;
+        for (int64_t b = 0; b < io.n; b += chunk) {
+                ProbeIO c = io;
+                c.n = std::min(chunk, io.n - b);
+                c.probes = io.probes + 4 * b;
+                c.sgs = io.sgs + 7 * kProbeSGs * b;
+                c.terms = io.terms ? io.terms + 3 * kProbeSGs * b * io.npoints : nullptr;
+                c.points = dpts;
+                const int64_t groups = kProbeSGs * c.n, waves = groups * wpg, nrays = groups * io.npoints;
+                hipLaunchKernelGGL(p.r.sc.wide_leaves ? k_probe_march<true> : k_probe_march<false>,
+                                   dim3((unsigned)((waves + kBlock / 64 - 1) / (kBlock / 64))), dim3(kBlock), 0, st, p,
+                                   c);
+                hipLaunchKernelGGL(k_probe_cones, dim3((unsigned)((nrays + kBatchRays - 1) / kBatchRays)), dim3(64),
+                                   0, st, p, c);
+                hipLaunchKernelGGL(k_probe_reduce, dim3((unsigned)((groups + 255) / 256)), dim3(256), 0, st, p, c);
+        }
+        return hipGetLastError();
+}
+
 // VRT_LIGHT_DIAG builds: the per-wave records of the last light pass
 hipError_t light_diag_copy(void *host, size_t bytes)
 {
