@@ -535,6 +535,97 @@ int vrt_probe_gather_device(vrt_scene *s, const vrt_probe *d_probes, int64_t n, 
  * cone step table's log2f).  dirs: 3m floats, used as they are. */
 int vrt_probe_eval(const vrt_sg *sgs, int64_t n, const float *dirs, int64_t m, float *rgb);
 
+/* ---- light probes as scene voxels (VRT/main.cc:56-64; LightProbe is a
+ * VoxelBase, VRT/voxel_octree.h:120-163) -----------------------------------
+ * The driver pushes its probes into the same voxel list as the triangles, so
+ * ray_march_init inserts them into the octree, and the view's trace(root,
+ * ray, 5, true) marches with even_invisible = true: a probe (is_visible() ==
+ * false, VRT/voxel_octree.cc:588-591) can then end a ray.
+ *
+ * vrt_scene_create_probes: gi::ray_march_init over the triangles followed by
+ * the probes (voxel v < ntri = triangle v, voxel ntri + k = probe k).  The
+ * root box is AABB{} merged with every triangle box and then with each
+ * probe's get_aabb() = {o - r, o + r} (VRT/voxel_octree.cc:541-544), so
+ * probes may enlarge it; each probe is inserted after all triangles by
+ * insert() (VRT/voxel_octree.cc:41-65) with LightProbe::is_overlap
+ * (VRT/voxel_octree.cc:567-586).  A leaf's list is its triangles in input
+ * order, then its probes in probe order.  nprobe == 0 or probes == NULL is
+ * vrt_scene_create_ex.  Bounds: ntri + nprobe < 2^31, o finite, r finite and
+ * >= 0 (r == 0 overlaps nothing).  VRT_BUILD_DEVICE with probes is
+ * VRT_E_INVALID: the device build inserts triangles only (out of scope here).
+ *
+ * Every visible-only call (vrt_ray_march_batch, vrt_lightmap_build's light
+ * pass, vrt_probe_gather, vrt_cone_trace_batch, vrt_render,
+ * vrt_render_secondary) runs on such a scene as the reference's ray_march(...,
+ * false) does: probes are skipped.  vrt_scene_info's nonempty_leaves and
+ * tri_refs keep their triangle meaning; nodes, internal and leaves count the
+ * whole tree.  Not available on a probe scene (VRT_E_INVALID; use
+ * vrt_trace_batch): vrt_render_trace[_device], vrt_trace_frame_device and
+ * vrt_render's instrumented counters. */
+int vrt_scene_create_probes(const vrt_scene_desc *desc, const vrt_probe *probes, int32_t nprobe,
+                            int max_depth, int device, int flags, vrt_scene **out);
+/* Probes of the scene, leaves that hold at least one probe, and the total
+ * length of their probe lists (all 0 for a scene without probes).  Any output
+ * may be NULL. */
+int vrt_scene_probe_info(const vrt_scene *s, int32_t *nprobe, int64_t *probe_leaves, int64_t *probe_refs);
+/* As vrt_scene_leaves: the leaves holding at least one probe sorted by voxel
+ * id; probes = concatenated probe indices (0-based) in list order. */
+int vrt_scene_probe_leaves(const vrt_scene *s, uint32_t *voxel, uint32_t *count, int32_t *probes);
+/* The scene's stored SGs (14 * nprobe records; zero at creation), read by a
+ * probe hit's get_albedo. */
+int vrt_scene_set_probe_sgs(vrt_scene *s, const vrt_sg *sgs);
+int vrt_scene_probe_sgs(const vrt_scene *s, vrt_sg *sgs);
+/* VRT/main.cc:104-105: gather_light for every probe of the scene with the
+ * reference's 100 points (vrt_probe_gather on the scene's own probes) into
+ * the stored SGs.  Needs a light map. */
+int vrt_scene_probes_gather(vrt_scene *s, float min_voxel, const float light_color[3]);
+
+/* LightProbe::is_overlap(AABB3D{box}) on the host (box = min xyz, max xyz):
+ * 1 / 0, negative on a NULL argument.  The float32 squared-distance test,
+ * one rounding per operation. */
+int vrt_probe_overlap(const vrt_probe *p, const float box[6]);
+/* LightProbe::isect(ray, isect) on the host (VRT/voxel_octree.cc:546-554 with
+ * jql::sphere_ray_isect / quadratic_solver, VRT/graphics_math.h:1105-1126,
+ * 1175-1206): 1 and *t, hit_p = o + t * d on success, 0 otherwise (outputs
+ * untouched).  The ray's tmin / tmax are not consulted.  The normal keeps the
+ * reference's aliasing: `*isect = ISect{hit, isect->hit - o_}` reads the
+ * ISect's hit point before it is overwritten, and ISect's constructor
+ * normalises, so normal = normalize(prev_hit - o) with prev_hit = the hit
+ * point the caller's ISect held (in a leaf: that of the last record before
+ * this one whose isect succeeded, else the march's initial ISect, zero). */
+int vrt_probe_isect(const vrt_probe *p, const vrt_ray *ray, const float prev_hit[3],
+                    float *t, float hit_p[3], float normal[3]);
+
+/* gi::ray_march's last parameter.  flags == 0, or a scene without probes:
+ * vrt_ray_march_batch.  VRT_MARCH_EVEN_INVISIBLE on a probe scene:
+ * ray_march(root, ray, .., true) -- probes are tested after a leaf's
+ * triangles, ray_march_isect's first minimum runs over the whole list, and a
+ * probe hit has tri = ntri + k, hit_p / normal as vrt_probe_isect. */
+#define VRT_MARCH_EVEN_INVISIBLE 1
+int vrt_ray_march_batch_ex(vrt_scene *s, const vrt_ray *rays, int64_t n, int flags, vrt_hit *hits);
+int vrt_ray_march_batch_ex_device(vrt_scene *s, const vrt_ray *d_rays, int64_t n, int flags,
+                                  vrt_hit *d_hits, void *stream);
+
+/* trace() on a probe scene.  vrt_trace_batch[_device] restate trace(root, ray,
+ * 5, true) (VRT/main.cc:10-30), whose ray_march passes even_invisible = true:
+ * on a probe scene they run the mixed march.  A triangle hit is shaded as on
+ * any scene (the cone march and the direct term read the probe scene's light
+ * map, in which a leaf holding only probes has coverage 1,
+ * VRT/voxel_octree.cc:192-199).  A probe hit returns get_albedo(isect) =
+ * LightProbe::eval(normalize(hit - o_)) over the scene's stored SGs
+ * (VRT/voxel_octree.cc:562-566, VRT/main.cc:25-29); parts->indirect and
+ * parts->direct are +0 there (the reference computes and discards them) and
+ * parts->albedo equals rgb.  eval needs the C library's expf (vrt_probe_eval's
+ * pinned contract), so the host-array call fills those elements on the host
+ * after the device pass; the device call writes +0 to rgb and to every part
+ * there and marks the element through hits[i].tri >= ntri.
+ * vrt_probe_shade_hits finishes such a batch on the host to the host call's
+ * bytes: for every element of `hits` (host array; a device caller copies back
+ * what it passed as d_parts->hits) that ended on a probe it writes the colour
+ * to rgb[3i..] and albedo[3i..] (host arrays, either may be NULL) and leaves
+ * every other element untouched. */
+int vrt_probe_shade_hits(vrt_scene *s, const vrt_hit *hits, int64_t n, float *rgb, float *albedo);
+
 /* ---- output (VRT/stb_image_write.h:178,723-757) ------------------------- */
 /* Byte-identical to stbi_write_hdr: returns 1 on success, 0 on failure. */
 int vrt_write_hdr(const char *filename, int w, int h, int comp,

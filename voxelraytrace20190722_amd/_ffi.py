@@ -103,6 +103,7 @@ class ObjInfo(C.Structure):
 
 VRT_OBJ_PARSE_ONLY = 1
 VRT_BUILD_DEVICE = 1
+VRT_MARCH_EVEN_INVISIBLE = 1
 
 _P = C.c_void_p
 SIGNATURES = {
@@ -149,6 +150,18 @@ SIGNATURES = {
                                    C.POINTER(SGRec), f32p]),
     "vrt_probe_gather_device": (C.c_int, [_P, _P, C.c_int64, C.c_float, f32p, f32p, C.c_int, _P, _P, _P]),
     "vrt_probe_eval": (C.c_int, [C.POINTER(SGRec), C.c_int64, f32p, C.c_int64, f32p]),
+    "vrt_scene_create_probes": (C.c_int, [C.POINTER(SceneDesc), C.POINTER(Probe), C.c_int32, C.c_int, C.c_int,
+                                          C.c_int, C.POINTER(_P)]),
+    "vrt_scene_probe_info": (C.c_int, [_P, i32p, i64p, i64p]),
+    "vrt_scene_probe_leaves": (C.c_int, [_P, u32p, u32p, i32p]),
+    "vrt_scene_set_probe_sgs": (C.c_int, [_P, C.POINTER(SGRec)]),
+    "vrt_scene_probe_sgs": (C.c_int, [_P, C.POINTER(SGRec)]),
+    "vrt_scene_probes_gather": (C.c_int, [_P, C.c_float, f32p]),
+    "vrt_probe_overlap": (C.c_int, [C.POINTER(Probe), f32p]),
+    "vrt_probe_isect": (C.c_int, [C.POINTER(Probe), C.POINTER(Ray), f32p, f32p, f32p, f32p]),
+    "vrt_probe_shade_hits": (C.c_int, [_P, _P, C.c_int64, f32p, f32p]),
+    "vrt_ray_march_batch_ex": (C.c_int, [_P, C.POINTER(Ray), C.c_int64, C.c_int, C.POINTER(Hit)]),
+    "vrt_ray_march_batch_ex_device": (C.c_int, [_P, _P, C.c_int64, C.c_int, _P, _P]),
     "vrt_device_selftest": (C.c_int, [C.c_int, f64p, f64p, f32p, i32p, C.c_int64]),
     "vrt_write_hdr": (C.c_int, [C.c_char_p, C.c_int, C.c_int, C.c_int, f32p]),
     "stbi_write_hdr": (C.c_int, [C.c_char_p, C.c_int, C.c_int, C.c_int, f32p]),

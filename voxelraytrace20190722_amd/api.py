@@ -285,13 +285,22 @@ class VoxelOctree:
     """The octree built by gi::ray_march_init and resident on one device
     (device < 0: host-only, for inspecting the build)."""
 
-    def __init__(self, scene, max_depth, device=0, build_on_device=False):
+    def __init__(self, scene, max_depth, device=0, build_on_device=False, probes=None):
+        """probes: (n, 4) light probes {o, r} (or LightProbe objects) pushed
+        into the voxel list behind the triangles, as VRT/main.cc:56-64 does:
+        voxel ntri + k is probe k (vrt_scene_create_probes)."""
         self.scene = scene  # keeps the arrays alive for the descriptor
         h = C.c_void_p()
         d = scene.desc()
         flags = _ffi.VRT_BUILD_DEVICE if build_on_device else 0
-        check(lib().vrt_scene_create_ex(C.byref(d), int(max_depth), int(device), flags, C.byref(h)),
-              "vrt_scene_create")
+        self.probes = _probes_arg(probes)
+        if self.probes is None:
+            check(lib().vrt_scene_create_ex(C.byref(d), int(max_depth), int(device), flags, C.byref(h)),
+                  "vrt_scene_create")
+        else:
+            check(lib().vrt_scene_create_probes(C.byref(d), self.probes.ctypes.data_as(C.POINTER(_ffi.Probe)),
+                                                len(self.probes), int(max_depth), int(device), flags, C.byref(h)),
+                  "vrt_scene_create_probes")
         self.h = h
         self.max_depth = int(max_depth)
         self.info = _ffi.SceneInfo()
@@ -349,14 +358,78 @@ class VoxelOctree:
                                      ptr(tris, _ffi.i32p)), "vrt_scene_leaves")
         return vox, cnt, tris[:nr]
 
-    def ray_march(self, rays):
-        """Batched gi::ray_march over (n, 8) rays {o, d, tmin, tmax} (d normalised)."""
+    def probe_info(self):
+        """(probes, leaves holding a probe, total length of their probe lists)."""
+        n, nl, nr = C.c_int32(), C.c_int64(), C.c_int64()
+        check(lib().vrt_scene_probe_info(self.h, C.byref(n), C.byref(nl), C.byref(nr)), "vrt_scene_probe_info")
+        return n.value, nl.value, nr.value
+
+    def probe_leaves(self):
+        """(voxel ids, counts, concatenated probe lists) of the leaves that hold
+        at least one probe, as leaves() is for the triangles."""
+        _, nl, nr = self.probe_info()
+        vox = np.zeros(max(nl, 1), np.uint32)
+        cnt = np.zeros(max(nl, 1), np.uint32)
+        pr = np.zeros(max(nr, 1), np.int32)
+        check(lib().vrt_scene_probe_leaves(self.h, ptr(vox, _ffi.u32p), ptr(cnt, _ffi.u32p), ptr(pr, _ffi.i32p)),
+              "vrt_scene_probe_leaves")
+        return vox[:nl], cnt[:nl], pr[:nr]
+
+    @property
+    def probe_sgs(self):
+        """The scene's stored SGs (zero at creation) as probe_gather's dict:
+        a, d (n, 14, 3) and s (n, 14); a probe hit's get_albedo reads them."""
+        n = self.probe_info()[0]
+        sgs = np.zeros((max(n, 1), PROBE_SGS, 7), np.float32)
+        check(lib().vrt_scene_probe_sgs(self.h, sgs.ctypes.data_as(C.POINTER(_ffi.SGRec))), "vrt_scene_probe_sgs")
+        sgs = sgs[:n]
+        return {"a": sgs[:, :, 0:3].copy(), "d": sgs[:, :, 3:6].copy(), "s": sgs[:, :, 6].copy()}
+
+    @probe_sgs.setter
+    def probe_sgs(self, sgs):
+        n = self.probe_info()[0]
+        a, d, s = (np.asarray(sgs[k], np.float32) for k in ("a", "d", "s"))
+        if a.shape != (n, PROBE_SGS, 3) or d.shape != a.shape or s.shape != (n, PROBE_SGS):
+            raise ValueError(f"sgs must hold a, d ({n}, 14, 3) and s ({n}, 14), got {a.shape}, {d.shape}, {s.shape}")
+        rec = np.ascontiguousarray(np.concatenate([a, d, s[:, :, None]], axis=2))
+        check(lib().vrt_scene_set_probe_sgs(self.h, rec.ctypes.data_as(C.POINTER(_ffi.SGRec))),
+              "vrt_scene_set_probe_sgs")
+
+    def gather_probes(self, res=0.0, light_color=(1.0, 1.0, 1.0)):
+        """VRT/main.cc:104-105: gather_light for every probe of the scene (the
+        reference's 100 points) into the stored SGs; returns them."""
+        lc = _f3(light_color)
+        check(lib().vrt_scene_probes_gather(self.h, float(res), ptr(lc, _ffi.f32p)), "vrt_scene_probes_gather")
+        return self.probe_sgs
+
+    def probe_shade_hits(self, hits, rgb, albedo=None):
+        """vrt_probe_shade_hits: finish a trace_device batch on the host.  hits:
+        the (n, 9) uint32 vrt_hit records copied back; rgb / albedo (n, 3)
+        float32 arrays updated in place where a ray ended on a probe."""
+        hits = np.ascontiguousarray(hits, np.uint32)
+        for a in (rgb, albedo):
+            if a is not None and not (a.dtype == np.float32 and a.flags.c_contiguous and a.shape == (len(hits), 3)):
+                raise ValueError("rgb / albedo must be C-contiguous float32 (n, 3)")
+        check(lib().vrt_probe_shade_hits(self.h, C.c_void_p(hits.ctypes.data), len(hits), ptr(rgb, _ffi.f32p),
+                                         ptr(albedo, _ffi.f32p)), "vrt_probe_shade_hits")
+
+    def ray_march(self, rays, even_invisible=False):
+        """Batched gi::ray_march over (n, 8) rays {o, d, tmin, tmax} (d
+        normalised).  even_invisible: the reference's last parameter -- on a
+        scene with probes they are tested too, and a probe hit has tri = ntri +
+        k (vrt_ray_march_batch_ex)."""
         rays = np.ascontiguousarray(np.asarray(rays, np.float32).reshape(-1, 8))
         n = rays.shape[0]
         out = np.zeros((max(n, 1), 9), np.uint32)
-        check(lib().vrt_ray_march_batch(self.h, rays.ctypes.data_as(C.POINTER(_ffi.Ray)), n,
-                                        out.ctypes.data_as(C.POINTER(_ffi.Hit))),
-              "vrt_ray_march_batch")
+        if even_invisible:
+            check(lib().vrt_ray_march_batch_ex(self.h, rays.ctypes.data_as(C.POINTER(_ffi.Ray)), n,
+                                               _ffi.VRT_MARCH_EVEN_INVISIBLE,
+                                               out.ctypes.data_as(C.POINTER(_ffi.Hit))),
+                  "vrt_ray_march_batch_ex")
+        else:
+            check(lib().vrt_ray_march_batch(self.h, rays.ctypes.data_as(C.POINTER(_ffi.Ray)), n,
+                                            out.ctypes.data_as(C.POINTER(_ffi.Hit))),
+                  "vrt_ray_march_batch")
         out = out[:n]
         return {"hit": out[:, 0].astype(np.int32), "tri": out[:, 1].view(np.int32).copy(),
                 "voxel": out[:, 2].copy(), "hit_p": out[:, 3:6].view(np.float32).copy(),
@@ -695,14 +768,29 @@ def multi_tile_map(film, device_mask):
     return dv, sl
 
 
-def ray_march_init(scene, max_depth, device=0):
-    """gi::ray_march_init(root, voxels, max_depth) (VRT/voxel_octree.cc:67-75)."""
-    return VoxelOctree(scene, max_depth, device)
+def ray_march_init(scene, max_depth, device=0, probes=None):
+    """gi::ray_march_init(root, voxels, max_depth) (VRT/voxel_octree.cc:67-75);
+    voxels = the scene's triangles, then `probes` (VRT/main.cc:56-64)."""
+    return VoxelOctree(scene, max_depth, device, probes=probes)
 
 
-def ray_march(tree, rays):
+def ray_march(tree, rays, even_invisible=False):
     """gi::ray_march over a batch of rays (VRT/voxel_octree.cc:131-188)."""
-    return tree.ray_march(rays)
+    return tree.ray_march(rays, even_invisible)
+
+
+def _probes_arg(probes):
+    """None, an (n, 4) array {o, r} or a sequence of LightProbe -> (n, 4) or None."""
+    if probes is None:
+        return None
+    if len(probes) and isinstance(probes[0], LightProbe):
+        probes = [np.concatenate([p.o, [p.r]]) for p in probes]
+    probes = np.asarray(probes, np.float32)
+    if probes.size == 0:
+        return None
+    if probes.ndim != 2 or probes.shape[1] != 4:
+        raise ValueError(f"probes must be (n, 4) {{o, r}}, got {probes.shape}")
+    return np.ascontiguousarray(probes)
 
 
 def trace(tree, rays, min_voxel=0.0, parts=False):
@@ -783,6 +871,39 @@ class LightProbe:
     def __init__(self, o, r):
         self.o, self.r = _f3(o), np.float32(r)
         self.sgs = None
+
+    def _rec4(self):
+        return np.ascontiguousarray(np.concatenate([self.o, [self.r]]).astype(np.float32))
+
+    def get_aabb(self):
+        """AABB3D{o_ - r_, o_ + r_} (VRT/voxel_octree.cc:541-544) -> (min, max)."""
+        return (self.o - self.r).astype(np.float32), (self.o + self.r).astype(np.float32)
+
+    def is_visible(self):
+        """VRT/voxel_octree.cc:588-591."""
+        return False
+
+    def is_overlap(self, box_min, box_max):
+        """LightProbe::is_overlap (VRT/voxel_octree.cc:567-586), vrt_probe_overlap."""
+        box = np.ascontiguousarray(np.concatenate([_f3(box_min), _f3(box_max)]))
+        p = self._rec4()
+        rc = lib().vrt_probe_overlap(p.ctypes.data_as(C.POINTER(_ffi.Probe)), ptr(box, _ffi.f32p))
+        if rc < 0:
+            check(rc, "vrt_probe_overlap")
+        return rc == 1
+
+    def isect(self, ray, prev_hit=(0.0, 0.0, 0.0)):
+        """LightProbe::isect (VRT/voxel_octree.cc:546-554), vrt_probe_isect: ray
+        = 8 floats {o, d, tmin, tmax}; prev_hit = the hit point the caller's
+        ISect held.  None on a miss, else (t, hit_p, normal)."""
+        ray = np.ascontiguousarray(np.asarray(ray, np.float32).reshape(8))
+        p, ph = self._rec4(), _f3(prev_hit)
+        t, hp, nr = C.c_float(), np.zeros(3, np.float32), np.zeros(3, np.float32)
+        rc = lib().vrt_probe_isect(p.ctypes.data_as(C.POINTER(_ffi.Probe)), ray.ctypes.data_as(C.POINTER(_ffi.Ray)),
+                                   ptr(ph, _ffi.f32p), C.byref(t), ptr(hp, _ffi.f32p), ptr(nr, _ffi.f32p))
+        if rc < 0:
+            check(rc, "vrt_probe_isect")
+        return (np.float32(t.value), hp, nr) if rc == 1 else None
 
     def gather_light(self, tree, res, light_color):
         probe = np.concatenate([self.o, [self.r]]).astype(np.float32)[None, :]

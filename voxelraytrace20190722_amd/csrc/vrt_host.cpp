@@ -284,6 +284,25 @@ struct BuildOut {
 // split iff some triangle overlaps it (and all its ancestors) above
 // max_depth; a max-depth leaf lists exactly those triangles.
 void descend(const float *tri9, uint32_t tri, const Box &b, int depth,
+             int max_depth, uint32_t code, BuildOut &o);
+
+// The same for a light probe (LightProbe::is_overlap, VRT/voxel_octree.cc:
+// 567-586): insert() splits and descends for any voxel alike.
+void descend_probe(const vrt_probe &pb, uint32_t k, const Box &b, int depth, int max_depth, uint32_t code,
+                   BuildOut &o)
+{
+        if (!probe_overlap(mk3(pb.o[0], pb.o[1], pb.o[2]), pb.r, b.mn, b.mx))
+                return;
+        if (depth == max_depth) {
+                o.refs.push_back(((uint64_t)code << 32) | k);
+                return;
+        }
+        o.internal[depth].push_back(code);
+        for (int i = 0; i < 8; ++i)
+                descend_probe(pb, k, child_box(b, i), depth + 1, max_depth, (code << 3) | (uint32_t)i, o);
+}
+
+void descend(const float *tri9, uint32_t tri, const Box &b, int depth,
              int max_depth, uint32_t code, BuildOut &o)
 {
         if (!overlaps(tri9, b))
@@ -354,6 +373,17 @@ struct vrt_scene {
         int64_t tex_bytes = 0;
         vrt_scene_info_t info{};
         std::vector<int64_t> level_begin;  // BFS level l (1-based) = [lb[l-1], lb[l])
+        // light probes as voxels (vrt_scene_create_probes; empty otherwise):
+        // the probes, per node its probe list or child mask (ProbeDev::pnode),
+        // the concatenated leaf lists, the stored SGs (14 per probe), and the
+        // device copy of the first three (one allocation, d_probe)
+        std::vector<vrt_probe> probes;
+        std::vector<uint2> pnode;
+        std::vector<uint32_t> pref;
+        std::vector<vrt_sg> probe_sgs;
+        int64_t probe_leaves = 0;
+        void *d_probe = nullptr;
+        ProbeDev pdev{};
         // full trace: two sets of {light-map block (LMRec + cone-descent
         // records + finiteness flag), split-trace records}, taken by
         // alternate light-map builds so that one frame's cone-traced shading
@@ -457,6 +487,14 @@ static int build_tree(vrt_scene *s, const vrt_scene_desc *d, bool on_device)
                         root.mx[k] = std_max(root.mx[k], tmx[k]);
                 }
         }
+        // then every probe's get_aabb() = AABB3D{o_ - r_, o_ + r_}, in probe
+        // order (VRT/voxel_octree.cc:541-544; main.cc pushes the probes
+        // behind the triangles)
+        for (const vrt_probe &pb : s->probes)
+                for (int k = 0; k < 3; ++k) {
+                        root.mn[k] = std_min(root.mn[k], pb.o[k] - pb.r);
+                        root.mx[k] = std_max(root.mx[k], pb.o[k] + pb.r);
+                }
 
         if (on_device) {
                 // level-synchronous descent, sorts, flatten and masks on the GPU
@@ -500,13 +538,25 @@ static int build_tree(vrt_scene *s, const vrt_scene_desc *d, bool on_device)
                 for (auto &x : th)
                         x.join();
         }
+        // the probes, after all triangles and in probe order: they split
+        // the nodes they overlap like any voxel; their leaf entries stay apart
+        // from the triangles' (prefs), so that a leaf's a / b words and the
+        // content masks keep counting triangles only
+        BuildOut pout;
+        pout.internal.resize(D + 1);
+        for (size_t k = 0; k < s->probes.size(); ++k)
+                descend_probe(s->probes[k], (uint32_t)k, root, 1, D, 0u, pout);
+        std::vector<uint64_t> prefs;
+        prefs.swap(pout.refs);
+        std::sort(prefs.begin(), prefs.end());  // (leaf code, probe index)
         // merge
         std::vector<std::vector<uint32_t>> internal(D + 1);
         for (int l = 1; l < D; ++l) {
-                size_t tot = 0;
+                size_t tot = pout.internal[l].size();
                 for (auto &o : outs)
                         tot += o.internal[l].size();
                 internal[l].reserve(tot);
+                internal[l].insert(internal[l].end(), pout.internal[l].begin(), pout.internal[l].end());
                 for (auto &o : outs) {
                         internal[l].insert(internal[l].end(), o.internal[l].begin(), o.internal[l].end());
                         std::vector<uint32_t>().swap(o.internal[l]);
@@ -549,7 +599,15 @@ static int build_tree(vrt_scene *s, const vrt_scene_desc *d, bool on_device)
         int64_t j_base = 0;  // global index of first internal node at level l
         // level l's nodes occupy a contiguous index range [lv_begin, lv_end)
         int64_t lv_begin = 0, lv_end = 1;
-        size_t ref_pos = 0;
+        size_t ref_pos = 0, pref_pos = 0;
+        const bool with_probes = !s->probes.empty();
+        if (with_probes) {
+                s->pnode.assign((size_t)nnodes, make_uint2(0u, 0u));
+                s->pref.resize(prefs.size());
+                for (size_t i = 0; i < prefs.size(); ++i)
+                        s->pref[i] = (uint32_t)(prefs[i] & 0xFFFFFFFFu);
+                s->probe_leaves = 0;
+        }
         s->level_begin.clear();
         for (int l = 1; l <= D; ++l) {
                 s->level_begin.push_back(lv_begin);
@@ -587,6 +645,16 @@ static int build_tree(vrt_scene *s, const vrt_scene_desc *d, bool on_device)
                                         ++ref_pos;
                                 nr.a = kLeafBit | (uint32_t)(ref_pos - r0);
                                 nr.b = (uint32_t)r0;
+                                if (with_probes) {
+                                        while (pref_pos < prefs.size() && prefs[pref_pos] < key)
+                                                ++pref_pos;
+                                        const size_t p0 = pref_pos;
+                                        while (pref_pos < prefs.size() && (prefs[pref_pos] >> 32) == code)
+                                                ++pref_pos;
+                                        s->pnode[ni] = make_uint2((uint32_t)p0, (uint32_t)(pref_pos - p0));
+                                        if (pref_pos > p0)
+                                                ++s->probe_leaves;
+                                }
                         } else {
                                 nr.a = kLeafBit;  // empty leaf above max depth
                                 nr.b = 0;
@@ -620,6 +688,23 @@ static int build_tree(vrt_scene *s, const vrt_scene_desc *d, bool on_device)
                                 for (int c = 0; c < 8; ++c)
                                         m |= (uint32_t)has[nr.a + c] << c;
                                 nr.b = m;
+                                has[ni] = m ? 1 : 0;
+                        }
+                }
+        }
+        // the same for the probes, in the side array: an internal node's
+        // pnode.x = the children with a probe somewhere below
+        if (with_probes) {
+                std::vector<uint8_t> has((size_t)nnodes, 0);
+                for (int64_t ni = nnodes - 1; ni >= 0; --ni) {
+                        const NodeRec &nr = s->nodes[ni];
+                        if (nr.a & kLeafBit) {
+                                has[ni] = s->pnode[ni].y ? 1 : 0;
+                        } else {
+                                uint32_t m = 0;
+                                for (int c = 0; c < 8; ++c)
+                                        m |= (uint32_t)has[nr.a + c] << c;
+                                s->pnode[ni] = make_uint2(m, 0u);
                                 has[ni] = m ? 1 : 0;
                         }
                 }
@@ -969,6 +1054,27 @@ static int upload(vrt_scene *s, const vrt_scene_desc *d)
                 s->dev.wide_leaves = s->wide_leaves ? 1 : 0;
         }
         chain_spacing(s);
+        if (!s->probes.empty()) {
+                // probe membership beside the octree (ProbeDev): DevScene's
+                // layout is untouched
+                static_assert(sizeof(vrt_probe) == sizeof(float4), "vrt_probe layout");
+                const size_t sz_pn = align_up(s->pnode.size() * sizeof(uint2));
+                const size_t sz_pr = align_up(std::max<size_t>(1, s->pref.size()) * sizeof(uint32_t));
+                const size_t sz_pb = align_up(s->probes.size() * sizeof(vrt_probe));
+                HIPCHK(hipMalloc(&s->d_probe, sz_pn + sz_pr + sz_pb));
+                char *pb = static_cast<char *>(s->d_probe);
+                HIPCHK(hipMemcpy(pb, s->pnode.data(), s->pnode.size() * sizeof(uint2), hipMemcpyHostToDevice));
+                if (!s->pref.empty())
+                        HIPCHK(hipMemcpy(pb + sz_pn, s->pref.data(), s->pref.size() * sizeof(uint32_t),
+                                         hipMemcpyHostToDevice));
+                HIPCHK(hipMemcpy(pb + sz_pn + sz_pr, s->probes.data(), s->probes.size() * sizeof(vrt_probe),
+                                 hipMemcpyHostToDevice));
+                s->pdev.pnode = reinterpret_cast<const uint2 *>(pb);
+                s->pdev.pref = reinterpret_cast<const uint32_t *>(pb + sz_pn);
+                s->pdev.probes = reinterpret_cast<const float4 *>(pb + sz_pn + sz_pr);
+                s->pdev.ntri = s->ntri;
+                tot += sz_pn + sz_pr + sz_pb;
+        }
         s->info.device_bytes = (int64_t)tot;
         HIPCHK(hipStreamCreateWithFlags(&s->stream, hipStreamNonBlocking));
         HIPCHK(hipEventCreate(&s->ev0));
@@ -1014,8 +1120,25 @@ extern "C" int vrt_scene_create(const vrt_scene_desc *d, int max_depth,
         return vrt_scene_create_ex(d, max_depth, device, 0, out);
 }
 
+static int scene_create(const vrt_scene_desc *d, const vrt_probe *probes, int32_t nprobe, int max_depth,
+                        int device, int flags, vrt_scene **out);
+
 extern "C" int vrt_scene_create_ex(const vrt_scene_desc *d, int max_depth,
                                    int device, int flags, vrt_scene **out)
+{
+        return scene_create(d, nullptr, 0, max_depth, device, flags, out);
+}
+
+extern "C" int vrt_scene_create_probes(const vrt_scene_desc *d, const vrt_probe *probes, int32_t nprobe,
+                                       int max_depth, int device, int flags, vrt_scene **out)
+{
+        if (nprobe == 0 || !probes)
+                return scene_create(d, nullptr, 0, max_depth, device, flags, out);
+        return scene_create(d, probes, nprobe, max_depth, device, flags, out);
+}
+
+static int scene_create(const vrt_scene_desc *d, const vrt_probe *probes, int32_t nprobe, int max_depth,
+                        int device, int flags, vrt_scene **out)
 {
         if (!out)
                 return fail(VRT_E_INVALID, "null out");
@@ -1027,6 +1150,18 @@ extern "C" int vrt_scene_create_ex(const vrt_scene_desc *d, int max_depth,
                 return fail(VRT_E_INVALID, "unknown flags %#x", flags);
         if ((flags & VRT_BUILD_DEVICE) && device < 0)
                 return fail(VRT_E_INVALID, "VRT_BUILD_DEVICE needs a device (device >= 0)");
+        if (probes) {
+                if (nprobe < 1 || (int64_t)d->ntri + (int64_t)nprobe > 0x7FFFFFFF)
+                        return fail(VRT_E_INVALID, "bad probe count %d (ntri + nprobe must stay below 2^31)", nprobe);
+                if (flags & VRT_BUILD_DEVICE)
+                        return fail(VRT_E_INVALID, "VRT_BUILD_DEVICE inserts triangles only: build a probe scene on the host");
+                for (int32_t k = 0; k < nprobe; ++k) {
+                        const vrt_probe &pb = probes[k];
+                        if (!std::isfinite(pb.o[0]) || !std::isfinite(pb.o[1]) || !std::isfinite(pb.o[2]) ||
+                            !std::isfinite(pb.r) || pb.r < 0.f)
+                                return fail(VRT_E_INVALID, "probe %d: centre must be finite, radius finite and >= 0", k);
+                }
+        }
         std::unique_ptr<vrt_scene> s(new (std::nothrow) vrt_scene);
         if (!s)
                 return fail(VRT_E_NOMEM, "scene alloc");
@@ -1035,6 +1170,10 @@ extern "C" int vrt_scene_create_ex(const vrt_scene_desc *d, int max_depth,
         s->ntri = d->ntri;
         const double t0 = now_ms();
         try {
+                if (probes) {
+                        s->probes.assign(probes, probes + nprobe);
+                        s->probe_sgs.assign((size_t)kProbeSGs * (size_t)nprobe, vrt_sg{});
+                }
                 rc = build_tree(s.get(), d, (flags & VRT_BUILD_DEVICE) != 0);
                 if (rc)
                         return rc;
@@ -1158,6 +1297,8 @@ extern "C" void vrt_scene_destroy(vrt_scene *s)
                                 (void)hipEventSynchronize(s->spill_ev[k]);
                 if (s->d_mem)
                         (void)hipFree(s->d_mem);
+                if (s->d_probe)
+                        (void)hipFree(s->d_probe);
                 for (TraceSet &t : s->ts) {
                         if (t.lm)
                                 (void)hipFree(t.lm);
@@ -1300,6 +1441,17 @@ static int need_device(const vrt_scene *s)
 {
         if (!s->d_mem)
                 return fail(VRT_E_NODEVICE, "scene was created host-only (device < 0)");
+        return VRT_OK;
+}
+
+// The film kernels of trace() and the instrumented render count or march
+// as the reference does with every voxel in the tree; they do not know probe
+// voxels yet (a follow-up).
+static int no_probe_scene(const vrt_scene *s, const char *what)
+{
+        if (!s->probes.empty())
+                return fail(VRT_E_INVALID,
+                            "%s is not available on a scene with light probes; use vrt_trace_batch for its rays", what);
         return VRT_OK;
 }
 
@@ -2015,6 +2167,9 @@ extern "C" int vrt_render(vrt_scene *s, const vrt_camera *cam,
         const size_t npix = (size_t)film->nx * film->ny;
         const size_t ns = npix * 4;
         const bool want_cnt = (samples && samples->counters) || stats;
+        if (want_cnt)
+                if (int rc = no_probe_scene(s, "vrt_render with instrumented counters"))
+                        return rc;
         DevBuf img, shit, stri, svox, srgb, scnt;
         HIPCHK(hipMalloc(&img.p, npix * 3 * sizeof(float)));
         HIPCHK(hipMemsetAsync(img.p, 0, npix * 3 * sizeof(float), s->stream));
@@ -2385,6 +2540,9 @@ static int lightmap_enqueue(vrt_scene *s, int set, const vrt_camera *light_cam, 
         // cone_trace_init_filter's leaf case first: it also zeroes the
         // counters the passes below add to (no memsets)
         HIPCHK(launch_lm_leaves(s->dev.nodes, nnodes, d_lm, d_bad, d_count, d_tail_n, d_nseg, s->stream));
+        // a leaf whose list holds probes only is non-empty too: coverage 1
+        if (!s->probes.empty())
+                HIPCHK(launch_lm_probe_leaves(s->dev.nodes, s->pdev.pnode, nnodes, d_lm, s->stream));
         HIPCHK(launch_light(lp, s->stream));
         if (overlap)
                 if (int rc = overlap())
@@ -2641,6 +2799,8 @@ extern "C" int vrt_render_trace_device(vrt_scene *s, const vrt_camera *cam, cons
                 return VRT_E_NODEVICE;
         if (!s || !cam || !d_out)
                 return fail(VRT_E_INVALID, "null argument");
+        if (int rc = no_probe_scene(s, "vrt_render_trace_device"))
+                return rc;
         if (int rc = film_ok(film))
                 return rc;
         if (nranks < 1 || rank < 0 || rank >= nranks)
@@ -2687,6 +2847,8 @@ extern "C" int vrt_trace_frame_device(vrt_scene *s, const vrt_camera *light_cam,
                 return VRT_E_NODEVICE;
         if (!s || !light_cam || !cam || !d_out)
                 return fail(VRT_E_INVALID, "null argument");
+        if (int rc = no_probe_scene(s, "vrt_trace_frame_device"))
+                return rc;
         if (int rc = film_ok(light_film))
                 return rc;
         if (int rc = film_ok(film))
@@ -2753,6 +2915,8 @@ extern "C" int vrt_render_trace(vrt_scene *s, const vrt_camera *cam, const vrt_f
                 return VRT_E_NODEVICE;
         if (!s || !cam || !rgb)
                 return fail(VRT_E_INVALID, "null argument");
+        if (int rc = no_probe_scene(s, "vrt_render_trace"))
+                return rc;
         if (int rc = film_ok(film))
                 return rc;
         if (int rc = trace_ok(s, min_voxel))
@@ -2813,8 +2977,17 @@ extern "C" int vrt_ray_march_batch_device(vrt_scene *s, const vrt_ray *d_rays,
         return VRT_OK;
 }
 
+// even_invisible: gi::ray_march's last parameter; it changes the march only
+// on a probe scene (vrt_ray_march_batch_ex)
+static int ray_march_host(vrt_scene *s, const vrt_ray *rays, int64_t n, vrt_hit *hits, bool even_invisible);
+
 extern "C" int vrt_ray_march_batch(vrt_scene *s, const vrt_ray *rays,
                                    int64_t n, vrt_hit *hits)
+{
+        return ray_march_host(s, rays, n, hits, false);
+}
+
+static int ray_march_host(vrt_scene *s, const vrt_ray *rays, int64_t n, vrt_hit *hits, bool even_invisible)
 {
         if (s && need_device(s))
                 return VRT_E_NODEVICE;
@@ -2848,7 +3021,10 @@ extern "C" int vrt_ray_march_batch(vrt_scene *s, const vrt_ray *rays,
         }
         par_memcpy(s->h_rays, rays, (size_t)n * sizeof(vrt_ray));
         HIPCHK(hipMemcpyAsync(s->d_rays, s->h_rays, (size_t)n * sizeof(vrt_ray), hipMemcpyHostToDevice, s->stream));
-        HIPCHK(launch_ray_march(s->dev, s->d_rays, n, s->d_hits, s->stream, s->ord_wmin));
+        if (even_invisible && !s->probes.empty())
+                HIPCHK(launch_ray_march_mixed(s->dev, s->pdev, s->d_rays, n, s->d_hits, s->stream));
+        else
+                HIPCHK(launch_ray_march(s->dev, s->d_rays, n, s->d_hits, s->stream, s->ord_wmin));
         HIPCHK(hipMemcpyAsync(s->h_hits, s->d_hits, (size_t)n * sizeof(vrt_hit), hipMemcpyDeviceToHost, s->stream));
         HIPCHK(hipStreamSynchronize(s->stream));
         par_memcpy(hits, s->h_hits, (size_t)n * sizeof(vrt_hit));
@@ -2884,7 +3060,9 @@ static int batch_enqueue(vrt_scene *s, const BatchIO &io, float min_voxel, hipSt
         if (int rc = ts_acquire(s, set, st))
                 return rc;
         (void)hipGetLastError();  // a leftover error of an earlier call is not this launch's
-        const hipError_t e = io.rays ? launch_trace_batch(tp, io, chunk, st) : launch_cones_batch(tp, io, st);
+        // trace() marches with even_invisible = true: the mixed march on a probe scene
+        const ProbeDev *pd = s->probes.empty() ? nullptr : &s->pdev;
+        const hipError_t e = io.rays ? launch_trace_batch(tp, io, chunk, st, pd) : launch_cones_batch(tp, io, st);
         if (e != hipSuccess) {
                 (void)ts_release(s, set, st);
                 return fail(VRT_E_DEVICE, "batched trace launch failed: %s", hipGetErrorString(e));
@@ -2984,13 +3162,23 @@ static int batch_staging(vrt_scene *s, size_t bytes)
 // Host arrays: chunk by chunk through the staging (in: `in_sz` bytes per
 // element at offset 0; out: the requested arrays behind it, out_sz[k] bytes
 // per element each), one host sync per chunk.
+static void probe_shade(const vrt_scene *s, const vrt_hit *hits, int64_t n, float *rgb, float *albedo);
+
 static int batch_host(vrt_scene *s, const void *in, size_t in_sz, bool rays, int64_t n, float min_voxel,
                       void *const out[5], const size_t out_sz[5])
 {
         const int64_t m = std::min(n, batch_chunk());
+        // trace() on a probe scene: the chunk's hit records come back
+        // whether or not the caller asked for them, and the rays that ended
+        // on a probe get their colour here (LightProbe::eval, the C
+        // library's expf) before the chunk is handed out
+        const bool shade = rays && !s->probes.empty();
+        bool want[5];
+        for (int k = 0; k < 5; ++k)
+                want[k] = out[k] != nullptr || (k == 1 && shade);
         size_t per = in_sz;
         for (int k = 0; k < 5; ++k)
-                per += out[k] ? out_sz[k] : 0;
+                per += want[k] ? out_sz[k] : 0;
         if (int rc = batch_staging(s, (size_t)m * per))
                 return rc;
         char *d = static_cast<char *>(s->d_tb), *h = static_cast<char *>(s->h_tb);
@@ -3004,10 +3192,10 @@ static int batch_host(vrt_scene *s, const void *in, size_t in_sz, bool rays, int
                 size_t off = (size_t)m * in_sz, o5[5] = {};
                 for (int k = 0; k < 5; ++k) {
                         o5[k] = off;
-                        off += out[k] ? (size_t)m * out_sz[k] : 0;
+                        off += want[k] ? (size_t)m * out_sz[k] : 0;
                 }
                 io.rgb = reinterpret_cast<float *>(d + o5[0]);
-                io.hits = out[1] ? reinterpret_cast<uint32_t *>(d + o5[1]) : nullptr;
+                io.hits = want[1] ? reinterpret_cast<uint32_t *>(d + o5[1]) : nullptr;
                 io.indirect = out[2] ? reinterpret_cast<float *>(d + o5[2]) : nullptr;
                 io.direct = out[3] ? reinterpret_cast<float *>(d + o5[3]) : nullptr;
                 io.albedo = out[4] ? reinterpret_cast<float *>(d + o5[4]) : nullptr;
@@ -3016,6 +3204,10 @@ static int batch_host(vrt_scene *s, const void *in, size_t in_sz, bool rays, int
                 HIPCHK(hipMemcpyAsync(h + (size_t)m * in_sz, d + (size_t)m * in_sz, off - (size_t)m * in_sz,
                                       hipMemcpyDeviceToHost, s->stream));
                 HIPCHK(hipStreamSynchronize(s->stream));
+                if (shade)
+                        probe_shade(s, reinterpret_cast<const vrt_hit *>(h + o5[1]), c,
+                                    reinterpret_cast<float *>(h + o5[0]),
+                                    out[4] ? reinterpret_cast<float *>(h + o5[4]) : nullptr);
                 for (int k = 0; k < 5; ++k)
                         if (out[k])
                                 par_memcpy(static_cast<char *>(out[k]) + (size_t)b * out_sz[k], h + o5[k],
@@ -3292,6 +3484,158 @@ extern "C" int vrt_probe_gather(vrt_scene *s, const vrt_probe *probes, int64_t n
                         par_memcpy(reinterpret_cast<char *>(terms) + (size_t)b * tm_sz, h + o_tm, (size_t)c * tm_sz);
         }
         return VRT_OK;
+}
+
+// ---- light probes as scene voxels (vrt_scene_create_probes) ----------------
+extern "C" int vrt_probe_overlap(const vrt_probe *p, const float box[6])
+{
+        if (!p || !box)
+                return fail(VRT_E_INVALID, "null argument");
+        return probe_overlap(mk3(p->o[0], p->o[1], p->o[2]), p->r, box, box + 3) ? 1 : 0;
+}
+
+extern "C" int vrt_probe_isect(const vrt_probe *p, const vrt_ray *ray, const float prev_hit[3], float *t,
+                               float hit_p[3], float normal[3])
+{
+        if (!p || !ray || !prev_hit || !t || !hit_p || !normal)
+                return fail(VRT_E_INVALID, "null argument");
+        float tt;
+        f3 hp, nrm;
+        if (!probe_isect(mk3(p->o[0], p->o[1], p->o[2]), p->r, mk3(ray->o[0], ray->o[1], ray->o[2]),
+                         mk3(ray->d[0], ray->d[1], ray->d[2]), mk3(prev_hit[0], prev_hit[1], prev_hit[2]), &tt, &hp,
+                         &nrm))
+                return 0;
+        *t = tt;
+        hit_p[0] = hp.x, hit_p[1] = hp.y, hit_p[2] = hp.z;
+        normal[0] = nrm.x, normal[1] = nrm.y, normal[2] = nrm.z;
+        return 1;
+}
+
+extern "C" int vrt_scene_probe_info(const vrt_scene *s, int32_t *nprobe, int64_t *probe_leaves, int64_t *probe_refs)
+{
+        if (!s)
+                return fail(VRT_E_INVALID, "null argument");
+        if (nprobe)
+                *nprobe = (int32_t)s->probes.size();
+        if (probe_leaves)
+                *probe_leaves = s->probe_leaves;
+        if (probe_refs)
+                *probe_refs = (int64_t)s->pref.size();
+        return VRT_OK;
+}
+
+extern "C" int vrt_scene_probe_leaves(const vrt_scene *s, uint32_t *voxel, uint32_t *count, int32_t *probes)
+{
+        if (!s || !voxel || !count || !probes)
+                return fail(VRT_E_INVALID, "null argument");
+        std::vector<std::pair<uint32_t, size_t>> lv;
+        for (size_t i = 0; i < s->pnode.size(); ++i)
+                if ((s->nodes[i].a & kLeafBit) && s->pnode[i].y)
+                        lv.emplace_back(s->node_vox[i], i);
+        std::sort(lv.begin(), lv.end());
+        size_t o = 0;
+        for (size_t j = 0; j < lv.size(); ++j) {
+                const uint2 pn = s->pnode[lv[j].second];
+                voxel[j] = lv[j].first;
+                count[j] = pn.y;
+                for (uint32_t k = 0; k < pn.y; ++k)
+                        probes[o++] = (int32_t)s->pref[pn.x + k];
+        }
+        return VRT_OK;
+}
+
+extern "C" int vrt_scene_set_probe_sgs(vrt_scene *s, const vrt_sg *sgs)
+{
+        if (!s || !sgs)
+                return fail(VRT_E_INVALID, "null argument");
+        if (s->probes.empty())
+                return fail(VRT_E_INVALID, "the scene has no probes (vrt_scene_create_probes)");
+        std::lock_guard<std::mutex> lk(s->mu);
+        std::copy(sgs, sgs + s->probe_sgs.size(), s->probe_sgs.begin());
+        return VRT_OK;
+}
+
+extern "C" int vrt_scene_probe_sgs(const vrt_scene *s, vrt_sg *sgs)
+{
+        if (!s || !sgs)
+                return fail(VRT_E_INVALID, "null argument");
+        if (s->probes.empty())
+                return fail(VRT_E_INVALID, "the scene has no probes (vrt_scene_create_probes)");
+        std::copy(s->probe_sgs.begin(), s->probe_sgs.end(), sgs);
+        return VRT_OK;
+}
+
+extern "C" int vrt_scene_probes_gather(vrt_scene *s, float min_voxel, const float light_color[3])
+{
+        if (!s || !light_color)
+                return fail(VRT_E_INVALID, "null argument");
+        if (s->probes.empty())
+                return fail(VRT_E_INVALID, "the scene has no probes (vrt_scene_create_probes)");
+        // VRT/main.cc:104-105: every probe's gather_light with its own 100 points
+        std::vector<vrt_sg> sgs(s->probe_sgs.size());
+        if (int rc = vrt_probe_gather(s, s->probes.data(), (int64_t)s->probes.size(), min_voxel, light_color, nullptr,
+                                      100, sgs.data(), nullptr))
+                return rc;
+        std::lock_guard<std::mutex> lk(s->mu);
+        s->probe_sgs.swap(sgs);
+        return VRT_OK;
+}
+
+// LightProbe::get_albedo (VRT/voxel_octree.cc:562-566) for the elements of a
+// batch that ended on a probe: eval(normalize(hit - o_)) over the stored SGs,
+// vrt_probe_eval's code; albedo = rgb (trace() returns get_albedo itself)
+static void probe_shade(const vrt_scene *s, const vrt_hit *hits, int64_t n, float *rgb, float *albedo)
+{
+        const int64_t np = (int64_t)s->probes.size();
+        for (int64_t i = 0; i < n; ++i) {
+                const vrt_hit &h = hits[i];
+                const int64_t k = (int64_t)h.tri - s->ntri;
+                if (h.hit != 1 || k < 0 || k >= np)
+                        continue;
+                const vrt_probe &pb = s->probes[(size_t)k];
+                const f3 dir = normalize(mk3(h.hit_p[0], h.hit_p[1], h.hit_p[2]) - mk3(pb.o[0], pb.o[1], pb.o[2]));
+                const float dv[3] = { dir.x, dir.y, dir.z };
+                float c[3];
+                vrt_probe_eval(&s->probe_sgs[(size_t)k * kProbeSGs], 1, dv, 1, c);
+                for (int q = 0; q < 3; ++q) {
+                        if (rgb)
+                                rgb[3 * i + q] = c[q];
+                        if (albedo)
+                                albedo[3 * i + q] = c[q];
+                }
+        }
+}
+
+extern "C" int vrt_probe_shade_hits(vrt_scene *s, const vrt_hit *hits, int64_t n, float *rgb, float *albedo)
+{
+        if (!s || n < 0 || (n > 0 && !hits))
+                return fail(VRT_E_INVALID, "bad argument");
+        std::lock_guard<std::mutex> lk(s->mu);
+        probe_shade(s, hits, n, rgb, albedo);
+        return VRT_OK;
+}
+
+extern "C" int vrt_ray_march_batch_ex_device(vrt_scene *s, const vrt_ray *d_rays, int64_t n, int flags,
+                                             vrt_hit *d_hits, void *stream)
+{
+        if (flags & ~VRT_MARCH_EVEN_INVISIBLE)
+                return fail(VRT_E_INVALID, "unknown flags %#x", flags);
+        if (!s || !(flags & VRT_MARCH_EVEN_INVISIBLE) || s->probes.empty())
+                return vrt_ray_march_batch_device(s, d_rays, n, d_hits, stream);
+        if (need_device(s))
+                return VRT_E_NODEVICE;
+        if ((n > 0 && (!d_rays || !d_hits)) || n < 0)
+                return fail(VRT_E_INVALID, "bad argument");
+        HIPCHK(hipSetDevice(s->device));
+        HIPCHK(launch_ray_march_mixed(s->dev, s->pdev, d_rays, n, d_hits, static_cast<hipStream_t>(stream)));
+        return VRT_OK;
+}
+
+extern "C" int vrt_ray_march_batch_ex(vrt_scene *s, const vrt_ray *rays, int64_t n, int flags, vrt_hit *hits)
+{
+        if (flags & ~VRT_MARCH_EVEN_INVISIBLE)
+                return fail(VRT_E_INVALID, "unknown flags %#x", flags);
+        return ray_march_host(s, rays, n, hits, (flags & VRT_MARCH_EVEN_INVISIBLE) != 0);
 }
 
 extern "C" int vrt_device_selftest(int device, const double *mt_in,

@@ -551,6 +551,26 @@ struct ProbeIO {
         const float *points;  // device: npoints x 3 (set by the launcher)
 };
 
+// Probe membership of a scene built with light probes as voxels
+// (vrt_scene_create_probes): side arrays beside the octree, so DevScene and
+// every triangle-only kernel stay as they are (a leaf's a / b words and the
+// content masks count triangles only).  pnode[i]: leaf -> {first entry of its
+// probe list in pref, length}; internal node -> {8-bit mask of the children
+// with a probe somewhere below, 0}.
+struct ProbeDev {
+        const uint2 *pnode;     // one per node
+        const uint32_t *pref;   // probe indices, leaf lists in probe order
+        const float4 *probes;   // {o xyz, r}
+        int32_t ntri;           // a probe hit's voxel index is ntri + k
+};
+hipError_t launch_ray_march_mixed(const DevScene &sc, const ProbeDev &pd, const void *d_rays, int64_t n,
+                                  void *d_hits, hipStream_t st);
+// light map of a probe scene: leaves that hold probes but no triangle get
+// coverage 1 (cone_trace_init_filter, VRT/voxel_octree.cc:192-199); after
+// launch_lm_leaves, before the level filter
+hipError_t launch_lm_probe_leaves(const NodeRec *nodes, const uint2 *pnode, int64_t nnodes, LMRec *lm,
+                                  hipStream_t st);
+
 // GPU octree build (vrt_build.hip): the host build's
 // arrays, produced on `device` and copied back.
 struct DeviceBuild {
@@ -645,7 +665,11 @@ hipError_t launch_trace_prim(const TraceParams &p, hipStream_t st);
 hipError_t launch_cones(const TraceParams &p, hipStream_t st);
 // the batched trace(): io.n rays in chunks of `chunk` records (p.rec), and
 // the batched cone_trace; both build the step table first when p.build_steps
-hipError_t launch_trace_batch(const TraceParams &p, const BatchIO &io, int64_t chunk, hipStream_t st);
+// pd != nullptr (a probe scene): the primary march is the mixed march; a ray
+// that ends on a probe is recorded as a zero-coloured miss (rgb and parts +0)
+// with its vrt_hit (tri >= ntri) when io.hits is set
+hipError_t launch_trace_batch(const TraceParams &p, const BatchIO &io, int64_t chunk, hipStream_t st,
+                              const ProbeDev *pd = nullptr);
 hipError_t launch_cones_batch(const TraceParams &p, const BatchIO &io, hipStream_t st);
 // the light-probe gather: io.n probes in chunks of `chunk` probes (p.rec
 // holds 14 * npoints records per probe of a chunk, p.tail the points);

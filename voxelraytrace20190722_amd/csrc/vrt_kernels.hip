@@ -2439,6 +2439,212 @@ __global__ __launch_bounds__(kBlock) void k_ray_march(DevScene sc,
 }
 
 // ---------------------------------------------------------------------------
+// gi::ray_march(root, ray, .., even_invisible = true) on a scene with light
+// probes as voxels (vrt_scene_create_probes): the exact general walk -- every
+// child's own slab test with the reference's select semantics and
+// travorder's pinned sort (expand_v1<false, false>) -- entering a child when
+// the triangle content mask or the probe mask has it.  None of the
+// triangle-only skips (xnodes union boxes, leaf-record boxes, chain order) is
+// used: their proofs say nothing about a probe below the node.
+// A leaf without probes takes the plain leaf loop (leaf_isect_v2).  A leaf
+// with probes runs ray_march_isect over the whole list, triangles then
+// probes, carrying the hit point of the last successful record: it is what
+// LightProbe::isect reads as isect->hit (VRT/voxel_octree.cc:550) -- the
+// march's ISect starts at zero (trace()'s `ISect isect{}`) and no earlier
+// leaf can have written it, since the march returns at the first leaf with a
+// success.
+// ---------------------------------------------------------------------------
+struct MixedResult {
+        bool hit;
+        bool probe;     // the winning record is a probe
+        uint32_t node;  // hit leaf
+        uint32_t vox;   // triangle id, or ntri + probe index
+        float u, v;     // triangle: clamped barycentrics
+        f3 hp;          // ISect::hit
+        f3 nrm;         // probe: ISect::normal
+};
+
+template <bool kR64>
+__device__ __forceinline__ bool leaf_isect_mixed(const DevScene &sc, const ProbeDev &pd, uint32_t first, uint32_t ntr,
+                                                 uint32_t pfirst, uint32_t npr, const RayK &r, MixedResult &m)
+{
+        bool any = false;
+        float best = 0.f;
+        f3 prev = mk3(0.f, 0.f, 0.f);  // isect->hit as the records see it
+        const double o[3] = { r.o.x, r.o.y, r.o.z }, d[3] = { r.d.x, r.d.y, r.d.z };
+#pragma unroll 1
+        for (uint32_t k = 0; k < ntr; ++k) {
+                const uint32_t tri = kR64 ? static_cast<const RefRec64 *>(sc.refs)[first + k].tri
+                                          : static_cast<const RefRec48 *>(sc.refs)[first + k].tri;
+                const TriPos *tp = sc.tri_pos + tri;
+                const double v0[3] = { tp->p[0], tp->p[1], tp->p[2] };
+                const double v1[3] = { tp->p[3], tp->p[4], tp->p[5] };
+                const double v2[3] = { tp->p[6], tp->p[7], tp->p[8] };
+                double t = 0, u = 0, v = 0;
+                if (mt_isect(o, d, v0, v1, v2, &t, &u, &v) != 1)
+                        continue;
+                // Triangle::isect (VRT/voxel_octree.cc:449-454)
+                const f3 hp = r.o + r.d * (float)t;
+                prev = hp;
+                const float depth = length(hp - r.o);
+                if (first_min_takes(any, best, depth)) {
+                        any = true;
+                        best = depth;
+                        m.probe = false;
+                        m.vox = tri;
+                        m.u = clampf((float)u, 0, 1);
+                        m.v = clampf((float)v, 0, 1);
+                        m.hp = hp;
+                }
+        }
+#pragma unroll 1
+        for (uint32_t k = 0; k < npr; ++k) {
+                const uint32_t pi = pd.pref[pfirst + k];
+                const float4 p = pd.probes[pi];
+                float t;
+                f3 hp, nrm;
+                if (!probe_isect(mk3(p.x, p.y, p.z), p.w, r.o, r.d, prev, &t, &hp, &nrm))
+                        continue;
+                prev = hp;
+                const float depth = length(hp - r.o);
+                if (first_min_takes(any, best, depth)) {
+                        any = true;
+                        best = depth;
+                        m.probe = true;
+                        m.vox = (uint32_t)pd.ntri + pi;
+                        m.hp = hp;
+                        m.nrm = nrm;
+                }
+        }
+        return any;
+}
+
+template <bool kR64>
+__device__ __forceinline__ bool leaf_mixed(const DevScene &sc, const ProbeDev &pd, uint32_t node, uint32_t a,
+                                           uint32_t b, const RayK &r, MixedResult &m)
+{
+        const uint32_t ntr = a & ~kLeafBit;
+        const uint2 pn = pd.pnode[node];
+        if (pn.y == 0) {
+                if (ntr == 0)
+                        return false;
+                MarchResult t;
+                if (!leaf_isect_v2<false, kR64>(sc.refs, b, ntr, r, t))
+                        return false;
+                m.probe = false;
+                m.vox = t.tri;
+                m.u = t.u;
+                m.v = t.v;
+                m.hp = t.hp;
+                return true;
+        }
+        return leaf_isect_mixed<kR64>(sc, pd, b, ntr, pn.x, pn.y, r, m);
+}
+
+template <bool kR64>
+__device__ __forceinline__ void ray_march_mixed(const DevScene &sc, const ProbeDev &pd, const RayK &r, uint2 *stk,
+                                                MixedResult &m)
+{
+        constexpr int kS = kBlock;
+        m.hit = false;
+        float bmin[3], bmax[3];
+        uint32_t a, b;
+        load_node(sc.nodes, 0, bmin, bmax, a, b);
+        if (!aabb_isect(bmin, bmax, r.o, r.dinv, r.tmin, r.tmax))
+                return;
+        if (a & kLeafBit) {
+                if (leaf_mixed<kR64>(sc, pd, 0, a, b, r, m)) {
+                        m.hit = true;
+                        m.node = 0;
+                }
+                return;
+        }
+        int cnt;
+        uint32_t fpos;
+        uint32_t order = expand_v1<false, false>(bmin, bmax, r, cnt, fpos, (b | pd.pnode[0].x) & 0xFFu);
+        uint32_t base = a;
+        int sp = 0;
+        for (;;) {
+                if (cnt == 0) {
+                        if (sp == 0)
+                                return;
+                        --sp;
+                        const uint2 e = stk[sp * kS];
+                        base = e.x;
+                        order = e.y & 0xFFFFFFu;
+                        cnt = (int)(e.y >> 24);
+                }
+                const uint32_t ci = order & 7u;
+                order >>= 3;
+                --cnt;
+                const uint32_t node = base + ci;
+                load_node(sc.nodes, node, bmin, bmax, a, b);
+                if (!(a & kLeafBit)) {
+                        // a pushed level always has children left; at most one
+                        // level per tree depth is pending (sp < kStack)
+                        if (cnt) {
+                                stk[sp * kS] = make_uint2(base, order | ((uint32_t)cnt << 24));
+                                ++sp;
+                        }
+                        order = expand_v1<false, false>(bmin, bmax, r, cnt, fpos, (b | pd.pnode[node].x) & 0xFFu);
+                        base = a;
+                        continue;
+                }
+                if (leaf_mixed<kR64>(sc, pd, node, a, b, r, m)) {
+                        m.hit = true;
+                        m.node = node;
+                        return;
+                }
+        }
+}
+
+// Batched ray_march(.., even_invisible = true): one ray per lane, vrt_hit
+// records as k_ray_march writes them; a probe hit has tri = ntri + k and the
+// normal LightProbe::isect left in the ISect.
+template <bool kR64>
+__global__ __launch_bounds__(kBlock) void k_ray_march_mixed(DevScene sc, ProbeDev pd,
+                                                            const float *__restrict__ rays, int64_t n,
+                                                            uint32_t *__restrict__ out)
+{
+        __shared__ uint2 stk[kStack * kBlock];
+        const int tid = threadIdx.x;
+        const int64_t i = (int64_t)blockIdx.x * kBlock + tid;
+        if (i >= n)
+                return;
+        const float *rr = rays + 8 * i;
+        const RayK r = make_rayk(mk3(rr[0], rr[1], rr[2]), mk3(rr[3], rr[4], rr[5]), rr[6], rr[7]);
+        MixedResult m;
+        ray_march_mixed<kR64>(sc, pd, r, stk + tid, m);
+        uint32_t *o = out + 9 * i;
+        if (m.hit) {
+                f3 nrm = m.nrm;
+                if (!m.probe) {
+                        const TriAttr *ta = sc.tri_attr + m.vox;
+                        const f3 n0 = mk3(ta->n[0], ta->n[1], ta->n[2]);
+                        const f3 n1 = mk3(ta->n[3], ta->n[4], ta->n[5]);
+                        const f3 n2 = mk3(ta->n[6], ta->n[7], ta->n[8]);
+                        const float w = clampf(1.0f - m.u - m.v, 0, 1);
+                        nrm = normalize((n0 * w + n1 * m.u) + n2 * m.v);
+                }
+                o[0] = 1;
+                o[1] = m.vox;
+                o[2] = sc.node_vox[m.node];
+                o[3] = __float_as_uint(m.hp.x);
+                o[4] = __float_as_uint(m.hp.y);
+                o[5] = __float_as_uint(m.hp.z);
+                o[6] = __float_as_uint(nrm.x);
+                o[7] = __float_as_uint(nrm.y);
+                o[8] = __float_as_uint(nrm.z);
+        } else {
+                o[0] = 0;
+                o[1] = 0xFFFFFFFFu;
+                o[2] = 0xFFFFFFFFu;
+                for (int q = 3; q < 9; ++q)
+                        o[q] = 0;
+        }
+}
+
+// ---------------------------------------------------------------------------
 // Config 5: one primary hit per pixel, then `spp` stochastic
 // secondary rays Ray{hit, normal + random_point_in_unit_sphere(pcg), res}.
 // ---------------------------------------------------------------------------
@@ -3901,6 +4107,43 @@ hipError_t launch_ray_march(const DevScene &sc, const void *d_rays, int64_t n,
         return hipGetLastError();
 }
 
+hipError_t launch_ray_march_mixed(const DevScene &sc, const ProbeDev &pd, const void *d_rays, int64_t n,
+                                  void *d_hits, hipStream_t st)
+{
+        if (n <= 0)
+                return hipSuccess;
+        const int64_t grid = (n + kBlock - 1) / kBlock;
+        hipLaunchKernelGGL(sc.wide_leaves ? k_ray_march_mixed<true> : k_ray_march_mixed<false>, dim3((unsigned)grid),
+                           dim3(kBlock), 0, st, sc, pd, static_cast<const float *>(d_rays), n,
+                           static_cast<uint32_t *>(d_hits));
+        return hipGetLastError();
+}
+
+// cone_trace_init_filter's leaf case for a leaf whose list holds probes only
+// (VRT/voxel_octree.cc:192-199: a non-empty list is coverage 1): k_lm_leaves
+// saw no triangle there and wrote coverage 0; illum stays zero (the light
+// pass is visible-only and never ends in such a leaf).
+__global__ __launch_bounds__(256) void k_lm_probe_leaves(const NodeRec *__restrict__ nodes,
+                                                         const uint2 *__restrict__ pnode, int64_t n,
+                                                         LMRec *__restrict__ lm)
+{
+        const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+        if (i >= n)
+                return;
+        if ((nodes[i].a & kLeafBit) && pnode[i].y != 0u)
+                lm[i].cov = 1.f;
+}
+
+hipError_t launch_lm_probe_leaves(const NodeRec *nodes, const uint2 *pnode, int64_t nnodes, LMRec *lm,
+                                  hipStream_t st)
+{
+        if (nnodes <= 0)
+                return hipSuccess;
+        const unsigned g = (unsigned)((nnodes + 255) / 256);
+        hipLaunchKernelGGL(k_lm_probe_leaves, dim3(g), dim3(256), 0, st, nodes, pnode, nnodes, lm);
+        return hipGetLastError();
+}
+
 // stbiw__linear_to_rgbe (VRT/stb_image_write.h:601-616) per pixel, the
 // per-pixel half of stbi_write_hdr (the scanline RLE stays on the host,
 // vrt_hdr.cpp).  Byte-identical to the reference's x86-64 build:
@@ -4902,6 +5145,66 @@ __global__ __launch_bounds__(kBlock) void k_trace_batch_prim(TraceParams p, Batc
         }
 }
 
+// The same on a probe scene: trace(root, ray, 5, true)'s ray_march passes
+// even_invisible = true (VRT/main.cc:13), so the mixed march runs.  A
+// triangle hit is recorded as above.  A probe hit returns get_albedo =
+// LightProbe::eval, which needs the C library's expf: its record is a miss
+// with a zero colour, so phase 2 writes +0 to rgb and to every part, and the
+// vrt_hit (tri = ntri + k) marks the element for the host's
+// vrt_probe_shade_hits.
+template <bool kR64>
+__global__ __launch_bounds__(kBlock) void k_trace_batch_prim_mixed(TraceParams p, ProbeDev pd, BatchIO io)
+{
+        __shared__ uint2 stk[kStack * kBlock];
+        const int tid = threadIdx.x;
+        const int64_t i = (int64_t)blockIdx.x * kBlock + tid;
+        if (i >= io.n)
+                return;
+        const float *rr = io.rays + 8 * i;
+        const RayK r = make_rayk(mk3(rr[0], rr[1], rr[2]), mk3(rr[3], rr[4], rr[5]), rr[6], rr[7]);
+        MixedResult x;
+        ray_march_mixed<kR64>(p.r.sc, pd, r, stk + tid, x);
+        MarchResult m;
+        m.hit = x.hit && !x.probe;
+        m.node = x.node;
+        m.tri = x.vox;
+        m.u = x.u;
+        m.v = x.v;
+        m.hp = x.hp;
+        f3 nrm = x.nrm;
+        if (x.hit && x.probe) {
+                float4 *o = p.rec + 4 * i;
+                o[0] = make_float4(0.f, 0.f, 0.f, 0.f);
+                o[2] = make_float4(0.f, 0.f, 0.f, 0.f);
+        } else {
+                trace_prim_record(p, r, m, i);
+                if (m.hit) {
+                        const float4 nr = p.rec[4 * i + 1];
+                        nrm = mk3(nr.x, nr.y, nr.z);
+                }
+        }
+        if (io.hits) {
+                uint32_t *o = io.hits + 9 * i;
+                if (x.hit) {
+                        o[0] = 1;
+                        o[1] = x.vox;
+                        o[2] = p.r.sc.node_vox[x.node];
+                        o[3] = __float_as_uint(x.hp.x);
+                        o[4] = __float_as_uint(x.hp.y);
+                        o[5] = __float_as_uint(x.hp.z);
+                        o[6] = __float_as_uint(nrm.x);
+                        o[7] = __float_as_uint(nrm.y);
+                        o[8] = __float_as_uint(nrm.z);
+                } else {
+                        o[0] = 0;
+                        o[1] = 0xFFFFFFFFu;
+                        o[2] = 0xFFFFFFFFu;
+                        for (int q = 3; q < 9; ++q)
+                                o[q] = 0;
+                }
+        }
+}
+
 // Phase 2, and all of vrt_cone_trace_batch (kIsect: the hit point and normal
 // come from the caller's vrt_isect array, every element is marched, and rgb
 // is cone_trace's sum alone).  A batch has no tile of neighbouring samples
@@ -5318,7 +5621,8 @@ hipError_t launch_cones(const TraceParams &p, hipStream_t st)
 // vrt_trace_batch: io.n rays in chunks of `chunk` (p.rec holds one chunk's
 // records; the chunks follow one another on the stream): the step table when
 // p.build_steps, then per chunk the primary march and the cones.
-hipError_t launch_trace_batch(const TraceParams &p, const BatchIO &io, int64_t chunk, hipStream_t st)
+hipError_t launch_trace_batch(const TraceParams &p, const BatchIO &io, int64_t chunk, hipStream_t st,
+                              const ProbeDev *pd)
 {
         if (io.n <= 0)
                 return hipSuccess;
@@ -5333,8 +5637,13 @@ hipError_t launch_trace_batch(const TraceParams &p, const BatchIO &io, int64_t c
                 c.indirect = io.indirect ? io.indirect + 3 * b : nullptr;
                 c.direct = io.direct ? io.direct + 3 * b : nullptr;
                 c.albedo = io.albedo ? io.albedo + 3 * b : nullptr;
-                hipLaunchKernelGGL(p.r.sc.wide_leaves ? k_trace_batch_prim<true> : k_trace_batch_prim<false>,
-                                   dim3((unsigned)((c.n + kBlock - 1) / kBlock)), dim3(kBlock), 0, st, p, c);
+                if (pd)
+                        hipLaunchKernelGGL(p.r.sc.wide_leaves ? k_trace_batch_prim_mixed<true>
+                                                              : k_trace_batch_prim_mixed<false>,
+                                           dim3((unsigned)((c.n + kBlock - 1) / kBlock)), dim3(kBlock), 0, st, p, *pd, c);
+                else
+                        hipLaunchKernelGGL(p.r.sc.wide_leaves ? k_trace_batch_prim<true> : k_trace_batch_prim<false>,
+                                           dim3((unsigned)((c.n + kBlock - 1) / kBlock)), dim3(kBlock), 0, st, p, c);
                 hipLaunchKernelGGL(k_cones_batch<false>, dim3((unsigned)((c.n + kBatchRays - 1) / kBatchRays)),
                                    dim3(64), 0, st, p, c);
         }

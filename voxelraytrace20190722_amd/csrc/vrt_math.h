@@ -221,6 +221,77 @@ VRT_HD bool aabb_isect(const float bmin[3], const float bmax[3], f3 o,
 }
 
 // ---------------------------------------------------------------------
+// LightProbe as a voxel (VRT/voxel_octree.cc:541-591).
+// ---------------------------------------------------------------------
+// LightProbe::is_overlap (VRT/voxel_octree.cc:567-586): r*r minus the squared
+// distance of the centre to the box, per axis, > 0.
+VRT_HD bool probe_overlap(f3 o, float r, const float bmin[3], const float bmax[3])
+{
+        const float oo[3] = { o.x, o.y, o.z };
+        float dist_squared = r * r;
+        for (int k = 0; k < 3; ++k) {
+                if (oo[k] < bmin[k]) {
+                        const float v = oo[k] - bmin[k];
+                        dist_squared -= v * v;
+                } else if (oo[k] > bmax[k]) {
+                        const float v = oo[k] - bmax[k];
+                        dist_squared -= v * v;
+                }
+        }
+        return dist_squared > 0;
+}
+
+// jql::sphere_ray_isect with quadratic_solver inlined (VRT/graphics_math.h:
+// 1105-1126, 1175-1206): a = 1, so 4*a*c = 4*c, 2*a = 2.  The ray's
+// tmin/tmax are not consulted.  std::min/std::max keep their own comparison:
+// with tmp == 0, t2_ is NaN and both roots come out as t1_.
+VRT_HD bool sphere_ray_isect(f3 so, float sr, f3 ro, f3 rd, float *t)
+{
+        const float a = 1.f;
+        const f3 tmp3 = ro - so;
+        const float b = 2.f * dot(tmp3, rd);
+        const float c = dot(tmp3, tmp3) - sr * sr;
+        const float delta = b * b - (4.f * a) * c;
+        if (delta < 0)
+                return false;
+        float tmp;
+        if (b > 0)
+                tmp = -b - sqrtf(delta);
+        else
+                tmp = -b + sqrtf(delta);
+        const float t1_ = tmp / (2.f * a);
+        const float t2_ = (2.f * c) / tmp;
+        const float t1 = std_min(t1_, t2_);
+        const float t2 = std_max(t1_, t2_);
+        if (t2 < 0)
+                return false;
+        if (t1 >= 0) {
+                *t = t1;
+                return true;
+        } else if (t2 >= 0) {
+                *t = t2;
+                return true;
+        }
+        return false;
+}
+
+// LightProbe::isect (VRT/voxel_octree.cc:546-554): `*isect = ISect{ray.o + t *
+// ray.d, isect->hit - o_}` reads the ISect's hit point *before* the
+// assignment, and ISect's constructor normalises its second argument
+// (VRT/graphics_math.h:1138-1142): normal = normalize(prev_hit - o_), hit =
+// o + t * d.  prev_hit is whatever the caller's ISect held.
+VRT_HD bool probe_isect(f3 po, float pr, f3 ro, f3 rd, f3 prev_hit, float *t, f3 *hit, f3 *normal)
+{
+        float tt = 0.f;
+        if (!sphere_ray_isect(po, pr, ro, rd, &tt))
+                return false;
+        *t = tt;
+        *hit = ro + rd * tt;
+        *normal = normalize(prev_hit - po);
+        return true;
+}
+
+// ---------------------------------------------------------------------
 // Texture addressing, VRT/voxel_octree.cc:392-422.
 // unit_cycle subtracts/adds 1 one step at a time; for |s| < 2^24 every step
 // but the last upward one is exact, so the loop equals the closed form
