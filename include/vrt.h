@@ -88,7 +88,7 @@ typedef struct {
         float root_min[3], root_max[3];
         int64_t device_bytes;
         double build_ms, upload_ms;
-        double build_device_ms;  /* GPU part of a VRT_BUILD_DEVICE build, else 0 */
+        double build_device_ms;  /* GPU part of a VRT_BUILD_DEVICE build (probes included), else 0 */
 } vrt_scene_info_t;
 
 /* Optional per-sample outputs of vrt_render (host arrays, index
@@ -122,6 +122,10 @@ int vrt_scene_create(const vrt_scene_desc *desc, int max_depth, int device,
  * (level-synchronous SAT descent + hipCUB sorts + BFS flatten, SURVEY §8
  * f3); the octree is identical to the host build.  Needs device >= 0. */
 #define VRT_BUILD_DEVICE 1
+/* With VRT_BUILD_DEVICE in vrt_scene_create_probes: the light probes are
+ * inserted on the GPU too (see there).  Without probes the bit changes
+ * nothing; without VRT_BUILD_DEVICE it is VRT_E_INVALID. */
+#define VRT_BUILD_DEVICE_PROBES 4
 int vrt_scene_create_ex(const vrt_scene_desc *desc, int max_depth, int device,
                         int flags, vrt_scene **out);
 void vrt_scene_destroy(vrt_scene *s);
@@ -551,8 +555,20 @@ int vrt_probe_eval(const vrt_sg *sgs, int64_t n, const float *dirs, int64_t m, f
  * (VRT/voxel_octree.cc:567-586).  A leaf's list is its triangles in input
  * order, then its probes in probe order.  nprobe == 0 or probes == NULL is
  * vrt_scene_create_ex.  Bounds: ntri + nprobe < 2^31, o finite, r finite and
- * >= 0 (r == 0 overlaps nothing).  VRT_BUILD_DEVICE with probes is
- * VRT_E_INVALID: the device build inserts triangles only (out of scope here).
+ * >= 0 (r == 0 overlaps nothing).
+ *
+ * flags: 0 builds on the host.  VRT_BUILD_DEVICE | VRT_BUILD_DEVICE_PROBES
+ * (needs device >= 0) runs the whole build on the GPU: the probes are a
+ * second frontier of (probe, node) pairs beside the triangles', expanded
+ * level by level with LightProbe::is_overlap; a level's internal nodes are
+ * those of both frontiers, and the probe lists and masks are written by the
+ * device.  Every array equals the host build's, and vrt_scene_info's
+ * build_device_ms covers triangles and probes.  VRT_BUILD_DEVICE alone with
+ * probes is VRT_E_INVALID (it inserts triangles only), as is
+ * VRT_BUILD_DEVICE_PROBES alone or any other bit.  Limits of the device
+ * build (VRT_E_INVALID): at every level 8 x the (triangle, node) pairs and
+ * 8 x the (probe, node) pairs stay below 2^31 each, and the tree below 2^31
+ * nodes.
  *
  * Every visible-only call (vrt_ray_march_batch, vrt_lightmap_build's light
  * pass, vrt_probe_gather, vrt_cone_trace_batch, vrt_render,

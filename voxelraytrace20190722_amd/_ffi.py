@@ -103,6 +103,7 @@ class ObjInfo(C.Structure):
 
 VRT_OBJ_PARSE_ONLY = 1
 VRT_BUILD_DEVICE = 1
+VRT_BUILD_DEVICE_PROBES = 4
 VRT_MARCH_EVEN_INVISIBLE = 1
 
 _P = C.c_void_p

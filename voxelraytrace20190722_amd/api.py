@@ -288,12 +288,15 @@ class VoxelOctree:
     def __init__(self, scene, max_depth, device=0, build_on_device=False, probes=None):
         """probes: (n, 4) light probes {o, r} (or LightProbe objects) pushed
         into the voxel list behind the triangles, as VRT/main.cc:56-64 does:
-        voxel ntri + k is probe k (vrt_scene_create_probes)."""
+        voxel ntri + k is probe k (vrt_scene_create_probes).  build_on_device
+        builds the whole tree on the GPU, the probes included."""
         self.scene = scene  # keeps the arrays alive for the descriptor
         h = C.c_void_p()
         d = scene.desc()
         flags = _ffi.VRT_BUILD_DEVICE if build_on_device else 0
         self.probes = _probes_arg(probes)
+        if build_on_device and self.probes is not None:
+            flags |= _ffi.VRT_BUILD_DEVICE_PROBES
         if self.probes is None:
             check(lib().vrt_scene_create_ex(C.byref(d), int(max_depth), int(device), flags, C.byref(h)),
                   "vrt_scene_create")

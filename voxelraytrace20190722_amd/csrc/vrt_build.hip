@@ -16,6 +16,15 @@
 // (children boxes from the parent's stored box with split()'s float ops),
 // and the content masks bottom-up.  Node boxes, codes, leaf lists and masks
 // are identical to the host build (tests/test_gpu.py).
+//
+// Light probes (vrt_scene_create_probes with VRT_BUILD_DEVICE_PROBES) are a
+// second frontier beside the triangles': (probe, node code, node box) pairs
+// expanded with LightProbe::is_overlap (probe_overlap).  A level's internal
+// nodes are the sorted unique codes of both frontiers together; the probes'
+// leaf lists, sorted (code << 32 | probe), stay apart from the triangles' in
+// the side arrays pnode / pref, as in the host build
+// (tests/test_probe_build_gpu.py).  A scene without probes takes none of the
+// probe launches.
 #include <hipcub/hipcub.hpp>
 
 #include "vrt_internal.h"
@@ -113,6 +122,67 @@ __global__ __launch_bounds__(256) void k_expand(int64_t n, const Pair *__restric
                 for (int c = 0; c < 8; ++c) {
                         child_box_dev(p.mn, p.mx, c, cmn[c], cmx[c]);
                         if (overlaps_dev(tri, cmn[c], cmx[c]))
+                                mask |= 1u << c;
+                }
+        }
+        uint32_t at = wave_append((uint32_t)__popc(mask), counter);
+        if (mask) {
+#pragma unroll
+                for (int c = 0; c < 8; ++c)
+                        if (mask & (1u << c)) {
+                                Pair q;
+#pragma unroll
+                                for (int k = 0; k < 3; ++k) {
+                                        q.mn[k] = cmn[c][k];
+                                        q.mx[k] = cmx[c][k];
+                                }
+                                q.tri = p.tri;
+                                q.code = (p.code << 3) | (uint32_t)c;
+                                out[at++] = q;
+                        }
+        }
+}
+
+// The probe frontier: Pair::tri is the probe index.  A probe that misses the
+// root (r == 0 among them) drops out here.
+__global__ __launch_bounds__(256) void k_seed_probes(int n, const float4 *__restrict__ probes, Pair root,
+                                                     Pair *__restrict__ out, unsigned int *counter)
+{
+        const int i = blockIdx.x * blockDim.x + threadIdx.x;
+        bool hit = false;
+        if (i < n) {
+                const float4 pb = probes[i];
+                hit = probe_overlap(mk3(pb.x, pb.y, pb.z), pb.w, root.mn, root.mx);
+        }
+        const uint32_t at = wave_append(hit ? 1u : 0u, counter);
+        if (hit) {
+                Pair p = root;
+                p.tri = (uint32_t)i;
+                p.code = 0;
+                out[at] = p;
+        }
+}
+
+// k_expand for the probe frontier: LightProbe::is_overlap on the 8 split()
+// children.  `codes` is this frontier's part of the level's code array.
+__global__ __launch_bounds__(256) void k_expand_probes(int64_t n, const Pair *__restrict__ in,
+                                                       const float4 *__restrict__ probes,
+                                                       uint32_t *__restrict__ codes, Pair *__restrict__ out,
+                                                       unsigned int *counter)
+{
+        const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+        uint32_t mask = 0;
+        Pair p;
+        float cmn[8][3], cmx[8][3];
+        if (i < n) {
+                p = in[i];
+                codes[i] = p.code;
+                const float4 pb = probes[p.tri];
+                const f3 o = mk3(pb.x, pb.y, pb.z);
+#pragma unroll
+                for (int c = 0; c < 8; ++c) {
+                        child_box_dev(p.mn, p.mx, c, cmn[c], cmx[c]);
+                        if (probe_overlap(o, pb.w, cmn[c], cmx[c]))
                                 mask |= 1u << c;
                 }
         }
@@ -250,6 +320,57 @@ __global__ __launch_bounds__(256) void k_masks(int64_t begin, int64_t end, NodeR
         has[ni] = m ? 1 : 0;
 }
 
+// pref = the probe indices of the sorted (code << 32 | probe) keys
+__global__ __launch_bounds__(256) void k_pref(int64_t n, const uint64_t *__restrict__ keys,
+                                              uint32_t *__restrict__ pref)
+{
+        const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+        if (i < n)
+                pref[i] = (uint32_t)(keys[i] & 0xFFFFFFFFu);
+}
+
+// k_flatten's leaf part for the probes: pnode = (first, count) of the
+// max-depth leaves [begin, begin + count) in the sorted probe keys (pnode is
+// zero elsewhere); *leaves counts those with a probe.
+__global__ __launch_bounds__(256) void k_probe_leaves(int level, int64_t begin, int64_t count,
+                                                      const uint32_t *__restrict__ iall,
+                                                      const uint64_t *__restrict__ keys, int64_t nkeys,
+                                                      uint2 *__restrict__ pnode, unsigned int *leaves)
+{
+        const int64_t t = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+        uint32_t some = 0;
+        if (t < count) {
+                const int64_t ni = begin + t;
+                const uint32_t code = level == 1 ? 0u : (iall[(ni - 1) >> 3] << 3) | (uint32_t)((ni - 1) & 7);
+                const uint64_t k0 = (uint64_t)code << 32;
+                const int64_t lo = lower_bound_dev<uint64_t>(keys, nkeys, k0);
+                const int64_t hi = lower_bound_dev<uint64_t>(keys, nkeys, k0 + (1ull << 32));
+                pnode[ni] = make_uint2((uint32_t)lo, (uint32_t)(hi - lo));
+                some = hi > lo ? 1u : 0u;
+        }
+        (void)wave_append(some, leaves);
+}
+
+// k_masks for the probes: an internal node's pnode.x = the children with a
+// probe somewhere below (vrt_host.cpp: build_tree)
+__global__ __launch_bounds__(256) void k_probe_masks(int64_t begin, int64_t end, const NodeRec *__restrict__ nodes,
+                                                     uint2 *__restrict__ pnode, uint8_t *__restrict__ has)
+{
+        const int64_t ni = begin + (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+        if (ni >= end)
+                return;
+        const uint32_t a = nodes[ni].a;
+        if (a & kLeafBit) {
+                has[ni] = pnode[ni].y ? 1 : 0;
+                return;
+        }
+        uint32_t m = 0;
+        for (int c = 0; c < 8; ++c)
+                m |= (uint32_t)has[a + c] << c;
+        pnode[ni] = make_uint2(m, 0u);
+        has[ni] = m ? 1 : 0;
+}
+
 struct Dev {
         void *p = nullptr;
         ~Dev()
@@ -280,6 +401,18 @@ struct Dev {
                 }                                                                            \
         } while (0)
 
+// a size limit of the build: VRT_E_INVALID for the caller, not a device error
+#define BLIMIT(cond, ...)                                                                    \
+        do {                                                                                 \
+                if (cond) {                                                                  \
+                        char m_[160];                                                        \
+                        std::snprintf(m_, sizeof m_, __VA_ARGS__);                           \
+                        *err = m_;                                                           \
+                        out->too_large = true;                                               \
+                        return hipErrorInvalidValue;                                         \
+                }                                                                            \
+        } while (0)
+
 unsigned grid_of(int64_t n)
 {
         return (unsigned)((n + 255) / 256);
@@ -288,8 +421,10 @@ unsigned grid_of(int64_t n)
 }  // namespace
 
 hipError_t build_tree_device(int device, const float *pos, int ntri, const float root_mn[3],
-                             const float root_mx[3], int D, DeviceBuild *out, std::string *err)
+                             const float root_mx[3], int D, const vrt_probe *probes, int nprobe, DeviceBuild *out,
+                             std::string *err)
 {
+        static_assert(sizeof(vrt_probe) == sizeof(float4), "vrt_probe layout");
         BCHK(hipSetDevice(device));
         hipStream_t st = nullptr;
         hipEvent_t e0, e1;
@@ -304,8 +439,13 @@ hipError_t build_tree_device(int device, const float *pos, int ntri, const float
                 }
         } evg{ e0, e1 };
         Dev dpos, cnt, pa, pb, codes, codes_s, uniq, nuniq, temp, iall, keys, keys_s, inode, dnodes, dvox, dhas;
+        Dev dprobes, qa, qb, pkeys, pkeys_s, dpref, dpnode, dphas;  // the probe frontier and its outputs
         BCHK(dpos.alloc((size_t)ntri * 36));
         BCHK(hipMemcpy(dpos.p, pos, (size_t)ntri * 36, hipMemcpyHostToDevice));
+        if (nprobe > 0) {
+                BCHK(dprobes.alloc((size_t)nprobe * sizeof(float4)));
+                BCHK(hipMemcpy(dprobes.p, probes, (size_t)nprobe * sizeof(float4), hipMemcpyHostToDevice));
+        }
         BCHK(hipEventRecord(e0, st));
         BCHK(cnt.alloc(16));
         Pair root;
@@ -325,11 +465,38 @@ hipError_t build_tree_device(int device, const float *pos, int ntri, const float
         unsigned int hn = 0;
         BCHK(hipMemcpy(&hn, cnt.p, 4, hipMemcpyDeviceToHost));
         int64_t n = hn;
+        // the probes' counter is the second word of cnt
+        unsigned int *const qcnt = cnt.as<unsigned int>() + 1;
+        int64_t nq = 0;
+        if (nprobe > 0) {
+                BCHK(qa.alloc((size_t)nprobe * sizeof(Pair)));
+                hipLaunchKernelGGL(k_seed_probes, dim3(grid_of(nprobe)), dim3(256), 0, st, nprobe,
+                                   dprobes.as<float4>(), root, qa.as<Pair>(), qcnt);
+                BCHK(hipGetLastError());
+                BCHK(hipMemcpy(&hn, qcnt, 4, hipMemcpyDeviceToHost));
+                nq = hn;
+        }
         std::vector<uint32_t> h_iall;          // internal codes, level by level
         std::vector<int64_t> n_int(D + 1, 0);  // per level
-        int64_t nrefs = 0;
+        int64_t nrefs = 0, nprefs = 0;
         for (int l = 1; l <= D; ++l) {
                 if (l == D) {
+                        // probe leaf lists: sort (code << 32 | probe)
+                        nprefs = nq;
+                        if (nq > 0) {
+                                BCHK(pkeys.alloc((size_t)nq * 8));
+                                BCHK(pkeys_s.alloc((size_t)nq * 8));
+                                hipLaunchKernelGGL(k_leaf_keys, dim3(grid_of(nq)), dim3(256), 0, st, nq, qa.as<Pair>(),
+                                                   pkeys.as<uint64_t>());
+                                BCHK(hipGetLastError());
+                                size_t tb = 0;
+                                const int bits = 32 + 3 * (D - 1);
+                                BCHK(hipcub::DeviceRadixSort::SortKeys(nullptr, tb, pkeys.as<uint64_t>(),
+                                                                       pkeys_s.as<uint64_t>(), (int)nq, 0, bits, st));
+                                BCHK(temp.alloc(tb));
+                                BCHK(hipcub::DeviceRadixSort::SortKeys(temp.p, tb, pkeys.as<uint64_t>(),
+                                                                       pkeys_s.as<uint64_t>(), (int)nq, 0, bits, st));
+                        }
                         // leaf lists: sort (code << 32 | tri)
                         nrefs = n;
                         BCHK(keys.alloc((size_t)std::max<int64_t>(1, n) * 8));
@@ -348,8 +515,15 @@ hipError_t build_tree_device(int device, const float *pos, int ntri, const float
                         }
                         break;
                 }
-                // expand: codes of this level + next frontier
-                BCHK(codes.alloc((size_t)std::max<int64_t>(1, n) * 4));
+                // the append counters are 32-bit and hipCUB takes int counts
+                BLIMIT(8 * n > 0x7FFFFFFF, "device octree build: %lld (triangle, node) pairs at level %d, 8 x that must stay below 2^31",
+                       (long long)n, l);
+                BLIMIT(8 * nq > 0x7FFFFFFF, "device octree build: %lld (probe, node) pairs at level %d, 8 x that must stay below 2^31",
+                       (long long)nq, l);
+                // expand: codes of this level (the triangles' pairs, then the
+                // probes') + next frontiers
+                const int64_t nc = n + nq;
+                BCHK(codes.alloc((size_t)std::max<int64_t>(1, nc) * 4));
                 BCHK(pb.alloc((size_t)std::max<int64_t>(1, 8 * n) * sizeof(Pair)));
                 BCHK(hipMemsetAsync(cnt.p, 0, 16, st));
                 if (n > 0)
@@ -357,23 +531,29 @@ hipError_t build_tree_device(int device, const float *pos, int ntri, const float
                                            dpos.as<float>(), codes.as<uint32_t>(), pb.as<Pair>(),
                                            cnt.as<unsigned int>());
                 BCHK(hipGetLastError());
+                if (nq > 0) {
+                        BCHK(qb.alloc((size_t)(8 * nq) * sizeof(Pair)));
+                        hipLaunchKernelGGL(k_expand_probes, dim3(grid_of(nq)), dim3(256), 0, st, nq, qa.as<Pair>(),
+                                           dprobes.as<float4>(), codes.as<uint32_t>() + n, qb.as<Pair>(), qcnt);
+                        BCHK(hipGetLastError());
+                }
                 // internal nodes of level l = sorted unique codes
                 int64_t nu = 0;
-                if (n > 0) {
+                if (nc > 0) {
                         const int bits = std::max(1, 3 * (l - 1));
-                        BCHK(codes_s.alloc((size_t)n * 4));
-                        BCHK(uniq.alloc((size_t)n * 4));
+                        BCHK(codes_s.alloc((size_t)nc * 4));
+                        BCHK(uniq.alloc((size_t)nc * 4));
                         BCHK(nuniq.alloc(8));
                         size_t tb = 0, tb2 = 0;
                         BCHK(hipcub::DeviceRadixSort::SortKeys(nullptr, tb, codes.as<uint32_t>(), codes_s.as<uint32_t>(),
-                                                               (int)n, 0, bits, st));
+                                                               (int)nc, 0, bits, st));
                         BCHK(hipcub::DeviceSelect::Unique(nullptr, tb2, codes_s.as<uint32_t>(), uniq.as<uint32_t>(),
-                                                          nuniq.as<int>(), (int)n, st));
+                                                          nuniq.as<int>(), (int)nc, st));
                         BCHK(temp.alloc(std::max(tb, tb2)));
                         BCHK(hipcub::DeviceRadixSort::SortKeys(temp.p, tb, codes.as<uint32_t>(), codes_s.as<uint32_t>(),
-                                                               (int)n, 0, bits, st));
+                                                               (int)nc, 0, bits, st));
                         BCHK(hipcub::DeviceSelect::Unique(temp.p, tb2, codes_s.as<uint32_t>(), uniq.as<uint32_t>(),
-                                                          nuniq.as<int>(), (int)n, st));
+                                                          nuniq.as<int>(), (int)nc, st));
                         int hnu = 0;
                         BCHK(hipMemcpy(&hnu, nuniq.p, 4, hipMemcpyDeviceToHost));
                         nu = hnu;
@@ -386,6 +566,11 @@ hipError_t build_tree_device(int device, const float *pos, int ntri, const float
                 BCHK(hipMemcpy(&hn, cnt.p, 4, hipMemcpyDeviceToHost));
                 n = hn;
                 std::swap(pa.p, pb.p);
+                if (nq > 0) {
+                        BCHK(hipMemcpy(&hn, qcnt, 4, hipMemcpyDeviceToHost));
+                        nq = hn;
+                        std::swap(qa.p, qb.p);
+                }
                 if (nu == 0)
                         break;  // nothing below this level
         }
@@ -393,6 +578,7 @@ hipError_t build_tree_device(int device, const float *pos, int ntri, const float
         // per internal node of the previous level, in code order)
         int64_t ninternal = (int64_t)h_iall.size();
         const int64_t nnodes = 1 + 8 * ninternal;
+        BLIMIT(nnodes > 0x7FFFFFFF, "octree too large (%lld nodes)", (long long)nnodes);
         out->level_begin.clear();
         BCHK(iall.alloc(std::max<size_t>(1, h_iall.size()) * 4));
         if (!h_iall.empty())
@@ -435,6 +621,32 @@ hipError_t build_tree_device(int device, const float *pos, int ntri, const float
                                    dhas.as<uint8_t>());
                 BCHK(hipGetLastError());
         }
+        // the probes' side arrays: leaf lists at max depth, then their child
+        // masks bottom-up; all zero when no probe reached a leaf
+        const int nlevels = (int)out->level_begin.size() - 1;
+        if (nprobe > 0) {
+                BCHK(dpnode.alloc((size_t)nnodes * sizeof(uint2)));
+                BCHK(hipMemsetAsync(dpnode.p, 0, (size_t)nnodes * sizeof(uint2), st));
+        }
+        if (nprefs > 0 && nlevels == D) {
+                unsigned int *const lcnt = cnt.as<unsigned int>() + 2;
+                BCHK(hipMemsetAsync(lcnt, 0, 4, st));
+                BCHK(dpref.alloc((size_t)nprefs * 4));
+                hipLaunchKernelGGL(k_pref, dim3(grid_of(nprefs)), dim3(256), 0, st, nprefs, pkeys_s.as<uint64_t>(),
+                                   dpref.as<uint32_t>());
+                BCHK(hipGetLastError());
+                const int64_t b0 = out->level_begin[D - 1], b1 = out->level_begin[D];
+                hipLaunchKernelGGL(k_probe_leaves, dim3(grid_of(b1 - b0)), dim3(256), 0, st, D, b0, b1 - b0,
+                                   iall.as<uint32_t>(), pkeys_s.as<uint64_t>(), nprefs, dpnode.as<uint2>(), lcnt);
+                BCHK(hipGetLastError());
+                BCHK(dphas.alloc((size_t)nnodes));
+                for (int l = nlevels; l >= 1; --l) {
+                        const int64_t c0 = out->level_begin[l - 1], c1 = out->level_begin[l];
+                        hipLaunchKernelGGL(k_probe_masks, dim3(grid_of(c1 - c0)), dim3(256), 0, st, c0, c1,
+                                           dnodes.as<NodeRec>(), dpnode.as<uint2>(), dphas.as<uint8_t>());
+                        BCHK(hipGetLastError());
+                }
+        }
         BCHK(hipEventRecord(e1, st));
         BCHK(hipEventSynchronize(e1));
         float ms = 0.f;
@@ -448,6 +660,20 @@ hipError_t build_tree_device(int device, const float *pos, int ntri, const float
         BCHK(hipMemcpy(out->node_vox.data(), dvox.p, (size_t)nnodes * 4, hipMemcpyDeviceToHost));
         if (nrefs)
                 BCHK(hipMemcpy(out->refs.data(), keys_s.p, (size_t)nrefs * 8, hipMemcpyDeviceToHost));
+        out->pnode.clear();
+        out->pref.clear();
+        out->probe_leaves = 0;
+        if (nprobe > 0) {
+                out->pnode.resize((size_t)nnodes);
+                BCHK(hipMemcpy(out->pnode.data(), dpnode.p, (size_t)nnodes * sizeof(uint2), hipMemcpyDeviceToHost));
+        }
+        if (nprefs > 0 && nlevels == D) {
+                unsigned int hl = 0;
+                out->pref.resize((size_t)nprefs);
+                BCHK(hipMemcpy(out->pref.data(), dpref.p, (size_t)nprefs * 4, hipMemcpyDeviceToHost));
+                BCHK(hipMemcpy(&hl, cnt.as<unsigned int>() + 2, 4, hipMemcpyDeviceToHost));
+                out->probe_leaves = hl;
+        }
         return hipSuccess;
 }
 

@@ -503,11 +503,18 @@ static int build_tree(vrt_scene *s, const vrt_scene_desc *d, bool on_device)
                 int rc = check_device(s->device);
                 if (rc)
                         return rc;
-                if (build_tree_device(s->device, d->pos, n, root.mn, root.mx, D, &db, &err) != hipSuccess)
+                if (build_tree_device(s->device, d->pos, n, root.mn, root.mx, D, s->probes.data(),
+                                      (int)s->probes.size(), &db, &err) != hipSuccess) {
+                        if (db.too_large)
+                                return fail(VRT_E_INVALID, "%s", err.c_str());
                         return fail(VRT_E_DEVICE, "device octree build: %s", err.c_str());
+                }
                 s->nodes.swap(db.nodes);
                 s->node_vox.swap(db.node_vox);
                 s->level_begin.swap(db.level_begin);
+                s->pnode.swap(db.pnode);
+                s->pref.swap(db.pref);
+                s->probe_leaves = db.probe_leaves;
                 s->info.build_device_ms = db.device_ms;
                 return finish_tree(s, d, root, db.refs, db.ninternal);
         }
@@ -1146,15 +1153,18 @@ static int scene_create(const vrt_scene_desc *d, const vrt_probe *probes, int32_
         int rc = validate_desc(d, max_depth);
         if (rc)
                 return rc;
-        if (flags & ~VRT_BUILD_DEVICE)
+        if (flags & ~(VRT_BUILD_DEVICE | VRT_BUILD_DEVICE_PROBES))
                 return fail(VRT_E_INVALID, "unknown flags %#x", flags);
+        if ((flags & VRT_BUILD_DEVICE_PROBES) && !(flags & VRT_BUILD_DEVICE))
+                return fail(VRT_E_INVALID, "VRT_BUILD_DEVICE_PROBES goes with VRT_BUILD_DEVICE (flags %#x)", flags);
         if ((flags & VRT_BUILD_DEVICE) && device < 0)
                 return fail(VRT_E_INVALID, "VRT_BUILD_DEVICE needs a device (device >= 0)");
         if (probes) {
                 if (nprobe < 1 || (int64_t)d->ntri + (int64_t)nprobe > 0x7FFFFFFF)
                         return fail(VRT_E_INVALID, "bad probe count %d (ntri + nprobe must stay below 2^31)", nprobe);
-                if (flags & VRT_BUILD_DEVICE)
-                        return fail(VRT_E_INVALID, "VRT_BUILD_DEVICE inserts triangles only: build a probe scene on the host");
+                if ((flags & VRT_BUILD_DEVICE) && !(flags & VRT_BUILD_DEVICE_PROBES))
+                        return fail(VRT_E_INVALID, "VRT_BUILD_DEVICE alone inserts triangles only: add "
+                                                   "VRT_BUILD_DEVICE_PROBES to build a probe scene on the device");
                 for (int32_t k = 0; k < nprobe; ++k) {
                         const vrt_probe &pb = probes[k];
                         if (!std::isfinite(pb.o[0]) || !std::isfinite(pb.o[1]) || !std::isfinite(pb.o[2]) ||

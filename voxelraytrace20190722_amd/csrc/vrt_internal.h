@@ -580,9 +580,18 @@ struct DeviceBuild {
         std::vector<int64_t> level_begin;  // BFS level ranges (+ end)
         int64_t ninternal = 0;
         double device_ms = 0;              // descent + sorts + flatten + masks
+        // with probes (nprobe > 0): the side arrays of vrt_scene, pnode one
+        // per node; empty otherwise
+        std::vector<uint2> pnode;
+        std::vector<uint32_t> pref;
+        int64_t probe_leaves = 0;
+        bool too_large = false;            // the error is a size limit (VRT_E_INVALID), not the device's
 };
+// probes / nprobe: the light probes inserted behind the triangles (nprobe
+// == 0: a triangle scene, which takes none of the probe launches)
 hipError_t build_tree_device(int device, const float *pos, int ntri, const float root_mn[3],
-                             const float root_mx[3], int max_depth, DeviceBuild *out, std::string *err);
+                             const float root_mx[3], int max_depth, const vrt_probe *probes, int nprobe,
+                             DeviceBuild *out, std::string *err);
 
 // Host helpers shared by vrt_host.cpp and vrt_multi.cpp (hidden symbols).
 // scene_replicate: src's host-side build uploaded to another device.

@@ -253,6 +253,9 @@ extern "C" int vrt_scene_create_multi(const vrt_scene_desc *desc, int max_depth,
         m->st.assign(n, nullptr);
         m->ev.assign(n, nullptr);
         m->send.assign(n, nullptr);
+        // no probes in a multi-device scene: VRT_BUILD_DEVICE_PROBES is refused too
+        if (flags & ~VRT_BUILD_DEVICE)
+                return set_error(VRT_E_INVALID, "vrt_scene_create_multi: unknown flags %#x", flags);
         // build once (host, or rank 0's device with VRT_BUILD_DEVICE) ...
         if (int rc = vrt_scene_create_ex(desc, max_depth, devs[0], flags, &m->sc[0]))
                 return rc;
