@@ -577,7 +577,8 @@ int vrt_probe_eval(const vrt_sg *sgs, int64_t n, const float *dirs, int64_t m, f
  * tri_refs keep their triangle meaning; nodes, internal and leaves count the
  * whole tree.  Not available on a probe scene (VRT_E_INVALID; use
  * vrt_trace_batch): vrt_render_trace[_device], vrt_trace_frame_device and
- * vrt_render's instrumented counters. */
+ * vrt_render's instrumented counters.  A probe scene's film frames are
+ * vrt_render_trace_probes[_device] and vrt_trace_frame_probes_device below. */
 int vrt_scene_create_probes(const vrt_scene_desc *desc, const vrt_probe *probes, int32_t nprobe,
                             int max_depth, int device, int flags, vrt_scene **out);
 /* Probes of the scene, leaves that hold at least one probe, and the total
@@ -641,6 +642,67 @@ int vrt_ray_march_batch_ex_device(vrt_scene *s, const vrt_ray *d_rays, int64_t n
  * to rgb[3i..] and albedo[3i..] (host arrays, either may be NULL) and leaves
  * every other element untouched. */
 int vrt_probe_shade_hits(vrt_scene *s, const vrt_hit *hits, int64_t n, float *rgb, float *albedo);
+
+/* ---- probe hits shaded on the device -------------------------------------
+ * LightProbe::eval calls the C library's expf.  The kernels compute the same
+ * bits with a model of it: glibc's table-driven single-precision expf
+ * restated in fp64, in two flavours -- 0: every operation rounded on its own
+ * (glibc's generic build), 1: the argument reduction r = fma(InvLn2N, x, -kd)
+ * fused (glibc's FMA build).  vrt_expf_flavour reports which one this
+ * process's expf is, found once by comparing expf with both flavours at about
+ * 64 K inputs (every binade of [2^-27, 128) for both signs, the special-case
+ * boundaries and the two inputs at which the flavours differ): 0, 1, or -1 for
+ * a libm that is neither.  With -1 every device-shading call below returns
+ * VRT_E_INVALID; vrt_trace_batch and vrt_probe_shade_hits remain the way on
+ * the host. */
+int vrt_expf_flavour(int *flavour);
+/* The host model: y[i] = the model's expf(x[i]), flavour 0 or 1. */
+int vrt_expf_model(const float *x, int64_t n, int flavour, float *y);
+/* The kernels' model on `device` over host arrays (for comparing the device
+ * with vrt_expf_model; either flavour, whatever this process's expf is). */
+int vrt_expf_model_device(int device, const float *x, int64_t n, int flavour, float *y);
+/* The model against this process's expf on the float bit patterns first_bits
+ * + k * stride, k < count (32-bit wrap-around; NaN inputs are skipped):
+ * *mismatches = the patterns whose results differ in bits, *first_bad = the
+ * first such pattern in k order (untouched when there is none; may be NULL).
+ * device < 0: the host model on up to 16 threads; device >= 0: the kernels'
+ * model on that device, chunk by chunk, compared on the host. */
+int vrt_expf_selftest(int device, uint32_t first_bits, uint64_t count, uint32_t stride, int flavour,
+                      uint64_t *mismatches, uint32_t *first_bad);
+
+/* vrt_probe_eval on device arrays (d_sgs: 14 n records, d_dirs: m x 3,
+ * d_rgb: n x m x 3), enqueued on `stream`: the same float operations with the
+ * model's expf of the detected flavour, so the same bytes (a NaN result is NaN
+ * on both, its sign bit may differ). */
+int vrt_probe_eval_device(int device, const vrt_sg *d_sgs, int64_t n, const float *d_dirs, int64_t m,
+                          float *d_rgb, void *stream);
+/* vrt_probe_shade_hits where the batch lies: d_hits, d_rgb, d_albedo are the
+ * device arrays a vrt_trace_batch_device call wrote (either of the last two
+ * may be NULL).  Elements that ended on a probe receive
+ * eval(normalize(hit_p - o)) over the scene's stored SGs; every other element
+ * is left untouched.  No host synchronisation; ordered on `stream` behind the
+ * scene's work in flight. */
+int vrt_probe_shade_hits_device(vrt_scene *s, const vrt_hit *d_hits, int64_t n, float *d_rgb, float *d_albedo,
+                                void *stream);
+
+/* trace() frames of a probe scene (VRT/main.cc:10-30 with the probe block of
+ * :104-105 in place): vrt_render_trace, vrt_render_trace_device and
+ * vrt_trace_frame_device argument for argument, with the mixed march as the
+ * primary pass and a probe hit coloured by LightProbe::eval over the stored
+ * SGs (no cones, no direct term).  s_hit is 0 for a miss, 1 for a triangle, 2
+ * for a probe.  On a scene without probes they are the old calls.
+ * vrt_trace_frame_probes_device: light_color (float[3]) given, the scene's
+ * probes gather behind the filter (vrt_scene_probes_gather's values) before
+ * the view is shaded; NULL keeps the stored SGs. */
+int vrt_render_trace_probes(vrt_scene *s, const vrt_camera *cam, const vrt_film *film, float min_voxel,
+                            float *rgb, int32_t *s_hit, float *s_rgb);
+int vrt_render_trace_probes_device(vrt_scene *s, const vrt_camera *cam, const vrt_film *film,
+                                   float min_voxel, int rank, int nranks, int image_layout,
+                                   float *d_out, void *stream);
+int vrt_trace_frame_probes_device(vrt_scene *s, const vrt_camera *light_cam, const vrt_film *light_film,
+                                  const float *light_color, const vrt_camera *cam, const vrt_film *film,
+                                  float min_voxel, int rank, int nranks, int image_layout, float *d_out,
+                                  void *stream, int64_t *hits);
 
 /* ---- output (VRT/stb_image_write.h:178,723-757) ------------------------- */
 /* Byte-identical to stbi_write_hdr: returns 1 on success, 0 on failure. */

@@ -161,6 +161,18 @@ SIGNATURES = {
     "vrt_probe_overlap": (C.c_int, [C.POINTER(Probe), f32p]),
     "vrt_probe_isect": (C.c_int, [C.POINTER(Probe), C.POINTER(Ray), f32p, f32p, f32p, f32p]),
     "vrt_probe_shade_hits": (C.c_int, [_P, _P, C.c_int64, f32p, f32p]),
+    "vrt_expf_flavour": (C.c_int, [C.POINTER(C.c_int)]),
+    "vrt_expf_model": (C.c_int, [f32p, C.c_int64, C.c_int, f32p]),
+    "vrt_expf_model_device": (C.c_int, [C.c_int, f32p, C.c_int64, C.c_int, f32p]),
+    "vrt_expf_selftest": (C.c_int, [C.c_int, C.c_uint32, C.c_uint64, C.c_uint32, C.c_int,
+                                    C.POINTER(C.c_uint64), C.POINTER(C.c_uint32)]),
+    "vrt_probe_eval_device": (C.c_int, [C.c_int, _P, C.c_int64, _P, C.c_int64, _P, _P]),
+    "vrt_probe_shade_hits_device": (C.c_int, [_P, _P, C.c_int64, _P, _P, _P]),
+    "vrt_render_trace_probes": (C.c_int, [_P, C.POINTER(Camera), C.POINTER(Film), C.c_float, f32p, i32p, f32p]),
+    "vrt_render_trace_probes_device": (C.c_int, [_P, C.POINTER(Camera), C.POINTER(Film), C.c_float, C.c_int,
+                                                 C.c_int, C.c_int, _P, _P]),
+    "vrt_trace_frame_probes_device": (C.c_int, [_P, _P, _P, f32p, _P, _P, C.c_float, C.c_int, C.c_int, C.c_int,
+                                                _P, _P, C.POINTER(C.c_int64)]),
     "vrt_ray_march_batch_ex": (C.c_int, [_P, C.POINTER(Ray), C.c_int64, C.c_int, C.POINTER(Hit)]),
     "vrt_ray_march_batch_ex_device": (C.c_int, [_P, _P, C.c_int64, C.c_int, _P, _P]),
     "vrt_device_selftest": (C.c_int, [C.c_int, f64p, f64p, f32p, i32p, C.c_int64]),

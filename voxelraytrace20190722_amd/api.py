@@ -416,6 +416,13 @@ class VoxelOctree:
         check(lib().vrt_probe_shade_hits(self.h, C.c_void_p(hits.ctypes.data), len(hits), ptr(rgb, _ffi.f32p),
                                          ptr(albedo, _ffi.f32p)), "vrt_probe_shade_hits")
 
+    def probe_shade_hits_device(self, d_hits_ptr, n, d_rgb_ptr=None, d_albedo_ptr=None, stream_ptr=None):
+        """vrt_probe_shade_hits_device: finish a trace_device batch where it
+        lies (device pointers; d_rgb_ptr / d_albedo_ptr may be None)."""
+        vp = lambda q: None if q is None else C.c_void_p(q)
+        check(lib().vrt_probe_shade_hits_device(self.h, C.c_void_p(d_hits_ptr), int(n), vp(d_rgb_ptr),
+                                                vp(d_albedo_ptr), vp(stream_ptr)), "vrt_probe_shade_hits_device")
+
     def ray_march(self, rays, even_invisible=False):
         """Batched gi::ray_march over (n, 8) rays {o, d, tmin, tmax} (d
         normalised).  even_invisible: the reference's last parameter -- on a
@@ -597,6 +604,43 @@ class VoxelOctree:
                                            int(image_layout), C.c_void_p(d_out_ptr),
                                            None if stream_ptr is None else C.c_void_p(stream_ptr), C.byref(hits)),
               "vrt_trace_frame_device")
+        return hits.value
+
+    # ---- trace() frames of a probe scene (probe hits shaded on the device) ----
+    def render_trace_probes(self, cam, film, min_voxel=0.0, samples=False):
+        """render_trace on a probe scene (vrt_render_trace_probes): the mixed
+        march; samples' hit is 0 miss / 1 triangle / 2 probe."""
+        rgb = np.zeros((film.ny, film.nx, 3), np.float32)
+        ns = film.nx * film.ny * 4
+        hit = np.zeros(ns, np.int32) if samples else None
+        srgb = np.zeros((ns, 3), np.float32) if samples else None
+        check(lib().vrt_render_trace_probes(self.h, C.byref(cam.c), C.byref(film.c), float(min_voxel),
+                                            ptr(rgb, _ffi.f32p), ptr(hit, _ffi.i32p), ptr(srgb, _ffi.f32p)),
+              "vrt_render_trace_probes")
+        return (rgb, {"hit": hit, "rgb": srgb}) if samples else rgb
+
+    def render_trace_probes_device(self, cam, film, rank, nranks, image_layout, d_out_ptr, min_voxel=0.0,
+                                   stream_ptr=None):
+        check(lib().vrt_render_trace_probes_device(self.h, C.byref(cam.c), C.byref(film.c), float(min_voxel),
+                                                   int(rank), int(nranks), int(image_layout), C.c_void_p(d_out_ptr),
+                                                   None if stream_ptr is None else C.c_void_p(stream_ptr)),
+              "vrt_render_trace_probes_device")
+
+    def trace_frame_probes_device(self, light_cam, light_film, light_color, cam, film, rank, nranks, image_layout,
+                                  d_out_ptr, min_voxel=0.0, stream_ptr=None):
+        """The reference main() frame with its probe block in one call
+        (vrt_trace_frame_probes_device): light map + filter beside the view's
+        mixed march, the scene's probes' gather (light_color None: the stored
+        SGs are kept), then the cones and the probe hits' colours; returns the
+        light pass's hit count."""
+        hits = C.c_int64()
+        lc = None if light_color is None else _f3(light_color)
+        check(lib().vrt_trace_frame_probes_device(self.h, C.byref(light_cam.c), C.byref(light_film.c),
+                                                  ptr(lc, _ffi.f32p), C.byref(cam.c), C.byref(film.c),
+                                                  float(min_voxel), int(rank), int(nranks), int(image_layout),
+                                                  C.c_void_p(d_out_ptr),
+                                                  None if stream_ptr is None else C.c_void_p(stream_ptr),
+                                                  C.byref(hits)), "vrt_trace_frame_probes_device")
         return hits.value
 
     # ---- batched trace() / cone_trace over the caller's rays and points ----
@@ -848,6 +892,47 @@ def probe_eval(sgs, dirs):
     check(lib().vrt_probe_eval(rec.ctypes.data_as(C.POINTER(_ffi.SGRec)), n, ptr(dirs, _ffi.f32p), m,
                                ptr(rgb, _ffi.f32p)), "vrt_probe_eval")
     return rgb
+
+
+def probe_eval_device(d_sgs_ptr, n, d_dirs_ptr, m, d_rgb_ptr, device=0, stream_ptr=None):
+    """vrt_probe_eval_device: probe_eval over device arrays (14 n vrt_sg
+    records, m x 3 directions -> n x m x 3), enqueued on the stream."""
+    check(lib().vrt_probe_eval_device(int(device), C.c_void_p(d_sgs_ptr), int(n), C.c_void_p(d_dirs_ptr), int(m),
+                                      C.c_void_p(d_rgb_ptr), None if stream_ptr is None else C.c_void_p(stream_ptr)),
+          "vrt_probe_eval_device")
+
+
+def expf_flavour():
+    """Which flavour of the expf model this process's C library computes: 1
+    (fused reduction), 0 (plain) or -1 (neither: no device shading)."""
+    f = C.c_int()
+    check(lib().vrt_expf_flavour(C.byref(f)), "vrt_expf_flavour")
+    return f.value
+
+
+def expf_model(x, flavour, device=None):
+    """The model of expf over a float32 array: on the host (vrt_expf_model),
+    or by the kernels' code on `device` (vrt_expf_model_device)."""
+    x = np.ascontiguousarray(x, np.float32)
+    y = np.empty_like(x)
+    if device is None:
+        check(lib().vrt_expf_model(ptr(x, _ffi.f32p), x.size, int(flavour), ptr(y, _ffi.f32p)), "vrt_expf_model")
+    else:
+        check(lib().vrt_expf_model_device(int(device), ptr(x, _ffi.f32p), x.size, int(flavour), ptr(y, _ffi.f32p)),
+              "vrt_expf_model_device")
+    return y
+
+
+def expf_selftest(first_bits, count, stride=1, flavour=None, device=-1):
+    """vrt_expf_selftest: the model (device < 0: on the host) against libm's
+    expf on the bit patterns first_bits + k * stride, k < count -> (mismatches,
+    first bad pattern or None)."""
+    if flavour is None:
+        flavour = expf_flavour()
+    bad, first = C.c_uint64(), C.c_uint32()
+    check(lib().vrt_expf_selftest(int(device), int(first_bits), int(count), int(stride), int(flavour),
+                                  C.byref(bad), C.byref(first)), "vrt_expf_selftest")
+    return bad.value, (first.value if bad.value else None)
 
 
 class SG:

@@ -384,6 +384,14 @@ struct vrt_scene {
         int64_t probe_leaves = 0;
         void *d_probe = nullptr;
         ProbeDev pdev{};
+        // the stored SGs' device copy (in d_probe), read by the kernels that
+        // shade a probe hit.  The host copy probe_sgs is what the host
+        // shaders read; sgs_stale: a device gather (vrt_trace_frame_probes_
+        // device) wrote the device copy last and the host copy is fetched
+        // before its next reader (sync_probe_sgs)
+        float *d_sgs = nullptr;
+        bool sgs_stale = false;
+        hipEvent_t sg_ev = nullptr;  // vrt_trace_frame_probes_device: the gather is done
         // full trace: two sets of {light-map block (LMRec + cone-descent
         // records + finiteness flag), split-trace records}, taken by
         // alternate light-map builds so that one frame's cone-traced shading
@@ -1068,7 +1076,8 @@ static int upload(vrt_scene *s, const vrt_scene_desc *d)
                 const size_t sz_pn = align_up(s->pnode.size() * sizeof(uint2));
                 const size_t sz_pr = align_up(std::max<size_t>(1, s->pref.size()) * sizeof(uint32_t));
                 const size_t sz_pb = align_up(s->probes.size() * sizeof(vrt_probe));
-                HIPCHK(hipMalloc(&s->d_probe, sz_pn + sz_pr + sz_pb));
+                const size_t sz_sg = align_up(s->probe_sgs.size() * sizeof(vrt_sg));
+                HIPCHK(hipMalloc(&s->d_probe, sz_pn + sz_pr + sz_pb + sz_sg));
                 char *pb = static_cast<char *>(s->d_probe);
                 HIPCHK(hipMemcpy(pb, s->pnode.data(), s->pnode.size() * sizeof(uint2), hipMemcpyHostToDevice));
                 if (!s->pref.empty())
@@ -1080,7 +1089,10 @@ static int upload(vrt_scene *s, const vrt_scene_desc *d)
                 s->pdev.pref = reinterpret_cast<const uint32_t *>(pb + sz_pn);
                 s->pdev.probes = reinterpret_cast<const float4 *>(pb + sz_pn + sz_pr);
                 s->pdev.ntri = s->ntri;
-                tot += sz_pn + sz_pr + sz_pb;
+                s->d_sgs = reinterpret_cast<float *>(pb + sz_pn + sz_pr + sz_pb);
+                HIPCHK(hipMemcpy(s->d_sgs, s->probe_sgs.data(), s->probe_sgs.size() * sizeof(vrt_sg),
+                                 hipMemcpyHostToDevice));
+                tot += sz_pn + sz_pr + sz_pb + sz_sg;
         }
         s->info.device_bytes = (int64_t)tot;
         HIPCHK(hipStreamCreateWithFlags(&s->stream, hipStreamNonBlocking));
@@ -1347,6 +1359,8 @@ extern "C" void vrt_scene_destroy(vrt_scene *s)
                                 (void)hipEventDestroy(s->q_ev[k]);
                 if (s->lm_ev)
                         (void)hipEventDestroy(s->lm_ev);
+                if (s->sg_ev)
+                        (void)hipEventDestroy(s->sg_ev);
                 HostOut &ho = s->ho;
                 if (ho.st2)
                         (void)hipStreamSynchronize(ho.st2);
@@ -3173,6 +3187,7 @@ static int batch_staging(vrt_scene *s, size_t bytes)
 // element at offset 0; out: the requested arrays behind it, out_sz[k] bytes
 // per element each), one host sync per chunk.
 static void probe_shade(const vrt_scene *s, const vrt_hit *hits, int64_t n, float *rgb, float *albedo);
+static int fetch_probe_sgs(vrt_scene *s);
 
 static int batch_host(vrt_scene *s, const void *in, size_t in_sz, bool rays, int64_t n, float min_voxel,
                       void *const out[5], const size_t out_sz[5])
@@ -3214,10 +3229,13 @@ static int batch_host(vrt_scene *s, const void *in, size_t in_sz, bool rays, int
                 HIPCHK(hipMemcpyAsync(h + (size_t)m * in_sz, d + (size_t)m * in_sz, off - (size_t)m * in_sz,
                                       hipMemcpyDeviceToHost, s->stream));
                 HIPCHK(hipStreamSynchronize(s->stream));
-                if (shade)
+                if (shade) {
+                        if (int rc = fetch_probe_sgs(s))  // a device gather may hold the latest SGs
+                                return rc;
                         probe_shade(s, reinterpret_cast<const vrt_hit *>(h + o5[1]), c,
                                     reinterpret_cast<float *>(h + o5[0]),
                                     out[4] ? reinterpret_cast<float *>(h + o5[4]) : nullptr);
+                }
                 for (int k = 0; k < 5; ++k)
                         if (out[k])
                                 par_memcpy(static_cast<char *>(out[k]) + (size_t)b * out_sz[k], h + o5[k],
@@ -3357,8 +3375,11 @@ static int64_t probe_chunk(int npoints)
 // One gather on stream st over device arrays (caller holds s->mu, the device
 // is set, a light map exists), as batch_enqueue: the current set's light
 // map, step table and record block, taken and released through its event.
+// rec_skip: records at the front of the set's block that belong to a frame in
+// flight (vrt_trace_frame_probes_device: the view's primary records, which the
+// cones + film pass reads after this gather); the gather's own follow them.
 static int probe_enqueue(vrt_scene *s, const ProbeIO &io0, const float *host_points, float min_voxel,
-                         hipStream_t st)
+                         hipStream_t st, size_t rec_skip = 0)
 {
         const int set = s->lm_cur;
         TraceParams tp0, tp;
@@ -3372,8 +3393,9 @@ static int probe_enqueue(vrt_scene *s, const ProbeIO &io0, const float *host_poi
                 vrt_scene_min_voxel(s, 0, &io.res);
         const int64_t chunk = probe_chunk(io.npoints);
         const size_t nslots = (size_t)std::min(io.n, chunk) * kProbeSGs * io.npoints;
-        if (int rc = trace_scratch_n(s, set, tp0, nslots, &tp))
+        if (int rc = trace_scratch_n(s, set, tp0, rec_skip + nslots, &tp))
                 return rc;
+        tp.rec += 4 * rec_skip;
         if (int rc = ts_acquire(s, set, st))
                 return rc;
         (void)hipGetLastError();  // a leftover error of an earlier call is not this launch's
@@ -3554,6 +3576,46 @@ extern "C" int vrt_scene_probe_leaves(const vrt_scene *s, uint32_t *voxel, uint3
         return VRT_OK;
 }
 
+// The stored SGs live twice: probe_sgs on the host (vrt_probe_shade_hits,
+// the host-array trace batch) and d_sgs on the device (the kernels that shade
+// a probe hit).  Whoever changes one copy brings the other up to date before
+// its next reader; both helpers first wait for the scene's work in flight --
+// the scene stream and each trace set's last user, through which every reader
+// and writer of d_sgs is ordered.  Caller holds s->mu.
+static int probe_sgs_quiesce(vrt_scene *s)
+{
+        HIPCHK(hipSetDevice(s->device));
+        HIPCHK(hipStreamSynchronize(s->stream));
+        for (TraceSet &t : s->ts)
+                if (t.live)
+                        HIPCHK(hipEventSynchronize(t.ev));
+        return VRT_OK;
+}
+
+// the host copy changed (vrt_scene_set_probe_sgs, vrt_scene_probes_gather)
+static int upload_probe_sgs(vrt_scene *s)
+{
+        s->sgs_stale = false;
+        if (!s->d_sgs)
+                return VRT_OK;
+        if (int rc = probe_sgs_quiesce(s))
+                return rc;
+        HIPCHK(hipMemcpy(s->d_sgs, s->probe_sgs.data(), s->probe_sgs.size() * sizeof(vrt_sg), hipMemcpyHostToDevice));
+        return VRT_OK;
+}
+
+// a device gather wrote d_sgs last (sgs_stale): fetch before a host reader
+static int fetch_probe_sgs(vrt_scene *s)
+{
+        if (!s->sgs_stale || !s->d_sgs)
+                return VRT_OK;
+        if (int rc = probe_sgs_quiesce(s))
+                return rc;
+        HIPCHK(hipMemcpy(s->probe_sgs.data(), s->d_sgs, s->probe_sgs.size() * sizeof(vrt_sg), hipMemcpyDeviceToHost));
+        s->sgs_stale = false;
+        return VRT_OK;
+}
+
 extern "C" int vrt_scene_set_probe_sgs(vrt_scene *s, const vrt_sg *sgs)
 {
         if (!s || !sgs)
@@ -3562,7 +3624,7 @@ extern "C" int vrt_scene_set_probe_sgs(vrt_scene *s, const vrt_sg *sgs)
                 return fail(VRT_E_INVALID, "the scene has no probes (vrt_scene_create_probes)");
         std::lock_guard<std::mutex> lk(s->mu);
         std::copy(sgs, sgs + s->probe_sgs.size(), s->probe_sgs.begin());
-        return VRT_OK;
+        return upload_probe_sgs(s);
 }
 
 extern "C" int vrt_scene_probe_sgs(const vrt_scene *s, vrt_sg *sgs)
@@ -3571,6 +3633,10 @@ extern "C" int vrt_scene_probe_sgs(const vrt_scene *s, vrt_sg *sgs)
                 return fail(VRT_E_INVALID, "null argument");
         if (s->probes.empty())
                 return fail(VRT_E_INVALID, "the scene has no probes (vrt_scene_create_probes)");
+        vrt_scene *ms = const_cast<vrt_scene *>(s);
+        std::lock_guard<std::mutex> lk(ms->mu);
+        if (int rc = fetch_probe_sgs(ms))  // a device gather may hold the latest
+                return rc;
         std::copy(s->probe_sgs.begin(), s->probe_sgs.end(), sgs);
         return VRT_OK;
 }
@@ -3588,7 +3654,7 @@ extern "C" int vrt_scene_probes_gather(vrt_scene *s, float min_voxel, const floa
                 return rc;
         std::lock_guard<std::mutex> lk(s->mu);
         s->probe_sgs.swap(sgs);
-        return VRT_OK;
+        return upload_probe_sgs(s);
 }
 
 // LightProbe::get_albedo (VRT/voxel_octree.cc:562-566) for the elements of a
@@ -3621,7 +3687,487 @@ extern "C" int vrt_probe_shade_hits(vrt_scene *s, const vrt_hit *hits, int64_t n
         if (!s || n < 0 || (n > 0 && !hits))
                 return fail(VRT_E_INVALID, "bad argument");
         std::lock_guard<std::mutex> lk(s->mu);
+        if (int rc = fetch_probe_sgs(s))
+                return rc;
         probe_shade(s, hits, n, rgb, albedo);
+        return VRT_OK;
+}
+
+// ---- probe hits shaded on the device ---------------------------------------
+// The C library's expf through a volatile argument: the compiler can neither
+// fold the call nor replace it.
+static float libm_expf(float x)
+{
+        volatile float xv = x;
+        return expf(xv);
+}
+
+static float bits_f32(uint32_t u)
+{
+        float f;
+        std::memcpy(&f, &u, 4);
+        return f;
+}
+
+// host threads of the expf sweeps: never more than 16, whatever the machine has
+static int expf_pool()
+{
+        const unsigned h = std::thread::hardware_concurrency();
+        return (int)std::min(16u, std::max(1u, h));
+}
+
+// f(begin, end) over [0, n) split evenly over the pool
+static void expf_parallel(uint64_t n, const std::function<void(int, uint64_t, uint64_t)> &f)
+{
+        const int nt = (int)std::min<uint64_t>((uint64_t)expf_pool(), std::max<uint64_t>(1, n >> 16));
+        if (nt <= 1) {
+                f(0, 0, n);
+                return;
+        }
+        std::vector<std::thread> th;
+        for (int t = 0; t < nt; ++t)
+                th.emplace_back(f, t, n * (uint64_t)t / nt, n * (uint64_t)(t + 1) / nt);
+        for (auto &x : th)
+                x.join();
+}
+
+// The inputs that tell the flavours apart and an unknown libm from both: the
+// two floats at which the flavours differ, the special-case boundaries, and
+// 960 mantissas in every binade of [2^-27, 128) for both signs (65,280).
+static std::vector<float> expf_probe_inputs()
+{
+        std::vector<float> v = { 0x1.04845ep+5f, -0x1.f8cbb2p+5f, 0.f, -0.f, 88.0f, -88.0f,
+                                 0x1.62e42ep6f, 0x1.62e43p6f, 0x1.62e42cp6f,
+                                 -0x1.9fe368p6f, -0x1.9fe36ap6f, -0x1.9fe366p6f, -0x1.9d1d9ep6f,
+                                 std::numeric_limits<float>::infinity(), -std::numeric_limits<float>::infinity(),
+                                 std::numeric_limits<float>::denorm_min(), -std::numeric_limits<float>::denorm_min() };
+        for (uint32_t e = 127 - 27; e < 127 + 7; ++e)
+                for (uint32_t j = 0; j < 960; ++j) {
+                        const uint32_t m = j * 8738u + ((j * 37u) & 0xFFu);
+                        v.push_back(bits_f32((e << 23) | m));
+                        v.push_back(bits_f32(0x80000000u | (e << 23) | m));
+                }
+        return v;
+}
+
+static int expf_flavour_cached()
+{
+        static std::mutex mu;
+        static int flavour = -2;
+        std::lock_guard<std::mutex> lk(mu);
+        if (flavour == -2) {
+                bool is[2] = { true, true };
+                for (float x : expf_probe_inputs()) {
+                        const uint32_t ref = f32_bits(libm_expf(x));
+                        is[0] = is[0] && ref == f32_bits(expf_model(x, false));
+                        is[1] = is[1] && ref == f32_bits(expf_model(x, true));
+                }
+                flavour = is[1] ? 1 : is[0] ? 0 : -1;
+        }
+        return flavour;
+}
+
+extern "C" int vrt_expf_flavour(int *flavour)
+{
+        if (!flavour)
+                return fail(VRT_E_INVALID, "null argument");
+        *flavour = expf_flavour_cached();
+        return VRT_OK;
+}
+
+extern "C" int vrt_expf_model(const float *x, int64_t n, int flavour, float *y)
+{
+        if (n < 0 || (n > 0 && (!x || !y)) || (flavour != 0 && flavour != 1))
+                return fail(VRT_E_INVALID, "bad argument");
+        for (int64_t i = 0; i < n; ++i)
+                y[i] = expf_model(x[i], flavour == 1);
+        return VRT_OK;
+}
+
+// the kernels' model on host arrays (either flavour, whatever libm is)
+extern "C" int vrt_expf_model_device(int device, const float *x, int64_t n, int flavour, float *y)
+{
+        if (n < 0 || (n > 0 && (!x || !y)) || (flavour != 0 && flavour != 1))
+                return fail(VRT_E_INVALID, "bad argument");
+        if (int rc = check_device(device))
+                return rc;
+        if (n == 0)
+                return VRT_OK;
+        HIPCHK(hipSetDevice(device));
+        DevBuf dx, dy;
+        HIPCHK(hipMalloc(&dx.p, (size_t)n * 4));
+        HIPCHK(hipMalloc(&dy.p, (size_t)n * 4));
+        HIPCHK(hipMemcpy(dx.p, x, (size_t)n * 4, hipMemcpyHostToDevice));
+        HIPCHK(launch_expf_model(static_cast<const float *>(dx.p), n, flavour, static_cast<float *>(dy.p), nullptr));
+        HIPCHK(hipDeviceSynchronize());
+        HIPCHK(hipMemcpy(y, dy.p, (size_t)n * 4, hipMemcpyDeviceToHost));
+        return VRT_OK;
+}
+
+// patterns k0 .. k0 + cnt of the sweep against libm: dev = the kernel's
+// results for them (nullptr: the host model); adds to *bad, lowers *first_k
+static void expf_compare(uint32_t first, uint32_t stride, uint64_t k0, uint64_t cnt, int flavour, const float *dev,
+                         uint64_t *bad, uint64_t *first_k)
+{
+        std::mutex mu;
+        expf_parallel(cnt, [&](int, uint64_t b, uint64_t e) {
+                uint64_t nb = 0, fk = UINT64_MAX;
+                for (uint64_t j = b; j < e; ++j) {
+                        const uint32_t u = first + (uint32_t)(k0 + j) * stride;
+                        const float x = bits_f32(u);
+                        if (x != x)
+                                continue;
+                        const float got = dev ? dev[j] : expf_model(x, flavour == 1);
+                        if (f32_bits(got) != f32_bits(libm_expf(x))) {
+                                if (!nb)
+                                        fk = k0 + j;
+                                ++nb;
+                        }
+                }
+                std::lock_guard<std::mutex> lk(mu);
+                *bad += nb;
+                *first_k = std::min(*first_k, fk);
+        });
+}
+
+extern "C" int vrt_expf_selftest(int device, uint32_t first_bits, uint64_t count, uint32_t stride, int flavour,
+                                 uint64_t *mismatches, uint32_t *first_bad)
+{
+        if (!mismatches || (flavour != 0 && flavour != 1))
+                return fail(VRT_E_INVALID, "bad argument");
+        uint64_t bad = 0, first_k = UINT64_MAX;
+        if (device < 0) {
+                expf_compare(first_bits, stride, 0, count, flavour, nullptr, &bad, &first_k);
+        } else {
+                if (int rc = check_device(device))
+                        return rc;
+                HIPCHK(hipSetDevice(device));
+                // two chunks in flight: the kernel and the copy of chunk c run
+                // while the host compares chunk c - 1
+                constexpr uint64_t kChunk = (uint64_t)1 << 24;
+                const uint64_t m = std::min(count, kChunk);
+                struct Bufs {
+                        void *d[2] = {}, *h[2] = {};
+                        hipStream_t st = nullptr;
+                        ~Bufs()
+                        {
+                                for (int k = 0; k < 2; ++k) {
+                                        if (d[k])
+                                                (void)hipFree(d[k]);
+                                        if (h[k])
+                                                (void)hipHostFree(h[k]);
+                                }
+                                if (st)
+                                        (void)hipStreamDestroy(st);
+                        }
+                } bf;
+                if (count > 0) {
+                        HIPCHK(hipStreamCreateWithFlags(&bf.st, hipStreamNonBlocking));
+                        for (int k = 0; k < (count > kChunk ? 2 : 1); ++k) {
+                                HIPCHK(hipMalloc(&bf.d[k], m * 4));
+                                HIPCHK(hipHostMalloc(&bf.h[k], m * 4, hipHostMallocDefault));
+                        }
+                }
+                auto enqueue = [&](uint64_t k0) -> int {
+                        const int b = (int)((k0 / kChunk) & 1);
+                        const uint64_t c = std::min(kChunk, count - k0);
+                        HIPCHK(launch_selftest_expf(first_bits + (uint32_t)k0 * stride, stride, (int64_t)c, flavour,
+                                                    static_cast<float *>(bf.d[b]), bf.st));
+                        HIPCHK(hipMemcpyAsync(bf.h[b], bf.d[b], c * 4, hipMemcpyDeviceToHost, bf.st));
+                        return VRT_OK;
+                };
+                if (count > 0)
+                        if (int rc = enqueue(0))
+                                return rc;
+                for (uint64_t k0 = 0; k0 < count; k0 += kChunk) {
+                        // chunk k0 is the only work on the stream here
+                        HIPCHK(hipStreamSynchronize(bf.st));
+                        if (k0 + kChunk < count)
+                                if (int rc = enqueue(k0 + kChunk))
+                                        return rc;
+                        expf_compare(first_bits, stride, k0, std::min(kChunk, count - k0), flavour,
+                                     static_cast<const float *>(bf.h[(k0 / kChunk) & 1]), &bad, &first_k);
+                }
+        }
+        *mismatches = bad;
+        if (bad && first_bad)
+                *first_bad = first_bits + (uint32_t)first_k * stride;
+        return VRT_OK;
+}
+
+// the detected flavour for a device-shading call, or VRT_E_INVALID
+static int device_expf(const char *what, int *fused)
+{
+        const int f = expf_flavour_cached();
+        if (f < 0)
+                return fail(VRT_E_INVALID,
+                            "%s: this C library's expf is neither flavour of the device model; shade probe hits on "
+                            "the host with vrt_probe_shade_hits",
+                            what);
+        *fused = f;
+        return VRT_OK;
+}
+
+extern "C" int vrt_probe_eval_device(int device, const vrt_sg *d_sgs, int64_t n, const float *d_dirs, int64_t m,
+                                     float *d_rgb, void *stream)
+{
+        if (n < 0 || m < 0 || (n > 0 && m > 0 && n > INT64_MAX / 3 / m))
+                return fail(VRT_E_INVALID, "bad argument");
+        if (n == 0 || m == 0)
+                return VRT_OK;
+        if (!d_sgs || !d_dirs || !d_rgb)
+                return fail(VRT_E_INVALID, "null argument");
+        int fused;
+        if (int rc = device_expf("vrt_probe_eval_device", &fused))
+                return rc;
+        if (int rc = check_device(device))
+                return rc;
+        HIPCHK(hipSetDevice(device));
+        HIPCHK(launch_probe_eval(reinterpret_cast<const float *>(d_sgs), n, d_dirs, m, fused, d_rgb,
+                                 static_cast<hipStream_t>(stream)));
+        return VRT_OK;
+}
+
+extern "C" int vrt_probe_shade_hits_device(vrt_scene *s, const vrt_hit *d_hits, int64_t n, float *d_rgb,
+                                           float *d_albedo, void *stream)
+{
+        if (!s || n < 0 || (n > 0 && !d_hits))
+                return fail(VRT_E_INVALID, "bad argument");
+        if (n == 0 || s->probes.empty() || (!d_rgb && !d_albedo))
+                return VRT_OK;
+        if (need_device(s))
+                return VRT_E_NODEVICE;
+        int fused;
+        if (int rc = device_expf("vrt_probe_shade_hits_device", &fused))
+                return rc;
+        std::lock_guard<std::mutex> lk(s->mu);
+        HIPCHK(hipSetDevice(s->device));
+        hipStream_t st = static_cast<hipStream_t>(stream);
+        // behind the batch that wrote the hits, and a reader of the device SGs:
+        // through the trace sets' events, as vrt_trace_batch_device is
+        const int set = s->lm_cur >= 0 ? s->lm_cur : 0;
+        for (int k = 0; k < 2; ++k)
+                if (int rc = ts_acquire(s, k, st))
+                        return rc;
+        (void)hipGetLastError();
+        const hipError_t e = launch_probe_shade_hits(d_hits, n, s->pdev, (int32_t)s->probes.size(), s->d_sgs, fused,
+                                                     d_rgb, d_albedo, st);
+        if (e != hipSuccess)
+                return fail(VRT_E_DEVICE, "probe shading launch failed: %s", hipGetErrorString(e));
+        return ts_release(s, set, st);
+}
+
+// The arguments the three frame calls share with the old ones.
+static int probe_frame_args_ok(const vrt_film *film, int rank, int nranks, int image_layout)
+{
+        if (int rc = film_ok(film))
+                return rc;
+        if (nranks < 1 || rank < 0 || rank >= nranks)
+                return fail(VRT_E_INVALID, "rank %d of %d", rank, nranks);
+        if (image_layout && nranks != 1)
+                return fail(VRT_E_INVALID, "image_layout requires nranks == 1");
+        return VRT_OK;
+}
+
+extern "C" int vrt_render_trace_probes_device(vrt_scene *s, const vrt_camera *cam, const vrt_film *film,
+                                              float min_voxel, int rank, int nranks, int image_layout, float *d_out,
+                                              void *stream)
+{
+        if (s && s->probes.empty())
+                return vrt_render_trace_device(s, cam, film, min_voxel, rank, nranks, image_layout, d_out, stream);
+        if (s && need_device(s))
+                return VRT_E_NODEVICE;
+        if (!s || !cam || !d_out)
+                return fail(VRT_E_INVALID, "null argument");
+        if (int rc = probe_frame_args_ok(film, rank, nranks, image_layout))
+                return rc;
+        if (int rc = trace_ok(s, min_voxel))
+                return rc;
+        int fused;
+        if (int rc = device_expf("vrt_render_trace_probes_device", &fused))
+                return rc;
+        std::lock_guard<std::mutex> lk(s->mu);
+        if (s->lm_cur < 0)
+                return fail(VRT_E_INVALID, "no light map: call vrt_lightmap_build first");
+        HIPCHK(hipSetDevice(s->device));
+        const int set = s->lm_cur;
+        TraceParams tp0, tp;
+        fill_trace_params(s, set, cam, film, min_voxel, rank, nranks, &tp0);
+        tp0.r.image_layout = image_layout;
+        tp0.r.out = d_out;
+        hipStream_t st = static_cast<hipStream_t>(stream);
+        if (int rc = trace_scratch(s, set, tp0, &tp))
+                return rc;
+        if (int rc = ts_acquire(s, set, st))
+                return rc;
+        HIPCHK(hipEventRecord(s->ev0, st));
+        HIPCHK(launch_trace_prim_mixed(tp, s->pdev, st));
+        steps_commit(s, set, tp);
+        HIPCHK(launch_cones_probes(tp, s->d_sgs, fused, st));
+        HIPCHK(hipEventRecord(s->ev1, st));
+        if (int rc = ts_release(s, set, st))
+                return rc;
+        s->timed = true;
+        return VRT_OK;
+}
+
+extern "C" int vrt_render_trace_probes(vrt_scene *s, const vrt_camera *cam, const vrt_film *film, float min_voxel,
+                                       float *rgb, int32_t *s_hit, float *s_rgb)
+{
+        if (s && s->probes.empty())
+                return vrt_render_trace(s, cam, film, min_voxel, rgb, s_hit, s_rgb);
+        if (s && need_device(s))
+                return VRT_E_NODEVICE;
+        if (!s || !cam || !rgb)
+                return fail(VRT_E_INVALID, "null argument");
+        if (int rc = film_ok(film))
+                return rc;
+        if (int rc = trace_ok(s, min_voxel))
+                return rc;
+        int fused;
+        if (int rc = device_expf("vrt_render_trace_probes", &fused))
+                return rc;
+        std::lock_guard<std::mutex> lk(s->mu);
+        if (s->lm_cur < 0)
+                return fail(VRT_E_INVALID, "no light map: call vrt_lightmap_build first");
+        HIPCHK(hipSetDevice(s->device));
+        const int set = s->lm_cur;
+        const size_t npix = (size_t)film->nx * film->ny, ns = npix * 4;
+        DevBuf img, dh, dr;
+        HIPCHK(hipMalloc(&img.p, npix * 12));
+        HIPCHK(hipMemsetAsync(img.p, 0, npix * 12, s->stream));
+        TraceParams tp0, tp;
+        fill_trace_params(s, set, cam, film, min_voxel, 0, 1, &tp0);
+        tp0.r.image_layout = 1;
+        tp0.r.out = static_cast<float *>(img.p);
+        if (int rc = trace_scratch(s, set, tp0, &tp))
+                return rc;
+        if (s_hit) {
+                HIPCHK(hipMalloc(&dh.p, ns * 4));
+                HIPCHK(hipMemsetAsync(dh.p, 0, ns * 4, s->stream));
+                tp.r.so.hit = static_cast<int32_t *>(dh.p);
+        }
+        if (s_rgb) {
+                HIPCHK(hipMalloc(&dr.p, ns * 12));
+                HIPCHK(hipMemsetAsync(dr.p, 0, ns * 12, s->stream));
+                tp.r.so.rgb = static_cast<float *>(dr.p);
+        }
+        if (int rc = ts_acquire(s, set, s->stream))
+                return rc;
+        HIPCHK(hipEventRecord(s->ev0, s->stream));
+        HIPCHK(launch_trace_prim_mixed(tp, s->pdev, s->stream));
+        steps_commit(s, set, tp);
+        HIPCHK(launch_cones_probes(tp, s->d_sgs, fused, s->stream));
+        HIPCHK(hipEventRecord(s->ev1, s->stream));
+        if (int rc = ts_release(s, set, s->stream))
+                return rc;
+        s->timed = true;
+        HIPCHK(hipStreamSynchronize(s->stream));
+        HIPCHK(hipMemcpy(rgb, img.p, npix * 12, hipMemcpyDeviceToHost));
+        if (s_hit)
+                HIPCHK(hipMemcpy(s_hit, dh.p, ns * 4, hipMemcpyDeviceToHost));
+        if (s_rgb)
+                HIPCHK(hipMemcpy(s_rgb, dr.p, ns * 12, hipMemcpyDeviceToHost));
+        return VRT_OK;
+}
+
+// The reference main() frame with its probe block in place
+// (VRT/main.cc:75-126, :104-105 un-commented) in one call: light pass + filter
+// on the scene's stream and, beside them on `stream`, the view's mixed primary
+// march (it reads neither the light map nor the SGs); with a light colour the
+// scene's probes then gather behind the filter, on the scene's stream, into
+// the device SGs; the cones + film pass waits for whichever came last.  The
+// gather's records follow the view's in the set's block, and the step table
+// is built by the gather (the primary march does not read it).
+extern "C" int vrt_trace_frame_probes_device(vrt_scene *s, const vrt_camera *light_cam,
+                                             const vrt_film *light_film, const float *light_color,
+                                             const vrt_camera *cam, const vrt_film *film, float min_voxel, int rank,
+                                             int nranks, int image_layout, float *d_out, void *stream, int64_t *hits)
+{
+        if (s && s->probes.empty())
+                return vrt_trace_frame_device(s, light_cam, light_film, cam, film, min_voxel, rank, nranks,
+                                              image_layout, d_out, stream, hits);
+        if (s && need_device(s))
+                return VRT_E_NODEVICE;
+        if (!s || !light_cam || !cam || !d_out)
+                return fail(VRT_E_INVALID, "null argument");
+        if (int rc = film_ok(light_film))
+                return rc;
+        if (int rc = probe_frame_args_ok(film, rank, nranks, image_layout))
+                return rc;
+        if (int rc = trace_ok(s, min_voxel))
+                return rc;
+        int fused;
+        if (int rc = device_expf("vrt_trace_frame_probes_device", &fused))
+                return rc;
+        std::lock_guard<std::mutex> lk(s->mu);
+        HIPCHK(hipSetDevice(s->device));
+        hipStream_t st = static_cast<hipStream_t>(stream);
+        if (!s->lm_ev)
+                HIPCHK(hipEventCreateWithFlags(&s->lm_ev, hipEventDisableTiming));
+        if (!s->sg_ev)
+                HIPCHK(hipEventCreateWithFlags(&s->sg_ev, hipEventDisableTiming));
+        const bool gather = light_color != nullptr;
+        const int set = s->ts_next;
+        s->ts_next ^= 1;
+        if (int rc = ensure_lm(s, set))  // the trace parameters point into it
+                return rc;
+        TraceParams tp0, tp;
+        fill_trace_params(s, set, cam, film, min_voxel, rank, nranks, &tp0);
+        tp0.r.image_layout = image_layout;
+        tp0.r.out = d_out;
+        // the view's records first, then (gather) one chunk of the gather's
+        const int64_t nprobe = (int64_t)s->probes.size();
+        const size_t view_slots = (size_t)tp0.r.tiles_this_rank * 256;
+        const size_t gather_slots = gather ? (size_t)std::min(nprobe, probe_chunk(100)) * kProbeSGs * 100 : 0;
+        if (int rc = trace_scratch_n(s, set, tp0, view_slots + gather_slots, &tp))
+                return rc;
+        if (gather)
+                tp.build_steps = 0;  // the gather builds the table, on the scene's stream
+        unsigned int nhit = 0;
+        auto overlap = [&]() -> int {
+                if (int rc = ts_acquire(s, set, st))
+                        return rc;
+                HIPCHK(launch_trace_prim_mixed(tp, s->pdev, st));
+                steps_commit(s, set, tp);
+                return VRT_OK;
+        };
+        auto bail = [&](int rc) {
+                // whatever was enqueued on either stream finishes before the
+                // set's next user starts
+                if (hipEventRecord(s->lm_ev, s->stream) == hipSuccess)
+                        (void)hipStreamWaitEvent(st, s->lm_ev, 0);
+                (void)ts_release(s, set, st);
+                return rc;
+        };
+        if (int rc = lightmap_enqueue(s, set, light_cam, light_film, &nhit, overlap, s->lm_ev))
+                return bail(rc);
+        if (gather) {
+                ProbeIO io{};
+                io.probes = reinterpret_cast<const float *>(s->pdev.probes);
+                io.n = nprobe;
+                io.npoints = 100;
+                std::memcpy(io.light, light_color, sizeof io.light);
+                io.sgs = s->d_sgs;
+                // the other set's last user may still read the device SGs
+                if (int rc = ts_acquire(s, set ^ 1, s->stream))
+                        return bail(rc);
+                s->sgs_stale = true;
+                if (int rc = probe_enqueue(s, io, probe_default_points(), min_voxel, s->stream, view_slots))
+                        return bail(rc);
+                HIPCHK(hipEventRecord(s->sg_ev, s->stream));
+                HIPCHK(hipStreamWaitEvent(st, s->sg_ev, 0));
+        } else {
+                HIPCHK(hipStreamWaitEvent(st, s->lm_ev, 0));
+        }
+        if (hipError_t e = launch_cones_probes(tp, s->d_sgs, fused, st)) {
+                (void)ts_release(s, set, st);
+                return fail(VRT_E_DEVICE, "cone pass launch failed: %s", hipGetErrorString(e));
+        }
+        if (int rc = ts_release(s, set, st))
+                return rc;
+        if (hits)
+                *hits = (int64_t)nhit;
         return VRT_OK;
 }
 

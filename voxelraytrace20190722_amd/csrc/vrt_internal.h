@@ -685,6 +685,22 @@ hipError_t launch_cones_batch(const TraceParams &p, const BatchIO &io, hipStream
 // host_points = npoints x 3 floats on the host
 hipError_t launch_probe_gather(const TraceParams &p, const ProbeIO &io, const float *host_points, int64_t chunk,
                                hipStream_t st);
+// a probe scene's frame (vrt_render_trace_probes*): the mixed primary pass,
+// which writes a probe hit's own record and reads neither the SGs nor the
+// light map, and the cones + film pass that colours those records by
+// LightProbe::eval over sgs (device, 14 vrt_sg per probe).  fused: the host
+// expf's flavour (expf_model), a kernel argument
+hipError_t launch_trace_prim_mixed(const TraceParams &p, const ProbeDev &pd, hipStream_t st);
+hipError_t launch_cones_probes(const TraceParams &p, const float *sgs, int fused, hipStream_t st);
+// out[k] = expf_model(bits first + k * stride), k < n (k_selftest_expf)
+hipError_t launch_selftest_expf(uint32_t first, uint32_t stride, int64_t n, int fused, float *out, hipStream_t st);
+// y[i] = expf_model(x[i]) on the device (device arrays)
+hipError_t launch_expf_model(const float *x, int64_t n, int fused, float *y, hipStream_t st);
+// vrt_probe_eval / vrt_probe_shade_hits over device arrays
+hipError_t launch_probe_eval(const float *sgs, int64_t n, const float *dirs, int64_t m, int fused, float *rgb,
+                             hipStream_t st);
+hipError_t launch_probe_shade_hits(const void *hits, int64_t n, const ProbeDev &pd, int32_t nprobe, const float *sgs,
+                                   int fused, float *rgb, float *albedo, hipStream_t st);
 // per-node cone-descent records and the light map's finiteness flag
 hipError_t launch_lm_aux(const NodeRec *nodes, const LMRec *lm, int64_t n, float4 *cc, uint32_t *bad,
                          hipStream_t st);

@@ -28,6 +28,7 @@
 #include <cmath>
 #include <cstring>
 #include <mutex>
+#include <type_traits>
 #include <vector>
 
 namespace vrt {
@@ -5028,6 +5029,47 @@ __global__ __launch_bounds__(64) void k_trace_prim_tail(TraceParams p)
         }
 }
 
+// The primary pass of a probe scene's frame: trace(root, ray, 5, true)'s
+// ray_march with even_invisible = true (VRT/main.cc:13), the mixed march, over
+// k_trace_prim's units and slots -- one block per tile, its four waves the
+// tile's four work units (the mixed march's stack has kBlock lanes), slot =
+// tile * 256 + tid = unit * 64 + lane.  No budget and no tail pass: the mixed
+// walk is the exact one.  A triangle hit and a miss write trace_prim_record's
+// records.  A probe hit writes {dir xyz, 2}, {probe index}: dir =
+// normalize(hit - o_), LightProbe::get_albedo's argument
+// (VRT/voxel_octree.cc:562-566).  It reads neither the SGs nor the light map,
+// so it runs beside the light pass and the gather.
+template <bool kR64>
+__global__ __launch_bounds__(kBlock) void k_trace_prim_mixed(TraceParams p, ProbeDev pd)
+{
+        __shared__ uint2 stk[kStack * kBlock];
+        const int tid = threadIdx.x;
+        const int u = (int)blockIdx.x * 4;
+        int k, px, py, s, lx, ly;
+        if (!tile_lane_at(p.r, u, tid, k, px, py, s, lx, ly))
+                return;
+        const int64_t slot = (int64_t)u * kRenderBlock + tid;
+        const RayK r = trace_ray(p, px, py, s);
+        MixedResult x;
+        ray_march_mixed<kR64>(p.r.sc, pd, r, stk + tid, x);
+        if (x.hit && x.probe) {
+                const float4 pb = pd.probes[x.vox - (uint32_t)pd.ntri];
+                const f3 dir = normalize(x.hp - mk3(pb.x, pb.y, pb.z));
+                float4 *o = p.rec + 4 * slot;
+                o[0] = make_float4(dir.x, dir.y, dir.z, 2.f);
+                o[1] = make_float4(__uint_as_float(x.vox - (uint32_t)pd.ntri), 0.f, 0.f, 0.f);
+                return;
+        }
+        MarchResult m;
+        m.hit = x.hit;
+        m.node = x.node;
+        m.tri = x.vox;
+        m.u = x.u;
+        m.v = x.v;
+        m.hp = x.hp;
+        trace_prim_record(p, r, m, slot);
+}
+
 // Cones + film: one wave per work unit of the primary pass (its 64 sample
 // slots: 16 pixels x 4 samples, lane = 4 * pixel + sample).  A hit lane
 // marches the 6 cones one after the other (the wave marches the same cone of
@@ -5041,7 +5083,35 @@ __global__ __launch_bounds__(64) void k_trace_prim_tail(TraceParams p)
 #ifndef VRT_CONES_WAVES_PER_EU
 #define VRT_CONES_WAVES_PER_EU 8  // 64 VGPRs, 24 B/lane of spill: +1.9 % over 7 waves (70 VGPRs) since the step table and cells (round 5; round 4, before them: 7 waves +9.8 %)
 #endif
-__global__ __launch_bounds__(64, VRT_CONES_WAVES_PER_EU) void k_cones_film(TraceParams p)
+// LightProbe::get_albedo (VRT/voxel_octree.cc:562-566, 626-632): the probe's 14
+// SG::eval lobes a * expf(s * (dot(dir, d) - 1)) (:503-508) added in order
+// from zero -- vrt_probe_eval's float operations, one rounding each, with the
+// host expf's bits from expf_model (fused: the detected flavour, uniform
+// over the launch).  sg: the probe's 14 vrt_sg records (7 floats each).
+__device__ __forceinline__ f3 probe_albedo(const float *__restrict__ sg, f3 dir, bool fused)
+{
+        f3 lit = mk3(0.f, 0.f, 0.f);
+        for (int i = 0; i < kProbeSGs; ++i) {
+                const float *g = sg + 7 * i;
+                const float tmp = dot(dir, mk3(g[3], g[4], g[5]));
+                const float e = expf_model(g[6] * (tmp - 1), fused);
+                lit = lit + mk3(g[0], g[1], g[2]) * e;
+        }
+        return lit;
+}
+
+// kProbes (a probe scene's frame): a record with w == 2 is a probe hit of
+// k_trace_prim_mixed -- {dir xyz, 2}, {probe index} -- and its colour is the
+// probe's get_albedo over the scene's device SGs: no cones, no direct term
+// (VRT/main.cc:25-29).  <false> takes TraceParams alone and is the kernel as it
+// was before probe frames, instruction for instruction.
+struct TraceParamsProbes : TraceParams {
+        const float *sgs;  // device: 14 vrt_sg per probe
+        int32_t fused;     // the host expf's flavour (expf_model)
+};
+template <bool kProbes>
+__global__ __launch_bounds__(64, VRT_CONES_WAVES_PER_EU) void k_cones_film(
+        std::conditional_t<kProbes, TraceParamsProbes, TraceParams> p)
 {
         const int u = blockIdx.x;
         constexpr int kQ = 4;
@@ -5049,7 +5119,15 @@ __global__ __launch_bounds__(64, VRT_CONES_WAVES_PER_EU) void k_cones_film(Trace
                 return;
         const int64_t slot = (int64_t)u * 64 + threadIdx.x;
         f3 col;
-        if (p.rec[4 * slot + 0].w != 0.f) {
+        bool probe = false;
+        if constexpr (kProbes)
+                probe = p.rec[4 * slot + 0].w == 2.f;
+        if (probe) {
+                const float4 r0 = p.rec[4 * slot + 0], r1 = p.rec[4 * slot + 1];
+                if constexpr (kProbes)
+                        col = probe_albedo(p.sgs + (size_t)__float_as_uint(r1.x) * (7 * kProbeSGs),
+                                           mk3(r0.x, r0.y, r0.z), p.fused != 0);
+        } else if (p.rec[4 * slot + 0].w != 0.f) {
                 // cone_trace with the hit point and normal read from the
                 // sample record per cone (L2 hits) and the basis remade per
                 // cone -- the same values -- rather than held in registers
@@ -5072,8 +5150,12 @@ __global__ __launch_bounds__(64, VRT_CONES_WAVES_PER_EU) void k_cones_film(Trace
         const int lx = (wave & 1) * 4 + (pix & 3), ly = (wave >> 1) * 4 + (pix >> 2);
         const int px = tx * 8 + lx, py = ty * 8 + ly;
         const size_t si = ((size_t)py * p.r.cam.nx + px) * 4 + s;
-        if (p.r.so.hit)
-                p.r.so.hit[si] = p.rec[4 * slot + 0].w != 0.f ? 1 : 0;
+        if (p.r.so.hit) {
+                if constexpr (kProbes)
+                        p.r.so.hit[si] = (int)p.rec[4 * slot + 0].w;  // 0 miss, 1 triangle, 2 probe
+                else
+                        p.r.so.hit[si] = p.rec[4 * slot + 0].w != 0.f ? 1 : 0;
+        }
         if (p.r.so.rgb) {
                 p.r.so.rgb[3 * si + 0] = col.x;
                 p.r.so.rgb[3 * si + 1] = col.y;
@@ -5614,7 +5696,137 @@ hipError_t launch_cones(const TraceParams &p, hipStream_t st)
         if (p.r.tiles_this_rank <= 0)
                 return hipSuccess;
         const int64_t nslots = (int64_t)p.r.tiles_this_rank * 256;
-        hipLaunchKernelGGL(k_cones_film, dim3((unsigned)(nslots / 64)), dim3(64), 0, st, p);
+        hipLaunchKernelGGL(k_cones_film<false>, dim3((unsigned)(nslots / 64)), dim3(64), 0, st, p);
+        return hipGetLastError();
+}
+
+// a probe scene's frame: the mixed primary pass (and the step table when
+// p.build_steps), then the cones + film pass over the device SGs
+hipError_t launch_trace_prim_mixed(const TraceParams &p, const ProbeDev &pd, hipStream_t st)
+{
+        if (p.r.tiles_this_rank <= 0)
+                return hipSuccess;
+        hipLaunchKernelGGL(p.r.sc.wide_leaves ? k_trace_prim_mixed<true> : k_trace_prim_mixed<false>,
+                           dim3((unsigned)p.r.tiles_this_rank), dim3(kBlock), 0, st, p, pd);
+        if (p.build_steps)
+                hipLaunchKernelGGL(k_cone_steps, dim3(1), dim3(64), 0, st, p);
+        return hipGetLastError();
+}
+
+hipError_t launch_cones_probes(const TraceParams &p, const float *sgs, int fused, hipStream_t st)
+{
+        if (p.r.tiles_this_rank <= 0)
+                return hipSuccess;
+        const int64_t nslots = (int64_t)p.r.tiles_this_rank * 256;
+        TraceParamsProbes pp;
+        static_cast<TraceParams &>(pp) = p;
+        pp.sgs = sgs;
+        pp.fused = fused;
+        hipLaunchKernelGGL(k_cones_film<true>, dim3((unsigned)(nslots / 64)), dim3(64), 0, st, pp);
+        return hipGetLastError();
+}
+
+// ---- probe hits shaded on the device (vrt_probe_eval_device,
+// vrt_probe_shade_hits_device, vrt_expf_selftest) ----
+// out[k] = expf_model(the float with bits first + k * stride) for k < n, one
+// pattern per lane in grid-stride
+__global__ __launch_bounds__(256) void k_selftest_expf(uint32_t first, uint32_t stride, int64_t n, int fused,
+                                                       float *__restrict__ out)
+{
+        for (int64_t k = (int64_t)blockIdx.x * 256 + threadIdx.x; k < n; k += (int64_t)gridDim.x * 256)
+                out[k] = expf_model(__uint_as_float(first + (uint32_t)k * stride), fused != 0);
+}
+
+hipError_t launch_selftest_expf(uint32_t first, uint32_t stride, int64_t n, int fused, float *out, hipStream_t st)
+{
+        if (n <= 0)
+                return hipSuccess;
+        const unsigned grid = (unsigned)std::min<int64_t>((n + 255) / 256, 1 << 16);
+        hipLaunchKernelGGL(k_selftest_expf, dim3(grid), dim3(256), 0, st, first, stride, n, fused, out);
+        return hipGetLastError();
+}
+
+// y[i] = expf_model(x[i]) (vrt_expf_model_device: the kernels' model on given inputs)
+__global__ __launch_bounds__(256) void k_expf_model(const float *__restrict__ x, int64_t n, int fused,
+                                                    float *__restrict__ y)
+{
+        for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < n; i += (int64_t)gridDim.x * 256)
+                y[i] = expf_model(x[i], fused != 0);
+}
+
+hipError_t launch_expf_model(const float *x, int64_t n, int fused, float *y, hipStream_t st)
+{
+        if (n <= 0)
+                return hipSuccess;
+        const unsigned grid = (unsigned)std::min<int64_t>((n + 255) / 256, 1 << 16);
+        hipLaunchKernelGGL(k_expf_model, dim3(grid), dim3(256), 0, st, x, n, fused, y);
+        return hipGetLastError();
+}
+
+// vrt_probe_eval on the device: one lane per (probe, direction), the
+// direction used as it is
+__global__ __launch_bounds__(256) void k_probe_eval(const float *__restrict__ sgs, int64_t n,
+                                                    const float *__restrict__ dirs, int64_t m, int fused,
+                                                    float *__restrict__ rgb)
+{
+        const int64_t tot = n * m;
+        for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < tot; i += (int64_t)gridDim.x * 256) {
+                const int64_t pi = i / m, k = i - pi * m;
+                const f3 c = probe_albedo(sgs + pi * (7 * kProbeSGs), mk3(dirs[3 * k], dirs[3 * k + 1], dirs[3 * k + 2]),
+                                          fused != 0);
+                rgb[3 * i + 0] = c.x;
+                rgb[3 * i + 1] = c.y;
+                rgb[3 * i + 2] = c.z;
+        }
+}
+
+hipError_t launch_probe_eval(const float *sgs, int64_t n, const float *dirs, int64_t m, int fused, float *rgb,
+                             hipStream_t st)
+{
+        if (n <= 0 || m <= 0)
+                return hipSuccess;
+        const unsigned grid = (unsigned)std::min<int64_t>((n * m + 255) / 256, 1 << 20);
+        hipLaunchKernelGGL(k_probe_eval, dim3(grid), dim3(256), 0, st, sgs, n, dirs, m, fused, rgb);
+        return hipGetLastError();
+}
+
+// vrt_probe_shade_hits on the device: the elements of a batch that ended on a
+// probe (hit == 1, ntri <= tri < ntri + nprobe) get eval(normalize(hit_p -
+// o_)) over the scene's SGs; every other element is left as it is
+__global__ __launch_bounds__(256) void k_probe_shade_hits(const uint32_t *__restrict__ hits, int64_t n,
+                                                          const float4 *__restrict__ probes, int32_t ntri,
+                                                          int32_t nprobe, const float *__restrict__ sgs, int fused,
+                                                          float *__restrict__ rgb, float *__restrict__ albedo)
+{
+        for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < n; i += (int64_t)gridDim.x * 256) {
+                const uint32_t *h = hits + 9 * i;
+                const int64_t k = (int64_t)(int32_t)h[1] - ntri;
+                if (h[0] != 1u || k < 0 || k >= nprobe)
+                        continue;
+                const float4 pb = probes[k];
+                const f3 hp = mk3(__uint_as_float(h[3]), __uint_as_float(h[4]), __uint_as_float(h[5]));
+                const f3 c = probe_albedo(sgs + k * (7 * kProbeSGs), normalize(hp - mk3(pb.x, pb.y, pb.z)), fused != 0);
+                if (rgb) {
+                        rgb[3 * i + 0] = c.x;
+                        rgb[3 * i + 1] = c.y;
+                        rgb[3 * i + 2] = c.z;
+                }
+                if (albedo) {
+                        albedo[3 * i + 0] = c.x;
+                        albedo[3 * i + 1] = c.y;
+                        albedo[3 * i + 2] = c.z;
+                }
+        }
+}
+
+hipError_t launch_probe_shade_hits(const void *hits, int64_t n, const ProbeDev &pd, int32_t nprobe, const float *sgs,
+                                   int fused, float *rgb, float *albedo, hipStream_t st)
+{
+        if (n <= 0)
+                return hipSuccess;
+        const unsigned grid = (unsigned)std::min<int64_t>((n + 255) / 256, 1 << 20);
+        hipLaunchKernelGGL(k_probe_shade_hits, dim3(grid), dim3(256), 0, st, static_cast<const uint32_t *>(hits), n,
+                           pd.probes, pd.ntri, nprobe, sgs, fused, rgb, albedo);
         return hipGetLastError();
 }
 
