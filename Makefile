@@ -76,7 +76,7 @@ $(PKG)/libvrt.so: $(OBJS)
 oracle:
 	$(MAKE) -C oracle
 
-# A/B variant of the kernels:  make variant NAME=v0 DEFS="-DVRT_EXPAND_V=0"
+# A/B variant of the kernels:  make variant NAME=v0 DEFS="-DVRT_CHAIN_ORDER=0"
 variant: $(HOSTOBJS) $(BLD)/vrt_build.o | $(BLD)
 	mkdir -p build/ab
 	$(HIPCC) $(HIPFLAGS) $(KFLAGS) $(DEFS) -c $(SRC)/vrt_kernels.hip -o build/ab/k_$(NAME).o

@@ -159,7 +159,8 @@ def main():
         t = np.array(times[p])
         out[os.path.basename(p)] = {"median_ms": round(float(np.median(t)), 4), "min_ms": round(float(t.min()), 4),
                                     "speedup": round(float(base / np.median(t)), 3),
-                                    "mrays": round(a.width * a.height * 4 / np.median(t) / 1e3, 1)}
+                                    "mrays": round(a.width * a.height * 4 / np.median(t) / 1e3, 1),
+                                    "rounds_ms": [round(float(v), 4) for v in t]}
         if a.per_pose and pose_times[p]:
             out[os.path.basename(p)]["per_pose_ms"] = [round(float(v), 4)
                                                        for v in np.median(np.array(pose_times[p]), axis=0)]
@@ -293,6 +294,8 @@ def trace_ab(a, libs, scenes, film):
     lbase = np.median(ltimes[a.libs[0]])
     print(json.dumps({os.path.basename(p): {"median_ms": round(float(np.median(t)), 4),
                                             "min_ms": round(float(np.min(t)), 4),
+                                            "rounds_ms": [round(float(v), 4) for v in t],
+                                            "frame_rounds_ms": [round(float(v), 4) for v in ftimes[p]],
                                             "speedup": round(float(base / np.median(t)), 3),
                                             "lightmap_wall_ms": round(float(np.median(ltimes[p])), 4),
                                             "lightmap_speedup": round(float(lbase / np.median(ltimes[p])), 3),

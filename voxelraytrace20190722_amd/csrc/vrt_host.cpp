@@ -453,13 +453,11 @@ struct vrt_scene {
         HostOut ho;
         // vrt_ray_march_batch: device ray / hit buffers and pinned staging
         // kept between calls (grown as needed)
-        void *d_rays = nullptr, *d_hits = nullptr, *h_rays = nullptr, *h_hits = nullptr;
-        int64_t rays_cap = 0;
+        Staging rays, hits;
         // vrt_trace_batch / vrt_cone_trace_batch (host arrays): one chunk's
         // inputs and outputs on the device and their pinned staging, kept
         // between calls (grown as needed, never beyond one chunk)
-        void *d_tb = nullptr, *h_tb = nullptr;
-        size_t tb_bytes = 0;
+        Staging tb;
         // every entry point that launches work on the scene holds mu (one
         // host thread at a time; device work on several streams is ordered
         // by the events above)
@@ -1382,18 +1380,8 @@ extern "C" void vrt_scene_destroy(vrt_scene *s)
                         (void)hipStreamDestroy(ho.st2);
                 if (ho.cp)
                         (void)hipStreamDestroy(ho.cp);
-                if (s->d_rays)
-                        (void)hipFree(s->d_rays);
-                if (s->d_hits)
-                        (void)hipFree(s->d_hits);
-                if (s->h_rays)
-                        (void)hipHostFree(s->h_rays);
-                if (s->h_hits)
-                        (void)hipHostFree(s->h_hits);
-                if (s->d_tb)
-                        (void)hipFree(s->d_tb);
-                if (s->h_tb)
-                        (void)hipHostFree(s->h_tb);
+                for (Staging *g : { &s->rays, &s->hits, &s->tb })
+                        g->release();
                 if (s->stream)
                         (void)hipStreamDestroy(s->stream);
         }
@@ -2320,7 +2308,7 @@ extern "C" int vrt_scene_scratch_bytes(vrt_scene *s, int64_t *bytes, int64_t *sp
         for (int k = 0; k < 2; ++k)
                 if (s->d_spill[k])
                         sp += (int64_t)spill_set_bytes(s->spill_cap[k], s->spill_px[k]);
-        int64_t t = sp + (int64_t)s->light_bytes + (int64_t)s->ho.bytes + (int64_t)s->tb_bytes;
+        int64_t t = sp + (int64_t)s->light_bytes + (int64_t)s->ho.bytes + (int64_t)s->tb.cap;
         for (const TraceSet &ts : s->ts) {
                 if (ts.lm)
                         t += (int64_t)lm_set_bytes(s->nodes.size());
@@ -2815,244 +2803,66 @@ static void fill_trace_light(vrt_scene *s, int set, float min_voxel, TraceParams
         split_bounds(tp->maxdist, tp->split_up, tp->split_bound);
 }
 
-extern "C" int vrt_render_trace_device(vrt_scene *s, const vrt_camera *cam, const vrt_film *film,
-                                       float min_voxel, int rank, int nranks, int image_layout,
-                                       float *d_out, void *stream)
+// ---- batched gi::ray_march (vrt_ray_march_batch[_ex][_device]) ------------
+// flags: 0 or VRT_MARCH_EVEN_INVISIBLE, gi::ray_march's last parameter; it
+// changes the march only on a probe scene, which then takes the mixed march
+// (pd set).  An unknown flag is reported before anything else.
+static int march_args_ok(vrt_scene *s, const void *rays, int64_t n, const void *hits, int flags, const ProbeDev **pd)
 {
+        if (flags & ~VRT_MARCH_EVEN_INVISIBLE)
+                return fail(VRT_E_INVALID, "unknown flags %#x", flags);
         if (s && need_device(s))
                 return VRT_E_NODEVICE;
-        if (!s || !cam || !d_out)
-                return fail(VRT_E_INVALID, "null argument");
-        if (int rc = no_probe_scene(s, "vrt_render_trace_device"))
-                return rc;
-        if (int rc = film_ok(film))
-                return rc;
-        if (nranks < 1 || rank < 0 || rank >= nranks)
-                return fail(VRT_E_INVALID, "rank %d of %d", rank, nranks);
-        if (image_layout && nranks != 1)
-                return fail(VRT_E_INVALID, "image_layout requires nranks == 1");
-        if (int rc = trace_ok(s, min_voxel))
-                return rc;
-        std::lock_guard<std::mutex> lk(s->mu);
-        if (s->lm_cur < 0)
-                return fail(VRT_E_INVALID, "no light map: call vrt_lightmap_build first");
-        HIPCHK(hipSetDevice(s->device));
-        const int set = s->lm_cur;  // the latest light map
-        TraceParams tp0, tp;
-        fill_trace_params(s, set, cam, film, min_voxel, rank, nranks, &tp0);
-        tp0.r.image_layout = image_layout;
-        tp0.r.out = d_out;
-        hipStream_t st = static_cast<hipStream_t>(stream);
-        if (int rc = trace_scratch(s, set, tp0, &tp))
-                return rc;
-        if (int rc = ts_acquire(s, set, st))
-                return rc;
-        HIPCHK(hipEventRecord(s->ev0, st));
-        HIPCHK(launch_trace(tp, st));
-        steps_commit(s, set, tp);
-        HIPCHK(hipEventRecord(s->ev1, st));
-        if (int rc = ts_release(s, set, st))
-                return rc;
-        s->timed = true;
-        return VRT_OK;
-}
-
-// The reference main() frame in one call (VRT/main.cc:75-126): light pass
-// + filter on the scene's stream and, beside them on `stream`, the view's
-// primary march (k_trace_prim reads no light map); the cones + film pass
-// waits for the filter.  Same values as vrt_lightmap_build followed by
-// vrt_render_trace_device.  Returns once the filter is enqueued (the light
-// pass's hit count needs one host sync); the image is ordered on `stream`.
-extern "C" int vrt_trace_frame_device(vrt_scene *s, const vrt_camera *light_cam, const vrt_film *light_film,
-                                      const vrt_camera *cam, const vrt_film *film, float min_voxel, int rank,
-                                      int nranks, int image_layout, float *d_out, void *stream, int64_t *hits)
-{
-        if (s && need_device(s))
-                return VRT_E_NODEVICE;
-        if (!s || !light_cam || !cam || !d_out)
-                return fail(VRT_E_INVALID, "null argument");
-        if (int rc = no_probe_scene(s, "vrt_trace_frame_device"))
-                return rc;
-        if (int rc = film_ok(light_film))
-                return rc;
-        if (int rc = film_ok(film))
-                return rc;
-        if (nranks < 1 || rank < 0 || rank >= nranks)
-                return fail(VRT_E_INVALID, "rank %d of %d", rank, nranks);
-        if (image_layout && nranks != 1)
-                return fail(VRT_E_INVALID, "image_layout requires nranks == 1");
-        if (int rc = trace_ok(s, min_voxel))
-                return rc;
-        std::lock_guard<std::mutex> lk(s->mu);
-        HIPCHK(hipSetDevice(s->device));
-        hipStream_t st = static_cast<hipStream_t>(stream);
-        if (!s->lm_ev)
-                HIPCHK(hipEventCreateWithFlags(&s->lm_ev, hipEventDisableTiming));
-        // alternate sets: this frame's light pass waits only for the frame
-        // before last (the set's previous user), so it runs beside the
-        // previous frame's cone-traced shading
-        const int set = s->ts_next;
-        s->ts_next ^= 1;
-        if (int rc = ensure_lm(s, set))  // the trace parameters point into it
-                return rc;
-        TraceParams tp0, tp;
-        fill_trace_params(s, set, cam, film, min_voxel, rank, nranks, &tp0);
-        tp0.r.image_layout = image_layout;
-        tp0.r.out = d_out;
-        if (int rc = trace_scratch(s, set, tp0, &tp))
-                return rc;
-        unsigned int nhit = 0;
-        auto overlap = [&]() -> int {
-                // the view's primary march beside the light pass (its records
-                // wait only for the previous frame's users of the scratch)
-                if (int rc = ts_acquire(s, set, st))
-                        return rc;
-                HIPCHK(launch_trace_prim(tp, st));
-                steps_commit(s, set, tp);
-                return VRT_OK;
-        };
-        if (int rc = lightmap_enqueue(s, set, light_cam, light_film, &nhit, overlap, s->lm_ev)) {
-                // whatever was enqueued on either stream (the light pass on
-                // the scene's, the primary march on the caller's) finishes
-                // before the set's next user starts
-                if (hipEventRecord(s->lm_ev, s->stream) == hipSuccess)
-                        (void)hipStreamWaitEvent(st, s->lm_ev, 0);
-                (void)ts_release(s, set, st);
-                return rc;
-        }
-        HIPCHK(hipStreamWaitEvent(st, s->lm_ev, 0));
-        if (hipError_t e = launch_cones(tp, st)) {
-                (void)ts_release(s, set, st);
-                return fail(VRT_E_DEVICE, "cone pass launch failed: %s", hipGetErrorString(e));
-        }
-        if (int rc = ts_release(s, set, st))
-                return rc;
-        if (hits)
-                *hits = (int64_t)nhit;
-        return VRT_OK;
-}
-
-extern "C" int vrt_render_trace(vrt_scene *s, const vrt_camera *cam, const vrt_film *film, float min_voxel,
-                                float *rgb, int32_t *s_hit, float *s_rgb)
-{
-        if (s && need_device(s))
-                return VRT_E_NODEVICE;
-        if (!s || !cam || !rgb)
-                return fail(VRT_E_INVALID, "null argument");
-        if (int rc = no_probe_scene(s, "vrt_render_trace"))
-                return rc;
-        if (int rc = film_ok(film))
-                return rc;
-        if (int rc = trace_ok(s, min_voxel))
-                return rc;
-        std::lock_guard<std::mutex> lk(s->mu);
-        if (s->lm_cur < 0)
-                return fail(VRT_E_INVALID, "no light map: call vrt_lightmap_build first");
-        HIPCHK(hipSetDevice(s->device));
-        const int set = s->lm_cur;
-        const size_t npix = (size_t)film->nx * film->ny, ns = npix * 4;
-        DevBuf img, dh, dr;
-        HIPCHK(hipMalloc(&img.p, npix * 12));
-        HIPCHK(hipMemsetAsync(img.p, 0, npix * 12, s->stream));
-        TraceParams tp0, tp;
-        fill_trace_params(s, set, cam, film, min_voxel, 0, 1, &tp0);
-        tp0.r.image_layout = 1;
-        tp0.r.out = static_cast<float *>(img.p);
-        if (int rc = trace_scratch(s, set, tp0, &tp))
-                return rc;
-        if (s_hit) {
-                HIPCHK(hipMalloc(&dh.p, ns * 4));
-                HIPCHK(hipMemsetAsync(dh.p, 0, ns * 4, s->stream));
-                tp.r.so.hit = static_cast<int32_t *>(dh.p);
-        }
-        if (s_rgb) {
-                HIPCHK(hipMalloc(&dr.p, ns * 12));
-                HIPCHK(hipMemsetAsync(dr.p, 0, ns * 12, s->stream));
-                tp.r.so.rgb = static_cast<float *>(dr.p);
-        }
-        if (int rc = ts_acquire(s, set, s->stream))
-                return rc;
-        HIPCHK(hipEventRecord(s->ev0, s->stream));
-        HIPCHK(launch_trace(tp, s->stream));
-        steps_commit(s, set, tp);
-        HIPCHK(hipEventRecord(s->ev1, s->stream));
-        if (int rc = ts_release(s, set, s->stream))
-                return rc;
-        s->timed = true;
-        HIPCHK(hipStreamSynchronize(s->stream));
-        HIPCHK(hipMemcpy(rgb, img.p, npix * 12, hipMemcpyDeviceToHost));
-        if (s_hit)
-                HIPCHK(hipMemcpy(s_hit, dh.p, ns * 4, hipMemcpyDeviceToHost));
-        if (s_rgb)
-                HIPCHK(hipMemcpy(s_rgb, dr.p, ns * 12, hipMemcpyDeviceToHost));
-        return VRT_OK;
-}
-
-extern "C" int vrt_ray_march_batch_device(vrt_scene *s, const vrt_ray *d_rays,
-                                          int64_t n, vrt_hit *d_hits,
-                                          void *stream)
-{
-        if (s && need_device(s))
-                return VRT_E_NODEVICE;
-        if (!s || (n > 0 && (!d_rays || !d_hits)) || n < 0)
-                return fail(VRT_E_INVALID, "bad argument");
-        HIPCHK(hipSetDevice(s->device));
-        HIPCHK(launch_ray_march(s->dev, d_rays, n, d_hits, static_cast<hipStream_t>(stream), s->ord_wmin));
-        return VRT_OK;
-}
-
-// even_invisible: gi::ray_march's last parameter; it changes the march only
-// on a probe scene (vrt_ray_march_batch_ex)
-static int ray_march_host(vrt_scene *s, const vrt_ray *rays, int64_t n, vrt_hit *hits, bool even_invisible);
-
-extern "C" int vrt_ray_march_batch(vrt_scene *s, const vrt_ray *rays,
-                                   int64_t n, vrt_hit *hits)
-{
-        return ray_march_host(s, rays, n, hits, false);
-}
-
-static int ray_march_host(vrt_scene *s, const vrt_ray *rays, int64_t n, vrt_hit *hits, bool even_invisible)
-{
-        if (s && need_device(s))
-                return VRT_E_NODEVICE;
-        static_assert(sizeof(vrt_ray) == 32, "vrt_ray layout");
-        static_assert(sizeof(vrt_hit) == 36, "vrt_hit layout");
         if (!s || n < 0 || (n > 0 && (!rays || !hits)))
                 return fail(VRT_E_INVALID, "bad argument");
+        *pd = (flags & VRT_MARCH_EVEN_INVISIBLE) && !s->probes.empty() ? &s->pdev : nullptr;
+        return VRT_OK;
+}
+
+extern "C" int vrt_ray_march_batch_ex_device(vrt_scene *s, const vrt_ray *d_rays, int64_t n, int flags,
+                                             vrt_hit *d_hits, void *stream)
+{
+        const ProbeDev *pd;
+        if (int rc = march_args_ok(s, d_rays, n, d_hits, flags, &pd))
+                return rc;
+        HIPCHK(hipSetDevice(s->device));
+        HIPCHK(launch_ray_march(s->dev, d_rays, n, d_hits, static_cast<hipStream_t>(stream), s->ord_wmin, pd));
+        return VRT_OK;
+}
+
+extern "C" int vrt_ray_march_batch_device(vrt_scene *s, const vrt_ray *d_rays, int64_t n, vrt_hit *d_hits,
+                                          void *stream)
+{
+        return vrt_ray_march_batch_ex_device(s, d_rays, n, 0, d_hits, stream);
+}
+
+// host arrays: through the scene's device buffers and pinned staging
+extern "C" int vrt_ray_march_batch_ex(vrt_scene *s, const vrt_ray *rays, int64_t n, int flags, vrt_hit *hits)
+{
+        static_assert(sizeof(vrt_ray) == 32, "vrt_ray layout");
+        static_assert(sizeof(vrt_hit) == 36, "vrt_hit layout");
+        const ProbeDev *pd;
+        if (int rc = march_args_ok(s, rays, n, hits, flags, &pd))
+                return rc;
         if (n == 0)
                 return VRT_OK;
         std::lock_guard<std::mutex> lk(s->mu);
         HIPCHK(hipSetDevice(s->device));
-        // device buffers and pinned staging kept in the scene (grown as needed)
-        if (n > s->rays_cap) {
-                HIPCHK(hipStreamSynchronize(s->stream));
-                for (void **p : { &s->d_rays, &s->d_hits })
-                        if (*p) {
-                                (void)hipFree(*p);
-                                *p = nullptr;
-                        }
-                for (void **p : { &s->h_rays, &s->h_hits })
-                        if (*p) {
-                                (void)hipHostFree(*p);
-                                *p = nullptr;
-                        }
-                s->rays_cap = 0;
-                HIPCHK(hipMalloc(&s->d_rays, (size_t)n * sizeof(vrt_ray)));
-                HIPCHK(hipMalloc(&s->d_hits, (size_t)n * sizeof(vrt_hit)));
-                HIPCHK(hipHostMalloc(&s->h_rays, (size_t)n * sizeof(vrt_ray), hipHostMallocDefault));
-                HIPCHK(hipHostMalloc(&s->h_hits, (size_t)n * sizeof(vrt_hit), hipHostMallocDefault));
-                s->rays_cap = n;
-        }
-        par_memcpy(s->h_rays, rays, (size_t)n * sizeof(vrt_ray));
-        HIPCHK(hipMemcpyAsync(s->d_rays, s->h_rays, (size_t)n * sizeof(vrt_ray), hipMemcpyHostToDevice, s->stream));
-        if (even_invisible && !s->probes.empty())
-                HIPCHK(launch_ray_march_mixed(s->dev, s->pdev, s->d_rays, n, s->d_hits, s->stream));
-        else
-                HIPCHK(launch_ray_march(s->dev, s->d_rays, n, s->d_hits, s->stream, s->ord_wmin));
-        HIPCHK(hipMemcpyAsync(s->h_hits, s->d_hits, (size_t)n * sizeof(vrt_hit), hipMemcpyDeviceToHost, s->stream));
+        const size_t rbytes = (size_t)n * sizeof(vrt_ray), hbytes = (size_t)n * sizeof(vrt_hit);
+        HIPCHK(s->rays.grow(rbytes, s->stream));
+        HIPCHK(s->hits.grow(hbytes, s->stream));
+        par_memcpy(s->rays.h, rays, rbytes);
+        HIPCHK(hipMemcpyAsync(s->rays.d, s->rays.h, rbytes, hipMemcpyHostToDevice, s->stream));
+        HIPCHK(launch_ray_march(s->dev, s->rays.d, n, s->hits.d, s->stream, s->ord_wmin, pd));
+        HIPCHK(hipMemcpyAsync(s->hits.h, s->hits.d, hbytes, hipMemcpyDeviceToHost, s->stream));
         HIPCHK(hipStreamSynchronize(s->stream));
-        par_memcpy(hits, s->h_hits, (size_t)n * sizeof(vrt_hit));
+        par_memcpy(hits, s->hits.h, hbytes);
         return VRT_OK;
+}
+
+extern "C" int vrt_ray_march_batch(vrt_scene *s, const vrt_ray *rays, int64_t n, vrt_hit *hits)
+{
+        return vrt_ray_march_batch_ex(s, rays, n, 0, hits);
 }
 
 // ---- batched trace() / cone_trace (vrt_trace_batch, vrt_cone_trace_batch) --
@@ -3164,28 +2974,9 @@ extern "C" int vrt_cone_trace_batch_device(vrt_scene *s, const vrt_isect *d_isec
         return batch_enqueue(s, io, min_voxel, static_cast<hipStream_t>(stream));
 }
 
-// the host-array calls' staging: `bytes` on the device and pinned (caller
-// holds s->mu; used on the scene's stream only)
-static int batch_staging(vrt_scene *s, size_t bytes)
-{
-        if (bytes <= s->tb_bytes)
-                return VRT_OK;
-        HIPCHK(hipStreamSynchronize(s->stream));
-        if (s->d_tb)
-                (void)hipFree(s->d_tb);
-        if (s->h_tb)
-                (void)hipHostFree(s->h_tb);
-        s->d_tb = s->h_tb = nullptr;
-        s->tb_bytes = 0;
-        HIPCHK(hipMalloc(&s->d_tb, bytes));
-        HIPCHK(hipHostMalloc(&s->h_tb, bytes, hipHostMallocDefault));
-        s->tb_bytes = bytes;
-        return VRT_OK;
-}
-
-// Host arrays: chunk by chunk through the staging (in: `in_sz` bytes per
-// element at offset 0; out: the requested arrays behind it, out_sz[k] bytes
-// per element each), one host sync per chunk.
+// Host arrays: chunk by chunk through the staging s->tb (in: `in_sz` bytes
+// per element at offset 0; out: the requested arrays behind it, out_sz[k]
+// bytes per element each), one host sync per chunk (caller holds s->mu).
 static void probe_shade(const vrt_scene *s, const vrt_hit *hits, int64_t n, float *rgb, float *albedo);
 static int fetch_probe_sgs(vrt_scene *s);
 
@@ -3204,9 +2995,8 @@ static int batch_host(vrt_scene *s, const void *in, size_t in_sz, bool rays, int
         size_t per = in_sz;
         for (int k = 0; k < 5; ++k)
                 per += want[k] ? out_sz[k] : 0;
-        if (int rc = batch_staging(s, (size_t)m * per))
-                return rc;
-        char *d = static_cast<char *>(s->d_tb), *h = static_cast<char *>(s->h_tb);
+        HIPCHK(s->tb.grow((size_t)m * per, s->stream));
+        char *d = static_cast<char *>(s->tb.d), *h = static_cast<char *>(s->tb.h);
         for (int64_t b = 0; b < n; b += m) {
                 const int64_t c = std::min(m, n - b);
                 par_memcpy(h, static_cast<const char *>(in) + (size_t)b * in_sz, (size_t)c * in_sz);
@@ -3490,9 +3280,8 @@ extern "C" int vrt_probe_gather(vrt_scene *s, const vrt_probe *probes, int64_t n
         const int64_t m = std::min(n, probe_chunk(np));
         const size_t sg_sz = (size_t)kProbeSGs * sizeof(vrt_sg), tm_sz = terms ? (size_t)kProbeSGs * np * 12 : 0;
         const size_t o_sg = (size_t)m * sizeof(vrt_probe), o_tm = o_sg + (size_t)m * sg_sz;
-        if (int rc = batch_staging(s, o_tm + (size_t)m * tm_sz))
-                return rc;
-        char *d = static_cast<char *>(s->d_tb), *h = static_cast<char *>(s->h_tb);
+        HIPCHK(s->tb.grow(o_tm + (size_t)m * tm_sz, s->stream));
+        char *d = static_cast<char *>(s->tb.d), *h = static_cast<char *>(s->tb.h);
         for (int64_t b = 0; b < n; b += m) {
                 const int64_t c = std::min(m, n - b);
                 std::memcpy(h, probes + b, (size_t)c * sizeof(vrt_probe));
@@ -3957,111 +3746,137 @@ extern "C" int vrt_probe_shade_hits_device(vrt_scene *s, const vrt_hit *d_hits, 
         return ts_release(s, set, st);
 }
 
-// The arguments the three frame calls share with the old ones.
-static int probe_frame_args_ok(const vrt_film *film, int rank, int nranks, int image_layout)
+// ---- the trace() frames ----------------------------------------------------
+// vrt_render_trace[_device] and vrt_trace_frame_device and, beside each, the
+// _probes name that also serves a scene with light probes: one implementation
+// per pair.  FramePath: what the call is (`what`, for its messages), whether
+// it may take the probe path (a _probes name) and, from frame_args_ok,
+// whether it does (a probe scene: the mixed primary march, probe hits shaded
+// over the device SGs with the detected expf flavour `fused`).  On a triangle
+// scene a _probes name is the old one.
+struct FramePath {
+        const char *what;
+        bool may_probe;
+        bool probe = false;
+        int fused = 0;
+};
+
+// The frame calls' arguments, in one order for all six.  ptrs: the call's
+// pointer arguments are all set; light_film: the frame calls' (has_light).
+static int frame_args_ok(vrt_scene *s, FramePath *fp, bool ptrs, bool has_light, const vrt_film *light_film,
+                         const vrt_film *film, int rank, int nranks, int image_layout, float min_voxel)
 {
+        if (s && need_device(s))
+                return VRT_E_NODEVICE;
+        if (!s || !ptrs)
+                return fail(VRT_E_INVALID, "null argument");
+        if (!fp->may_probe)
+                if (int rc = no_probe_scene(s, fp->what))
+                        return rc;
+        if (has_light)
+                if (int rc = film_ok(light_film))
+                        return rc;
         if (int rc = film_ok(film))
                 return rc;
         if (nranks < 1 || rank < 0 || rank >= nranks)
                 return fail(VRT_E_INVALID, "rank %d of %d", rank, nranks);
         if (image_layout && nranks != 1)
                 return fail(VRT_E_INVALID, "image_layout requires nranks == 1");
+        if (int rc = trace_ok(s, min_voxel))
+                return rc;
+        fp->probe = !s->probes.empty();
+        if (fp->probe)
+                return device_expf(fp->what, &fp->fused);
         return VRT_OK;
 }
 
-extern "C" int vrt_render_trace_probes_device(vrt_scene *s, const vrt_camera *cam, const vrt_film *film,
-                                              float min_voxel, int rank, int nranks, int image_layout, float *d_out,
-                                              void *stream)
+static hipError_t frame_prim(vrt_scene *s, int set, const TraceParams &tp, const FramePath &fp, hipStream_t st)
 {
-        if (s && s->probes.empty())
-                return vrt_render_trace_device(s, cam, film, min_voxel, rank, nranks, image_layout, d_out, stream);
-        if (s && need_device(s))
-                return VRT_E_NODEVICE;
-        if (!s || !cam || !d_out)
-                return fail(VRT_E_INVALID, "null argument");
-        if (int rc = probe_frame_args_ok(film, rank, nranks, image_layout))
-                return rc;
-        if (int rc = trace_ok(s, min_voxel))
-                return rc;
-        int fused;
-        if (int rc = device_expf("vrt_render_trace_probes_device", &fused))
-                return rc;
-        std::lock_guard<std::mutex> lk(s->mu);
-        if (s->lm_cur < 0)
-                return fail(VRT_E_INVALID, "no light map: call vrt_lightmap_build first");
-        HIPCHK(hipSetDevice(s->device));
-        const int set = s->lm_cur;
+        const hipError_t e = launch_trace_prim(tp, st, fp.probe ? &s->pdev : nullptr);
+        if (e == hipSuccess)
+                steps_commit(s, set, tp);
+        return e;
+}
+
+static hipError_t frame_cones(vrt_scene *s, const TraceParams &tp, const FramePath &fp, hipStream_t st)
+{
+        return launch_cones(tp, st, fp.probe ? s->d_sgs : nullptr, fp.fused);
+}
+
+// A view over the latest light map on stream st, between the scene's timing
+// events (caller holds s->mu, the device is set, a light map exists): the
+// set is taken, the primary march and the cones + film pass are enqueued, and
+// the set is released -- after a failure too, as batch_enqueue does.  d_hit /
+// d_rgb: the per-sample outputs or null.
+static int view_enqueue(vrt_scene *s, const FramePath &fp, const vrt_camera *cam, const vrt_film *film,
+                        float min_voxel, int rank, int nranks, int image_layout, float *d_out, int32_t *d_hit,
+                        float *d_rgb, hipStream_t st)
+{
+        const int set = s->lm_cur;  // the latest light map
         TraceParams tp0, tp;
         fill_trace_params(s, set, cam, film, min_voxel, rank, nranks, &tp0);
         tp0.r.image_layout = image_layout;
         tp0.r.out = d_out;
-        hipStream_t st = static_cast<hipStream_t>(stream);
+        tp0.r.so.hit = d_hit;
+        tp0.r.so.rgb = d_rgb;
         if (int rc = trace_scratch(s, set, tp0, &tp))
                 return rc;
         if (int rc = ts_acquire(s, set, st))
                 return rc;
-        HIPCHK(hipEventRecord(s->ev0, st));
-        HIPCHK(launch_trace_prim_mixed(tp, s->pdev, st));
-        steps_commit(s, set, tp);
-        HIPCHK(launch_cones_probes(tp, s->d_sgs, fused, st));
-        HIPCHK(hipEventRecord(s->ev1, st));
+        hipError_t e = hipEventRecord(s->ev0, st);
+        if (e == hipSuccess)
+                e = frame_prim(s, set, tp, fp, st);
+        if (e == hipSuccess)
+                e = frame_cones(s, tp, fp, st);
+        if (e == hipSuccess)
+                e = hipEventRecord(s->ev1, st);
+        if (e != hipSuccess) {
+                (void)ts_release(s, set, st);
+                return fail(VRT_E_DEVICE, "trace frame launch failed: %s", hipGetErrorString(e));
+        }
         if (int rc = ts_release(s, set, st))
                 return rc;
         s->timed = true;
         return VRT_OK;
 }
 
-extern "C" int vrt_render_trace_probes(vrt_scene *s, const vrt_camera *cam, const vrt_film *film, float min_voxel,
-                                       float *rgb, int32_t *s_hit, float *s_rgb)
+static int render_trace_device(vrt_scene *s, FramePath fp, const vrt_camera *cam, const vrt_film *film,
+                               float min_voxel, int rank, int nranks, int image_layout, float *d_out, void *stream)
 {
-        if (s && s->probes.empty())
-                return vrt_render_trace(s, cam, film, min_voxel, rgb, s_hit, s_rgb);
-        if (s && need_device(s))
-                return VRT_E_NODEVICE;
-        if (!s || !cam || !rgb)
-                return fail(VRT_E_INVALID, "null argument");
-        if (int rc = film_ok(film))
-                return rc;
-        if (int rc = trace_ok(s, min_voxel))
-                return rc;
-        int fused;
-        if (int rc = device_expf("vrt_render_trace_probes", &fused))
+        if (int rc = frame_args_ok(s, &fp, cam && d_out, false, nullptr, film, rank, nranks, image_layout, min_voxel))
                 return rc;
         std::lock_guard<std::mutex> lk(s->mu);
         if (s->lm_cur < 0)
                 return fail(VRT_E_INVALID, "no light map: call vrt_lightmap_build first");
         HIPCHK(hipSetDevice(s->device));
-        const int set = s->lm_cur;
+        return view_enqueue(s, fp, cam, film, min_voxel, rank, nranks, image_layout, d_out, nullptr, nullptr,
+                            static_cast<hipStream_t>(stream));
+}
+
+static int render_trace_host(vrt_scene *s, FramePath fp, const vrt_camera *cam, const vrt_film *film,
+                             float min_voxel, float *rgb, int32_t *s_hit, float *s_rgb)
+{
+        if (int rc = frame_args_ok(s, &fp, cam && rgb, false, nullptr, film, 0, 1, 1, min_voxel))
+                return rc;
+        std::lock_guard<std::mutex> lk(s->mu);
+        if (s->lm_cur < 0)
+                return fail(VRT_E_INVALID, "no light map: call vrt_lightmap_build first");
+        HIPCHK(hipSetDevice(s->device));
         const size_t npix = (size_t)film->nx * film->ny, ns = npix * 4;
         DevBuf img, dh, dr;
         HIPCHK(hipMalloc(&img.p, npix * 12));
         HIPCHK(hipMemsetAsync(img.p, 0, npix * 12, s->stream));
-        TraceParams tp0, tp;
-        fill_trace_params(s, set, cam, film, min_voxel, 0, 1, &tp0);
-        tp0.r.image_layout = 1;
-        tp0.r.out = static_cast<float *>(img.p);
-        if (int rc = trace_scratch(s, set, tp0, &tp))
-                return rc;
         if (s_hit) {
                 HIPCHK(hipMalloc(&dh.p, ns * 4));
                 HIPCHK(hipMemsetAsync(dh.p, 0, ns * 4, s->stream));
-                tp.r.so.hit = static_cast<int32_t *>(dh.p);
         }
         if (s_rgb) {
                 HIPCHK(hipMalloc(&dr.p, ns * 12));
                 HIPCHK(hipMemsetAsync(dr.p, 0, ns * 12, s->stream));
-                tp.r.so.rgb = static_cast<float *>(dr.p);
         }
-        if (int rc = ts_acquire(s, set, s->stream))
+        if (int rc = view_enqueue(s, fp, cam, film, min_voxel, 0, 1, 1, static_cast<float *>(img.p),
+                                  static_cast<int32_t *>(dh.p), static_cast<float *>(dr.p), s->stream))
                 return rc;
-        HIPCHK(hipEventRecord(s->ev0, s->stream));
-        HIPCHK(launch_trace_prim_mixed(tp, s->pdev, s->stream));
-        steps_commit(s, set, tp);
-        HIPCHK(launch_cones_probes(tp, s->d_sgs, fused, s->stream));
-        HIPCHK(hipEventRecord(s->ev1, s->stream));
-        if (int rc = ts_release(s, set, s->stream))
-                return rc;
-        s->timed = true;
         HIPCHK(hipStreamSynchronize(s->stream));
         HIPCHK(hipMemcpy(rgb, img.p, npix * 12, hipMemcpyDeviceToHost));
         if (s_hit)
@@ -4071,43 +3886,36 @@ extern "C" int vrt_render_trace_probes(vrt_scene *s, const vrt_camera *cam, cons
         return VRT_OK;
 }
 
-// The reference main() frame with its probe block in place
-// (VRT/main.cc:75-126, :104-105 un-commented) in one call: light pass + filter
-// on the scene's stream and, beside them on `stream`, the view's mixed primary
-// march (it reads neither the light map nor the SGs); with a light colour the
+// The reference main() frame in one call (VRT/main.cc:75-126; on a probe
+// scene with its probe block, :104-105, in place): light pass + filter on the
+// scene's stream and, beside them on `stream`, the view's primary march (it
+// reads neither the light map nor the SGs); with a light colour a probe
 // scene's probes then gather behind the filter, on the scene's stream, into
-// the device SGs; the cones + film pass waits for whichever came last.  The
-// gather's records follow the view's in the set's block, and the step table
-// is built by the gather (the primary march does not read it).
-extern "C" int vrt_trace_frame_probes_device(vrt_scene *s, const vrt_camera *light_cam,
-                                             const vrt_film *light_film, const float *light_color,
-                                             const vrt_camera *cam, const vrt_film *film, float min_voxel, int rank,
-                                             int nranks, int image_layout, float *d_out, void *stream, int64_t *hits)
+// the device SGs; the cones + film pass waits for whichever came last.  Same
+// values as vrt_lightmap_build followed by vrt_render_trace_device.  Returns
+// once the filter is enqueued (the light pass's hit count needs one host
+// sync); the image is ordered on `stream`.  The gather's records follow the
+// view's in the set's block, and the gather builds the step table (the
+// primary march does not read it).
+static int trace_frame_device(vrt_scene *s, FramePath fp, const vrt_camera *light_cam, const vrt_film *light_film,
+                              const float *light_color, const vrt_camera *cam, const vrt_film *film,
+                              float min_voxel, int rank, int nranks, int image_layout, float *d_out, void *stream,
+                              int64_t *hits)
 {
-        if (s && s->probes.empty())
-                return vrt_trace_frame_device(s, light_cam, light_film, cam, film, min_voxel, rank, nranks,
-                                              image_layout, d_out, stream, hits);
-        if (s && need_device(s))
-                return VRT_E_NODEVICE;
-        if (!s || !light_cam || !cam || !d_out)
-                return fail(VRT_E_INVALID, "null argument");
-        if (int rc = film_ok(light_film))
-                return rc;
-        if (int rc = probe_frame_args_ok(film, rank, nranks, image_layout))
-                return rc;
-        if (int rc = trace_ok(s, min_voxel))
-                return rc;
-        int fused;
-        if (int rc = device_expf("vrt_trace_frame_probes_device", &fused))
+        if (int rc = frame_args_ok(s, &fp, light_cam && cam && d_out, true, light_film, film, rank, nranks,
+                                   image_layout, min_voxel))
                 return rc;
         std::lock_guard<std::mutex> lk(s->mu);
         HIPCHK(hipSetDevice(s->device));
         hipStream_t st = static_cast<hipStream_t>(stream);
         if (!s->lm_ev)
                 HIPCHK(hipEventCreateWithFlags(&s->lm_ev, hipEventDisableTiming));
-        if (!s->sg_ev)
+        if (fp.probe && !s->sg_ev)
                 HIPCHK(hipEventCreateWithFlags(&s->sg_ev, hipEventDisableTiming));
-        const bool gather = light_color != nullptr;
+        const bool gather = fp.probe && light_color != nullptr;
+        // alternate sets: this frame's light pass waits only for the frame
+        // before last (the set's previous user), so it runs beside the
+        // previous frame's cone-traced shading
         const int set = s->ts_next;
         s->ts_next ^= 1;
         if (int rc = ensure_lm(s, set))  // the trace parameters point into it
@@ -4126,15 +3934,17 @@ extern "C" int vrt_trace_frame_probes_device(vrt_scene *s, const vrt_camera *lig
                 tp.build_steps = 0;  // the gather builds the table, on the scene's stream
         unsigned int nhit = 0;
         auto overlap = [&]() -> int {
+                // the view's primary march beside the light pass (its records
+                // wait only for the previous frame's users of the scratch)
                 if (int rc = ts_acquire(s, set, st))
                         return rc;
-                HIPCHK(launch_trace_prim_mixed(tp, s->pdev, st));
-                steps_commit(s, set, tp);
+                HIPCHK(frame_prim(s, set, tp, fp, st));
                 return VRT_OK;
         };
         auto bail = [&](int rc) {
-                // whatever was enqueued on either stream finishes before the
-                // set's next user starts
+                // whatever was enqueued on either stream (the light pass and
+                // the gather on the scene's, the primary march on the
+                // caller's) finishes before the set's next user starts
                 if (hipEventRecord(s->lm_ev, s->stream) == hipSuccess)
                         (void)hipStreamWaitEvent(st, s->lm_ev, 0);
                 (void)ts_release(s, set, st);
@@ -4142,6 +3952,7 @@ extern "C" int vrt_trace_frame_probes_device(vrt_scene *s, const vrt_camera *lig
         };
         if (int rc = lightmap_enqueue(s, set, light_cam, light_film, &nhit, overlap, s->lm_ev))
                 return bail(rc);
+        hipEvent_t last = s->lm_ev;  // what the cones + film pass waits for
         if (gather) {
                 ProbeIO io{};
                 io.probes = reinterpret_cast<const float *>(s->pdev.probes);
@@ -4155,15 +3966,15 @@ extern "C" int vrt_trace_frame_probes_device(vrt_scene *s, const vrt_camera *lig
                 s->sgs_stale = true;
                 if (int rc = probe_enqueue(s, io, probe_default_points(), min_voxel, s->stream, view_slots))
                         return bail(rc);
-                HIPCHK(hipEventRecord(s->sg_ev, s->stream));
-                HIPCHK(hipStreamWaitEvent(st, s->sg_ev, 0));
-        } else {
-                HIPCHK(hipStreamWaitEvent(st, s->lm_ev, 0));
+                last = s->sg_ev;
+                if (hipError_t e = hipEventRecord(last, s->stream))
+                        return bail(fail(VRT_E_DEVICE, "hipEventRecord failed: %s", hipGetErrorString(e)));
         }
-        if (hipError_t e = launch_cones_probes(tp, s->d_sgs, fused, st)) {
-                (void)ts_release(s, set, st);
-                return fail(VRT_E_DEVICE, "cone pass launch failed: %s", hipGetErrorString(e));
-        }
+        hipError_t e = hipStreamWaitEvent(st, last, 0);
+        if (e == hipSuccess)
+                e = frame_cones(s, tp, fp, st);
+        if (e != hipSuccess)
+                return bail(fail(VRT_E_DEVICE, "cone pass launch failed: %s", hipGetErrorString(e)));
         if (int rc = ts_release(s, set, st))
                 return rc;
         if (hits)
@@ -4171,27 +3982,49 @@ extern "C" int vrt_trace_frame_probes_device(vrt_scene *s, const vrt_camera *lig
         return VRT_OK;
 }
 
-extern "C" int vrt_ray_march_batch_ex_device(vrt_scene *s, const vrt_ray *d_rays, int64_t n, int flags,
-                                             vrt_hit *d_hits, void *stream)
+extern "C" int vrt_render_trace_device(vrt_scene *s, const vrt_camera *cam, const vrt_film *film,
+                                       float min_voxel, int rank, int nranks, int image_layout,
+                                       float *d_out, void *stream)
 {
-        if (flags & ~VRT_MARCH_EVEN_INVISIBLE)
-                return fail(VRT_E_INVALID, "unknown flags %#x", flags);
-        if (!s || !(flags & VRT_MARCH_EVEN_INVISIBLE) || s->probes.empty())
-                return vrt_ray_march_batch_device(s, d_rays, n, d_hits, stream);
-        if (need_device(s))
-                return VRT_E_NODEVICE;
-        if ((n > 0 && (!d_rays || !d_hits)) || n < 0)
-                return fail(VRT_E_INVALID, "bad argument");
-        HIPCHK(hipSetDevice(s->device));
-        HIPCHK(launch_ray_march_mixed(s->dev, s->pdev, d_rays, n, d_hits, static_cast<hipStream_t>(stream)));
-        return VRT_OK;
+        return render_trace_device(s, { "vrt_render_trace_device", false }, cam, film, min_voxel, rank, nranks,
+                                   image_layout, d_out, stream);
 }
 
-extern "C" int vrt_ray_march_batch_ex(vrt_scene *s, const vrt_ray *rays, int64_t n, int flags, vrt_hit *hits)
+extern "C" int vrt_render_trace_probes_device(vrt_scene *s, const vrt_camera *cam, const vrt_film *film,
+                                              float min_voxel, int rank, int nranks, int image_layout, float *d_out,
+                                              void *stream)
 {
-        if (flags & ~VRT_MARCH_EVEN_INVISIBLE)
-                return fail(VRT_E_INVALID, "unknown flags %#x", flags);
-        return ray_march_host(s, rays, n, hits, (flags & VRT_MARCH_EVEN_INVISIBLE) != 0);
+        return render_trace_device(s, { "vrt_render_trace_probes_device", true }, cam, film, min_voxel, rank, nranks,
+                                   image_layout, d_out, stream);
+}
+
+extern "C" int vrt_render_trace(vrt_scene *s, const vrt_camera *cam, const vrt_film *film, float min_voxel,
+                                float *rgb, int32_t *s_hit, float *s_rgb)
+{
+        return render_trace_host(s, { "vrt_render_trace", false }, cam, film, min_voxel, rgb, s_hit, s_rgb);
+}
+
+extern "C" int vrt_render_trace_probes(vrt_scene *s, const vrt_camera *cam, const vrt_film *film, float min_voxel,
+                                       float *rgb, int32_t *s_hit, float *s_rgb)
+{
+        return render_trace_host(s, { "vrt_render_trace_probes", true }, cam, film, min_voxel, rgb, s_hit, s_rgb);
+}
+
+extern "C" int vrt_trace_frame_device(vrt_scene *s, const vrt_camera *light_cam, const vrt_film *light_film,
+                                      const vrt_camera *cam, const vrt_film *film, float min_voxel, int rank,
+                                      int nranks, int image_layout, float *d_out, void *stream, int64_t *hits)
+{
+        return trace_frame_device(s, { "vrt_trace_frame_device", false }, light_cam, light_film, nullptr, cam, film,
+                                  min_voxel, rank, nranks, image_layout, d_out, stream, hits);
+}
+
+extern "C" int vrt_trace_frame_probes_device(vrt_scene *s, const vrt_camera *light_cam,
+                                             const vrt_film *light_film, const float *light_color,
+                                             const vrt_camera *cam, const vrt_film *film, float min_voxel, int rank,
+                                             int nranks, int image_layout, float *d_out, void *stream, int64_t *hits)
+{
+        return trace_frame_device(s, { "vrt_trace_frame_probes_device", true }, light_cam, light_film, light_color,
+                                  cam, film, min_voxel, rank, nranks, image_layout, d_out, stream, hits);
 }
 
 extern "C" int vrt_device_selftest(int device, const double *mt_in,

@@ -563,8 +563,6 @@ struct ProbeDev {
         const float4 *probes;   // {o xyz, r}
         int32_t ntri;           // a probe hit's voxel index is ntri + k
 };
-hipError_t launch_ray_march_mixed(const DevScene &sc, const ProbeDev &pd, const void *d_rays, int64_t n,
-                                  void *d_hits, hipStream_t st);
 // light map of a probe scene: leaves that hold probes but no triangle get
 // coverage 1 (cone_trace_init_filter, VRT/voxel_octree.cc:192-199); after
 // launch_lm_leaves, before the level filter
@@ -600,6 +598,36 @@ int scene_replicate(const vrt_scene *src, const vrt_scene_desc *d, int device, v
 void par_memcpy(void *dst, const void *src, size_t bytes);
 // the process-wide vrt_set_test_flags value
 int test_flags();
+// A grow-only staging pair kept in a scene between calls: cap bytes on the
+// device and as many pinned on the host, used on one stream only.
+struct Staging {
+        void *d = nullptr, *h = nullptr;
+        size_t cap = 0;
+        // room for `bytes`; growing waits for the stream's work on the old pair
+        hipError_t grow(size_t bytes, hipStream_t st)
+        {
+                if (bytes <= cap)
+                        return hipSuccess;
+                if (hipError_t e = hipStreamSynchronize(st))
+                        return e;
+                release();
+                if (hipError_t e = hipMalloc(&d, bytes))
+                        return e;
+                if (hipError_t e = hipHostMalloc(&h, bytes, hipHostMallocDefault))
+                        return e;
+                cap = bytes;
+                return hipSuccess;
+        }
+        void release()
+        {
+                if (d)
+                        (void)hipFree(d);
+                if (h)
+                        (void)hipHostFree(h);
+                d = h = nullptr;
+                cap = 0;
+        }
+};
 
 // Kernel launchers (vrt_kernels.hip)
 // Which primary-render kernel launch_render runs: the one-wave grid
@@ -623,8 +651,10 @@ hipError_t launch_render(const RenderParams &p, bool instrumented,
 // current device
 hipError_t persistent_blocks(int *render_blocks, int *sec_blocks);
 bool secondary_uses_queue(const DevScene &sc);
-hipError_t launch_ray_march(const DevScene &sc, const void *d_rays,
-                            int64_t n, void *d_hits, hipStream_t st, const float *ord_wmin = nullptr);
+// pd != nullptr (a probe scene, even_invisible): the mixed march, which takes
+// no chain order
+hipError_t launch_ray_march(const DevScene &sc, const void *d_rays, int64_t n, void *d_hits, hipStream_t st,
+                            const float *ord_wmin = nullptr, const ProbeDev *pd = nullptr);
 hipError_t launch_unpack(int nx, int ny, int ntx, int nty, int nranks,
                          int tiles_per_rank, const float *src, float *dst,
                          hipStream_t st);
@@ -669,9 +699,13 @@ hipError_t launch_lm_accum(int64_t n, const uint64_t *keys_sorted, const uint32_
 hipError_t launch_lm_leaves(const NodeRec *nodes, int64_t nnodes, LMRec *lm, uint32_t *bad, unsigned int *count,
                             unsigned int *tail_n, unsigned int *nseg, hipStream_t st);
 hipError_t launch_lm_level(const NodeRec *nodes, int64_t begin, int64_t end, LMRec *lm, hipStream_t st);
-hipError_t launch_trace(const TraceParams &p, hipStream_t st);
-hipError_t launch_trace_prim(const TraceParams &p, hipStream_t st);
-hipError_t launch_cones(const TraceParams &p, hipStream_t st);
+// a frame's two halves.  A probe scene's frame passes pd and sgs: the mixed
+// primary pass writes a probe hit's own record and reads neither the SGs nor
+// the light map; the cones + film pass colours those records by
+// LightProbe::eval over sgs (device, 14 vrt_sg per probe).  fused: the host
+// expf's flavour (expf_model), a kernel argument
+hipError_t launch_trace_prim(const TraceParams &p, hipStream_t st, const ProbeDev *pd = nullptr);
+hipError_t launch_cones(const TraceParams &p, hipStream_t st, const float *sgs = nullptr, int fused = 0);
 // the batched trace(): io.n rays in chunks of `chunk` records (p.rec), and
 // the batched cone_trace; both build the step table first when p.build_steps
 // pd != nullptr (a probe scene): the primary march is the mixed march; a ray
@@ -685,13 +719,6 @@ hipError_t launch_cones_batch(const TraceParams &p, const BatchIO &io, hipStream
 // host_points = npoints x 3 floats on the host
 hipError_t launch_probe_gather(const TraceParams &p, const ProbeIO &io, const float *host_points, int64_t chunk,
                                hipStream_t st);
-// a probe scene's frame (vrt_render_trace_probes*): the mixed primary pass,
-// which writes a probe hit's own record and reads neither the SGs nor the
-// light map, and the cones + film pass that colours those records by
-// LightProbe::eval over sgs (device, 14 vrt_sg per probe).  fused: the host
-// expf's flavour (expf_model), a kernel argument
-hipError_t launch_trace_prim_mixed(const TraceParams &p, const ProbeDev &pd, hipStream_t st);
-hipError_t launch_cones_probes(const TraceParams &p, const float *sgs, int fused, hipStream_t st);
 // out[k] = expf_model(bits first + k * stride), k < n (k_selftest_expf)
 hipError_t launch_selftest_expf(uint32_t first, uint32_t stride, int64_t n, int fused, float *out, hipStream_t st);
 // y[i] = expf_model(x[i]) on the device (device arrays)

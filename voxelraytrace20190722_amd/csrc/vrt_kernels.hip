@@ -1324,6 +1324,13 @@ __device__ __forceinline__ RayK make_rayk(f3 o, f3 dn, float tmin, float tmax)
         return r;
 }
 
+// the i-th vrt_ray of a caller's array: {o, d, tmin, tmax}, 8 floats
+__device__ __forceinline__ RayK load_ray(const float *__restrict__ rays, int64_t i)
+{
+        const float *rr = rays + 8 * i;
+        return make_rayk(mk3(rr[0], rr[1], rr[2]), mk3(rr[3], rr[4], rr[5]), rr[6], rr[7]);
+}
+
 // Rays for which expand's fast path is exact (see expand_v1): finite
 // origin and direction, no non-zero denormal direction component, |o| <
 // 2^60 and |d| < 2^64 per component (the scene's own flag bounds the boxes
@@ -1952,8 +1959,22 @@ __device__ __forceinline__ void spill_group(SpillRec *rec, SpillCursor &c, bool 
 }
 
 
+// Triangle::isect's normal (VRT/voxel_octree.cc:451-453): the vertex normals
+// weighted by the hit's clamped barycentrics, one rounding per operation
+__device__ __forceinline__ f3 tri_normal(f3 n0, f3 n1, f3 n2, float u, float v)
+{
+        const float w = clampf(1.0f - u - v, 0, 1);
+        return normalize((n0 * w + n1 * u) + n2 * v);
+}
+
+__device__ __forceinline__ f3 tri_normal(const TriAttr *ta, float u, float v)
+{
+        return tri_normal(mk3(ta->n[0], ta->n[1], ta->n[2]), mk3(ta->n[3], ta->n[4], ta->n[5]),
+                          mk3(ta->n[6], ta->n[7], ta->n[8]), u, v);
+}
+
 // Triangle::get_albedo (VRT/voxel_octree.cc:472-484) with Triangle::isect's
-// normal (VRT/voxel_octree.cc:451-453).
+// normal.
 __device__ __forceinline__ f3 hit_albedo(const DevScene &sc, const MarchResult &m, f3 &normal)
 {
         const TriAttr *ta = sc.tri_attr + m.tri;
@@ -1968,8 +1989,7 @@ __device__ __forceinline__ f3 hit_albedo(const DevScene &sc, const MarchResult &
         const float t0u = a2.y, t0v = a2.z, t1u = a2.w, t1v = a3.x,
                     t2u = a3.y, t2v = a3.z;
         const int mat = __float_as_int(a3.w);
-        const float w = clampf(1.0f - m.u - m.v, 0, 1);
-        normal = normalize((n0 * w + n1 * m.u) + n2 * m.v);
+        normal = tri_normal(n0, n1, n2, m.u, m.v);
         const MatRec mr = sc.mats[mat];
         f3 albedo;
         if (mr.tex < 0) {
@@ -2395,6 +2415,28 @@ __global__ __launch_bounds__(kPersistBlock, VRT_PERSIST_WAVES_PER_EU) void k_ren
 // Batched gi::ray_march over arbitrary rays: one ray per lane.
 // Output record = vrt_hit {hit, tri, voxel, hit_p[3], normal[3]} (36 B).
 // ---------------------------------------------------------------------------
+__device__ __forceinline__ void write_hit(uint32_t *__restrict__ o, uint32_t tri, uint32_t vox, f3 hp, f3 nrm)
+{
+        o[0] = 1;
+        o[1] = tri;
+        o[2] = vox;
+        o[3] = __float_as_uint(hp.x);
+        o[4] = __float_as_uint(hp.y);
+        o[5] = __float_as_uint(hp.z);
+        o[6] = __float_as_uint(nrm.x);
+        o[7] = __float_as_uint(nrm.y);
+        o[8] = __float_as_uint(nrm.z);
+}
+
+__device__ __forceinline__ void write_miss(uint32_t *__restrict__ o)
+{
+        o[0] = 0;
+        o[1] = 0xFFFFFFFFu;
+        o[2] = 0xFFFFFFFFu;
+        for (int q = 3; q < 9; ++q)
+                o[q] = 0;
+}
+
 template <bool kR64>
 __global__ __launch_bounds__(kBlock) void k_ray_march(DevScene sc,
                                                       const float *__restrict__ rays,
@@ -2406,37 +2448,15 @@ __global__ __launch_bounds__(kBlock) void k_ray_march(DevScene sc,
         const int64_t i = (int64_t)blockIdx.x * kBlock + tid;
         if (i >= n)
                 return;
-        const float *rr = rays + 8 * i;
-        const RayK r = make_rayk(mk3(rr[0], rr[1], rr[2]), mk3(rr[3], rr[4], rr[5]),
-                                 rr[6], rr[7]);
+        const RayK r = load_ray(rays, i);
         MarchResult m;
         ray_march_dispatch<false, kBlock, true, kR64, 0, true, !kR64>(sc, r, stk + tid, nullptr, nullptr, m, cw.wmin[0],
                                                                       cw.wmin[1], cw.wmin[2]);
         uint32_t *o = out + 9 * i;
-        if (m.hit) {
-                f3 nrm;
-                const TriAttr *ta = sc.tri_attr + m.tri;
-                const f3 n0 = mk3(ta->n[0], ta->n[1], ta->n[2]);
-                const f3 n1 = mk3(ta->n[3], ta->n[4], ta->n[5]);
-                const f3 n2 = mk3(ta->n[6], ta->n[7], ta->n[8]);
-                const float w = clampf(1.0f - m.u - m.v, 0, 1);
-                nrm = normalize((n0 * w + n1 * m.u) + n2 * m.v);
-                o[0] = 1;
-                o[1] = m.tri;
-                o[2] = sc.node_vox[m.node];
-                o[3] = __float_as_uint(m.hp.x);
-                o[4] = __float_as_uint(m.hp.y);
-                o[5] = __float_as_uint(m.hp.z);
-                o[6] = __float_as_uint(nrm.x);
-                o[7] = __float_as_uint(nrm.y);
-                o[8] = __float_as_uint(nrm.z);
-        } else {
-                o[0] = 0;
-                o[1] = 0xFFFFFFFFu;
-                o[2] = 0xFFFFFFFFu;
-                for (int q = 3; q < 9; ++q)
-                        o[q] = 0;
-        }
+        if (m.hit)
+                write_hit(o, m.tri, sc.node_vox[m.node], m.hp, tri_normal(sc.tri_attr + m.tri, m.u, m.v));
+        else
+                write_miss(o);
 }
 
 // ---------------------------------------------------------------------------
@@ -2464,6 +2484,20 @@ struct MixedResult {
         f3 hp;          // ISect::hit
         f3 nrm;         // probe: ISect::normal
 };
+
+// a mixed march's result as the triangle march's, for the code that records a
+// triangle hit or a miss (tri is meaningful for a triangle hit only)
+__device__ __forceinline__ MarchResult as_march(const MixedResult &x)
+{
+        MarchResult m;
+        m.hit = x.hit;
+        m.node = x.node;
+        m.tri = x.vox;
+        m.u = x.u;
+        m.v = x.v;
+        m.hp = x.hp;
+        return m;
+}
 
 template <bool kR64>
 __device__ __forceinline__ bool leaf_isect_mixed(const DevScene &sc, const ProbeDev &pd, uint32_t first, uint32_t ntr,
@@ -2612,36 +2646,17 @@ __global__ __launch_bounds__(kBlock) void k_ray_march_mixed(DevScene sc, ProbeDe
         const int64_t i = (int64_t)blockIdx.x * kBlock + tid;
         if (i >= n)
                 return;
-        const float *rr = rays + 8 * i;
-        const RayK r = make_rayk(mk3(rr[0], rr[1], rr[2]), mk3(rr[3], rr[4], rr[5]), rr[6], rr[7]);
+        const RayK r = load_ray(rays, i);
         MixedResult m;
         ray_march_mixed<kR64>(sc, pd, r, stk + tid, m);
         uint32_t *o = out + 9 * i;
         if (m.hit) {
                 f3 nrm = m.nrm;
-                if (!m.probe) {
-                        const TriAttr *ta = sc.tri_attr + m.vox;
-                        const f3 n0 = mk3(ta->n[0], ta->n[1], ta->n[2]);
-                        const f3 n1 = mk3(ta->n[3], ta->n[4], ta->n[5]);
-                        const f3 n2 = mk3(ta->n[6], ta->n[7], ta->n[8]);
-                        const float w = clampf(1.0f - m.u - m.v, 0, 1);
-                        nrm = normalize((n0 * w + n1 * m.u) + n2 * m.v);
-                }
-                o[0] = 1;
-                o[1] = m.vox;
-                o[2] = sc.node_vox[m.node];
-                o[3] = __float_as_uint(m.hp.x);
-                o[4] = __float_as_uint(m.hp.y);
-                o[5] = __float_as_uint(m.hp.z);
-                o[6] = __float_as_uint(nrm.x);
-                o[7] = __float_as_uint(nrm.y);
-                o[8] = __float_as_uint(nrm.z);
+                if (!m.probe)
+                        nrm = tri_normal(sc.tri_attr + m.vox, m.u, m.v);
+                write_hit(o, m.vox, sc.node_vox[m.node], m.hp, nrm);
         } else {
-                o[0] = 0;
-                o[1] = 0xFFFFFFFFu;
-                o[2] = 0xFFFFFFFFu;
-                for (int q = 3; q < 9; ++q)
-                        o[q] = 0;
+                write_miss(o);
         }
 }
 
@@ -2745,6 +2760,7 @@ __global__ __launch_bounds__(kBlock) void k_primary1(RenderParams p, float *__re
         const f3 n0 = mk3(ta->n[0], ta->n[1], ta->n[2]);
         const f3 n1 = mk3(ta->n[3], ta->n[4], ta->n[5]);
         const f3 n2 = mk3(ta->n[6], ta->n[7], ta->n[8]);
+        // tri_normal, written out: through the helper this kernel is scheduled differently
         const float w = clampf(1.0f - m.u - m.v, 0, 1);
         const f3 nrm = normalize((n0 * w + n1 * m.u) + n2 * m.v);
         o[0] = 1.f;
@@ -4096,27 +4112,19 @@ hipError_t launch_render(const RenderParams &p, bool instrumented,
 }
 
 hipError_t launch_ray_march(const DevScene &sc, const void *d_rays, int64_t n,
-                            void *d_hits, hipStream_t st, const float *ord_wmin)
+                            void *d_hits, hipStream_t st, const float *ord_wmin, const ProbeDev *pd)
 {
         if (n <= 0)
                 return hipSuccess;
-        const int64_t grid = (n + kBlock - 1) / kBlock;
-        hipLaunchKernelGGL(sc.wide_leaves ? k_ray_march<true> : k_ray_march<false>, dim3((unsigned)grid),
-                           dim3(kBlock), 0, st,
-                           sc, static_cast<const float *>(d_rays), n,
-                           static_cast<uint32_t *>(d_hits), chain_w(ord_wmin));
-        return hipGetLastError();
-}
-
-hipError_t launch_ray_march_mixed(const DevScene &sc, const ProbeDev &pd, const void *d_rays, int64_t n,
-                                  void *d_hits, hipStream_t st)
-{
-        if (n <= 0)
-                return hipSuccess;
-        const int64_t grid = (n + kBlock - 1) / kBlock;
-        hipLaunchKernelGGL(sc.wide_leaves ? k_ray_march_mixed<true> : k_ray_march_mixed<false>, dim3((unsigned)grid),
-                           dim3(kBlock), 0, st, sc, pd, static_cast<const float *>(d_rays), n,
-                           static_cast<uint32_t *>(d_hits));
+        const dim3 grid((unsigned)((n + kBlock - 1) / kBlock));
+        const float *rays = static_cast<const float *>(d_rays);
+        uint32_t *hits = static_cast<uint32_t *>(d_hits);
+        if (pd)
+                hipLaunchKernelGGL(sc.wide_leaves ? k_ray_march_mixed<true> : k_ray_march_mixed<false>, grid,
+                                   dim3(kBlock), 0, st, sc, *pd, rays, n, hits);
+        else
+                hipLaunchKernelGGL(sc.wide_leaves ? k_ray_march<true> : k_ray_march<false>, grid, dim3(kBlock), 0, st,
+                                   sc, rays, n, hits, chain_w(ord_wmin));
         return hipGetLastError();
 }
 
@@ -4900,8 +4908,50 @@ __device__ __forceinline__ f3 cone_march_ref(const TraceParams &p, f3 o, f3 d)
 // rec[0].xyz, normal in rec[1].xyz), the record re-read and the basis remade
 // per cone -- the same operations, so the same values (volatile asm keeps the
 // compiler from hoisting the record across the marches)
+constexpr float kConeX[6] = { 0.000000f, 0.000000f, 0.823639f, 0.509037f, -0.509037f, -0.823639f };
+constexpr float kConeY[6] = { 0.000000f, 0.866025f, 0.267617f, -0.700629f, -0.700629f, 0.267617f };
+constexpr float kConeZ[6] = { 1.0f, 0.5f, 0.5f, 0.5f, 0.5f, 0.5f };
+constexpr float kConeW[6] = { 0.25f, 0.15f, 0.15f, 0.15f, 0.15f, 0.15f };
+
+// a cone's direction about the normal n: orthonormal_basis(n) = (t, bb), then
+// normalize(t * x + bb * y + n * z) added in that order from zero
+__device__ __forceinline__ f3 cone_dir(f3 n, float x, float y, float z)
+{
+        const float sg = (0.0f > n.z) ? -1.0f : 1.0f;
+        const float a0 = -1.0f / (sg + n.z);
+        const float a1 = n.x * n.y * a0;
+        const f3 t = mk3(1.0f + sg * n.x * n.x * a0, sg * a1, -sg * n.x);
+        const f3 bb = mk3(a1, sg + n.y * n.y * a0, -n.y);
+        f3 r = mk3(0.f, 0.f, 0.f);
+        r = r + t * x;
+        r = r + bb * y;
+        r = r + n * z;
+        return normalize(r);
+}
+
+__device__ __forceinline__ f3 cone_dir(f3 n, int c)
+{
+        return cone_dir(n, kConeX[c], kConeY[c], kConeZ[c]);
+}
+
+// one (ray, cone) per lane, a ray's cones in lanes l0 .. l0 + 5: their
+// weighted sum in cone order from zero, as cone_trace adds them, in every lane
+__device__ __forceinline__ f3 cone_sum(f3 cm, int l0)
+{
+        f3 diffuse = mk3(0.f, 0.f, 0.f);
+#pragma unroll
+        for (int j = 0; j < 6; ++j) {
+                const int src = (l0 + j) & 63;
+                const f3 cj = mk3(__shfl(cm.x, src, 64), __shfl(cm.y, src, 64), __shfl(cm.z, src, 64));
+                diffuse = diffuse + cj * kConeW[j];
+        }
+        return diffuse;
+}
+
 __device__ __forceinline__ f3 cone_trace_rec(const TraceParams &p, const float4 *rec)
 {
+        // kConeX .. kConeW, local so that the built k_cones_film<> (whose code
+        // names its tables) stays as it was
         const float hx[6] = { 0.000000f, 0.000000f, 0.823639f, 0.509037f, -0.509037f, -0.823639f };
         const float hy[6] = { 0.000000f, 0.866025f, 0.267617f, -0.700629f, -0.700629f, 0.267617f };
         const float hz[6] = { 1.0f, 0.5f, 0.5f, 0.5f, 0.5f, 0.5f };
@@ -4912,17 +4962,7 @@ __device__ __forceinline__ f3 cone_trace_rec(const TraceParams &p, const float4 
                 asm volatile("" : "+v"(q));
                 const float4 r0 = q[0], r1 = q[1];
                 const f3 hit = mk3(r0.x, r0.y, r0.z), n = mk3(r1.x, r1.y, r1.z);
-                const float sg = (0.0f > n.z) ? -1.0f : 1.0f;
-                const float a0 = -1.0f / (sg + n.z);
-                const float a1 = n.x * n.y * a0;
-                const f3 t = mk3(1.0f + sg * n.x * n.x * a0, sg * a1, -sg * n.x);
-                const f3 bb = mk3(a1, sg + n.y * n.y * a0, -n.y);
-                f3 r = mk3(0.f, 0.f, 0.f);
-                r = r + t * hx[i];
-                r = r + bb * hy[i];
-                r = r + n * hz[i];
-                const f3 cd = normalize(r);
-                const f3 cm = cone_march(p, hit, cd);
+                const f3 cm = cone_march(p, hit, cone_dir(n, hx[i], hy[i], hz[i]));
                 diffuse = diffuse + cm * hw[i];
         }
         return diffuse;
@@ -5060,14 +5100,7 @@ __global__ __launch_bounds__(kBlock) void k_trace_prim_mixed(TraceParams p, Prob
                 o[1] = make_float4(__uint_as_float(x.vox - (uint32_t)pd.ntri), 0.f, 0.f, 0.f);
                 return;
         }
-        MarchResult m;
-        m.hit = x.hit;
-        m.node = x.node;
-        m.tri = x.vox;
-        m.u = x.u;
-        m.v = x.v;
-        m.hp = x.hp;
-        trace_prim_record(p, r, m, slot);
+        trace_prim_record(p, r, as_march(x), slot);
 }
 
 // Cones + film: one wave per work unit of the primary pass (its 64 sample
@@ -5197,8 +5230,7 @@ __global__ __launch_bounds__(kBlock) void k_trace_batch_prim(TraceParams p, Batc
         const int64_t i = (int64_t)blockIdx.x * kBlock + tid;
         if (i >= io.n)
                 return;
-        const float *rr = io.rays + 8 * i;
-        const RayK r = make_rayk(mk3(rr[0], rr[1], rr[2]), mk3(rr[3], rr[4], rr[5]), rr[6], rr[7]);
+        const RayK r = load_ray(io.rays, i);
         MarchResult m;
         ray_march_dispatch<false, kBlock, true, kR64>(p.r.sc, r, stk + tid, nullptr, nullptr, m);
         trace_prim_record(p, r, m, i);
@@ -5208,21 +5240,9 @@ __global__ __launch_bounds__(kBlock) void k_trace_batch_prim(TraceParams p, Batc
                         // the record's normal: hit_albedo's, the operations of
                         // k_ray_march's
                         const float4 nr = p.rec[4 * i + 1];
-                        o[0] = 1;
-                        o[1] = m.tri;
-                        o[2] = p.r.sc.node_vox[m.node];
-                        o[3] = __float_as_uint(m.hp.x);
-                        o[4] = __float_as_uint(m.hp.y);
-                        o[5] = __float_as_uint(m.hp.z);
-                        o[6] = __float_as_uint(nr.x);
-                        o[7] = __float_as_uint(nr.y);
-                        o[8] = __float_as_uint(nr.z);
+                        write_hit(o, m.tri, p.r.sc.node_vox[m.node], m.hp, mk3(nr.x, nr.y, nr.z));
                 } else {
-                        o[0] = 0;
-                        o[1] = 0xFFFFFFFFu;
-                        o[2] = 0xFFFFFFFFu;
-                        for (int q = 3; q < 9; ++q)
-                                o[q] = 0;
+                        write_miss(o);
                 }
         }
 }
@@ -5242,17 +5262,11 @@ __global__ __launch_bounds__(kBlock) void k_trace_batch_prim_mixed(TraceParams p
         const int64_t i = (int64_t)blockIdx.x * kBlock + tid;
         if (i >= io.n)
                 return;
-        const float *rr = io.rays + 8 * i;
-        const RayK r = make_rayk(mk3(rr[0], rr[1], rr[2]), mk3(rr[3], rr[4], rr[5]), rr[6], rr[7]);
+        const RayK r = load_ray(io.rays, i);
         MixedResult x;
         ray_march_mixed<kR64>(p.r.sc, pd, r, stk + tid, x);
-        MarchResult m;
+        MarchResult m = as_march(x);
         m.hit = x.hit && !x.probe;
-        m.node = x.node;
-        m.tri = x.vox;
-        m.u = x.u;
-        m.v = x.v;
-        m.hp = x.hp;
         f3 nrm = x.nrm;
         if (x.hit && x.probe) {
                 float4 *o = p.rec + 4 * i;
@@ -5267,23 +5281,10 @@ __global__ __launch_bounds__(kBlock) void k_trace_batch_prim_mixed(TraceParams p
         }
         if (io.hits) {
                 uint32_t *o = io.hits + 9 * i;
-                if (x.hit) {
-                        o[0] = 1;
-                        o[1] = x.vox;
-                        o[2] = p.r.sc.node_vox[x.node];
-                        o[3] = __float_as_uint(x.hp.x);
-                        o[4] = __float_as_uint(x.hp.y);
-                        o[5] = __float_as_uint(x.hp.z);
-                        o[6] = __float_as_uint(nrm.x);
-                        o[7] = __float_as_uint(nrm.y);
-                        o[8] = __float_as_uint(nrm.z);
-                } else {
-                        o[0] = 0;
-                        o[1] = 0xFFFFFFFFu;
-                        o[2] = 0xFFFFFFFFu;
-                        for (int q = 3; q < 9; ++q)
-                                o[q] = 0;
-                }
+                if (x.hit)
+                        write_hit(o, x.vox, p.r.sc.node_vox[x.node], x.hp, nrm);
+                else
+                        write_miss(o);
         }
 }
 
@@ -5305,10 +5306,6 @@ constexpr int kBatchRays = 10;
 template <bool kIsect>
 __global__ __launch_bounds__(64, VRT_BATCH_WAVES_PER_EU) void k_cones_batch(TraceParams p, BatchIO io)
 {
-        const float hx[6] = { 0.000000f, 0.000000f, 0.823639f, 0.509037f, -0.509037f, -0.823639f };
-        const float hy[6] = { 0.000000f, 0.866025f, 0.267617f, -0.700629f, -0.700629f, 0.267617f };
-        const float hz[6] = { 1.0f, 0.5f, 0.5f, 0.5f, 0.5f, 0.5f };
-        const float hw[6] = { 0.25f, 0.15f, 0.15f, 0.15f, 0.15f, 0.15f };
         const int lane = threadIdx.x;
         const int rl = lane / 6, c = lane - 6 * rl;  // lanes 60-63: rl == kBatchRays
         const int64_t i = (int64_t)blockIdx.x * kBatchRays + rl;
@@ -5332,29 +5329,10 @@ __global__ __launch_bounds__(64, VRT_BATCH_WAVES_PER_EU) void k_cones_batch(Trac
                                 n = mk3(r1.x, r1.y, r1.z);
                         }
                 }
-                if (hit) {
-                        const float sg = (0.0f > n.z) ? -1.0f : 1.0f;
-                        const float a0 = -1.0f / (sg + n.z);
-                        const float a1 = n.x * n.y * a0;
-                        const f3 t = mk3(1.0f + sg * n.x * n.x * a0, sg * a1, -sg * n.x);
-                        const f3 bb = mk3(a1, sg + n.y * n.y * a0, -n.y);
-                        f3 r = mk3(0.f, 0.f, 0.f);
-                        r = r + t * hx[c];
-                        r = r + bb * hy[c];
-                        r = r + n * hz[c];
-                        const f3 cd = normalize(r);
-                        cm = cone_march(p, hp, cd);
-                }
+                if (hit)
+                        cm = cone_march(p, hp, cone_dir(n, c));
         }
-        // every lane is back here: the six cones of the ray, in cone order
-        const int l0 = lane - c;
-        f3 diffuse = mk3(0.f, 0.f, 0.f);
-#pragma unroll
-        for (int j = 0; j < 6; ++j) {
-                const int src = (l0 + j) & 63;
-                const f3 cj = mk3(__shfl(cm.x, src, 64), __shfl(cm.y, src, 64), __shfl(cm.z, src, 64));
-                diffuse = diffuse + cj * hw[j];
-        }
+        f3 diffuse = cone_sum(cm, lane - c);  // every lane is back here
         if (!live || c != 0)
                 return;
         float *o = io.rgb + 3 * i;
@@ -5462,12 +5440,7 @@ __global__ __launch_bounds__(kBlock) void k_probe_march(TraceParams p, ProbeIO i
         ray_march_dispatch<false, kBlock, true, kR64>(p.r.sc, r, stk + tid, nullptr, nullptr, m);
         float4 *rec = p.rec + 4 * ((int64_t)grp * io.npoints + j);
         if (m.hit) {
-                const TriAttr *ta = p.r.sc.tri_attr + m.tri;
-                const f3 n0 = mk3(ta->n[0], ta->n[1], ta->n[2]);
-                const f3 n1 = mk3(ta->n[3], ta->n[4], ta->n[5]);
-                const f3 n2 = mk3(ta->n[6], ta->n[7], ta->n[8]);
-                const float w = clampf(1.0f - m.u - m.v, 0, 1);
-                const f3 nrm = normalize((n0 * w + n1 * m.u) + n2 * m.v);
+                const f3 nrm = tri_normal(p.r.sc.tri_attr + m.tri, m.u, m.v);
                 rec[0] = make_float4(m.hp.x, m.hp.y, m.hp.z, 1.f);
                 rec[1] = make_float4(nrm.x, nrm.y, nrm.z, 0.f);
         } else {
@@ -5482,10 +5455,6 @@ __global__ __launch_bounds__(kBlock) void k_probe_march(TraceParams p, ProbeIO i
 // nothing).
 __global__ __launch_bounds__(64, VRT_BATCH_WAVES_PER_EU) void k_probe_cones(TraceParams p, ProbeIO io)
 {
-        const float hx[6] = { 0.000000f, 0.000000f, 0.823639f, 0.509037f, -0.509037f, -0.823639f };
-        const float hy[6] = { 0.000000f, 0.866025f, 0.267617f, -0.700629f, -0.700629f, 0.267617f };
-        const float hz[6] = { 1.0f, 0.5f, 0.5f, 0.5f, 0.5f, 0.5f };
-        const float hw[6] = { 0.25f, 0.15f, 0.15f, 0.15f, 0.15f, 0.15f };
         const int lane = threadIdx.x;
         const int rl = lane / 6, c = lane - 6 * rl;  // lanes 60-63: rl == kBatchRays
         const int64_t nrays = (int64_t)kProbeSGs * io.n * io.npoints;
@@ -5500,28 +5469,10 @@ __global__ __launch_bounds__(64, VRT_BATCH_WAVES_PER_EU) void k_probe_cones(Trac
                         const f3 hp = mk3(r0.x, r0.y, r0.z);
                         const float4 r1 = p.rec[4 * i + 1];
                         const f3 n = mk3(r1.x, r1.y, r1.z);
-                        const float sg = (0.0f > n.z) ? -1.0f : 1.0f;
-                        const float a0 = -1.0f / (sg + n.z);
-                        const float a1 = n.x * n.y * a0;
-                        const f3 t = mk3(1.0f + sg * n.x * n.x * a0, sg * a1, -sg * n.x);
-                        const f3 bb = mk3(a1, sg + n.y * n.y * a0, -n.y);
-                        f3 r = mk3(0.f, 0.f, 0.f);
-                        r = r + t * hx[c];
-                        r = r + bb * hy[c];
-                        r = r + n * hz[c];
-                        const f3 cd = normalize(r);
-                        cm = cone_march(p, hp, cd);
+                        cm = cone_march(p, hp, cone_dir(n, c));
                 }
         }
-        // every lane is back here: the six cones of the ray, in cone order
-        const int l0 = lane - c;
-        f3 diffuse = mk3(0.f, 0.f, 0.f);
-#pragma unroll
-        for (int j = 0; j < 6; ++j) {
-                const int src = (l0 + j) & 63;
-                const f3 cj = mk3(__shfl(cm.x, src, 64), __shfl(cm.y, src, 64), __shfl(cm.z, src, 64));
-                diffuse = diffuse + cj * hw[j];
-        }
+        const f3 diffuse = cone_sum(cm, lane - c);  // every lane is back here
         if (!live || c != 0)
                 return;
         const f3 term = hit ? diffuse : mk3(io.light[0], io.light[1], io.light[2]);
@@ -5662,67 +5613,48 @@ hipError_t launch_lm_level(const NodeRec *nodes, int64_t begin, int64_t end, LMR
         return hipGetLastError();
 }
 
-hipError_t launch_trace(const TraceParams &p, hipStream_t st)
+// the split trace's two halves: the primary march (no light-map read; then
+// the step table when p.build_steps) and the cones + film pass (reads the
+// light map).  pd / sgs set: a probe scene's frame, the mixed primary pass
+// and the cones + film pass that also shades probe hits over the device SGs.
+hipError_t launch_trace_prim(const TraceParams &p, hipStream_t st, const ProbeDev *pd)
 {
         if (p.r.tiles_this_rank <= 0)
                 return hipSuccess;
-        if (hipError_t e = launch_trace_prim(p, st))
-                return e;
-        return launch_cones(p, st);
-}
-
-// the split trace's two halves: the primary march (no light-map read) and
-// the cones + film pass (reads the light map)
-hipError_t launch_trace_prim(const TraceParams &p, hipStream_t st)
-{
-        if (p.r.tiles_this_rank <= 0)
-                return hipSuccess;
-        const bool tail = VRT_PRIM_BUDGET > 0 || (p.r.test_flags & VRT_TEST_PRIM_TAIL);
-        if (tail)
-                if (hipError_t e = hipMemsetAsync(p.tail_n, 0, 4, st))
-                        return e;
-        hipLaunchKernelGGL(p.r.sc.wide_leaves ? k_trace_prim<true> : k_trace_prim<false>,
-                           dim3(trace_vblocks(p.r.tiles_this_rank)), dim3(kRenderBlock), 0, st, p);
-        if (tail)
-                hipLaunchKernelGGL(p.r.sc.wide_leaves ? k_trace_prim_tail<true> : k_trace_prim_tail<false>,
-                                   dim3(VRT_LIGHT_TAIL_GRID), dim3(64), 0, st, p);
+        const bool w = p.r.sc.wide_leaves;
+        if (pd) {
+                hipLaunchKernelGGL(w ? k_trace_prim_mixed<true> : k_trace_prim_mixed<false>,
+                                   dim3((unsigned)p.r.tiles_this_rank), dim3(kBlock), 0, st, p, *pd);
+        } else {
+                const bool tail = VRT_PRIM_BUDGET > 0 || (p.r.test_flags & VRT_TEST_PRIM_TAIL);
+                if (tail)
+                        if (hipError_t e = hipMemsetAsync(p.tail_n, 0, 4, st))
+                                return e;
+                hipLaunchKernelGGL(w ? k_trace_prim<true> : k_trace_prim<false>,
+                                   dim3(trace_vblocks(p.r.tiles_this_rank)), dim3(kRenderBlock), 0, st, p);
+                if (tail)
+                        hipLaunchKernelGGL(w ? k_trace_prim_tail<true> : k_trace_prim_tail<false>,
+                                           dim3(VRT_LIGHT_TAIL_GRID), dim3(64), 0, st, p);
+        }
         if (p.build_steps)
                 hipLaunchKernelGGL(k_cone_steps, dim3(1), dim3(64), 0, st, p);
         return hipGetLastError();
 }
 
-hipError_t launch_cones(const TraceParams &p, hipStream_t st)
+hipError_t launch_cones(const TraceParams &p, hipStream_t st, const float *sgs, int fused)
 {
         if (p.r.tiles_this_rank <= 0)
                 return hipSuccess;
-        const int64_t nslots = (int64_t)p.r.tiles_this_rank * 256;
-        hipLaunchKernelGGL(k_cones_film<false>, dim3((unsigned)(nslots / 64)), dim3(64), 0, st, p);
-        return hipGetLastError();
-}
-
-// a probe scene's frame: the mixed primary pass (and the step table when
-// p.build_steps), then the cones + film pass over the device SGs
-hipError_t launch_trace_prim_mixed(const TraceParams &p, const ProbeDev &pd, hipStream_t st)
-{
-        if (p.r.tiles_this_rank <= 0)
-                return hipSuccess;
-        hipLaunchKernelGGL(p.r.sc.wide_leaves ? k_trace_prim_mixed<true> : k_trace_prim_mixed<false>,
-                           dim3((unsigned)p.r.tiles_this_rank), dim3(kBlock), 0, st, p, pd);
-        if (p.build_steps)
-                hipLaunchKernelGGL(k_cone_steps, dim3(1), dim3(64), 0, st, p);
-        return hipGetLastError();
-}
-
-hipError_t launch_cones_probes(const TraceParams &p, const float *sgs, int fused, hipStream_t st)
-{
-        if (p.r.tiles_this_rank <= 0)
-                return hipSuccess;
-        const int64_t nslots = (int64_t)p.r.tiles_this_rank * 256;
-        TraceParamsProbes pp;
-        static_cast<TraceParams &>(pp) = p;
-        pp.sgs = sgs;
-        pp.fused = fused;
-        hipLaunchKernelGGL(k_cones_film<true>, dim3((unsigned)(nslots / 64)), dim3(64), 0, st, pp);
+        const dim3 grid((unsigned)p.r.tiles_this_rank * 4);  // a wave per 64 sample slots
+        if (sgs) {
+                TraceParamsProbes pp;
+                static_cast<TraceParams &>(pp) = p;
+                pp.sgs = sgs;
+                pp.fused = fused;
+                hipLaunchKernelGGL(k_cones_film<true>, grid, dim3(64), 0, st, pp);
+        } else {
+                hipLaunchKernelGGL(k_cones_film<false>, grid, dim3(64), 0, st, p);
+        }
         return hipGetLastError();
 }
 
