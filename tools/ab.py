@@ -220,7 +220,8 @@ def share_ab(a, libs, scenes, film, cams):
         mx = max(per.values())
         base = base or mx
         out[os.path.basename(p)] = {"max_step_ms": round(mx, 4), "speedup": round(base / mx, 3),
-                                    "per_rank_ms": {r: round(v, 4) for r, v in per.items()}}
+                                    "per_rank_ms": {r: round(v, 4) for r, v in per.items()},
+                                    "rounds_ms": {r: [round(float(v), 4) for v in times[p][r]] for r in ranks}}
     print(json.dumps(out, indent=1))
 
 

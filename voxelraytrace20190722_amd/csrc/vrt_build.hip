@@ -371,25 +371,9 @@ __global__ __launch_bounds__(256) void k_probe_masks(int64_t begin, int64_t end,
         has[ni] = m ? 1 : 0;
 }
 
-struct Dev {
-        void *p = nullptr;
-        ~Dev()
-        {
-                if (p)
-                        (void)hipFree(p);
-        }
-        hipError_t alloc(size_t n)
-        {
-                if (p)
-                        (void)hipFree(p);
-                p = nullptr;
-                return hipMalloc(&p, n ? n : 16);
-        }
-        template <class T>
-        T *as() const
-        {
-                return static_cast<T *>(p);
-        }
+// a build array: never empty once allocated
+struct Dev : DevMem {
+        hipError_t alloc(size_t n) { return DevMem::alloc(n ? n : 16); }
 };
 
 #define BCHK(expr)                                                                           \
@@ -427,24 +411,16 @@ hipError_t build_tree_device(int device, const float *pos, int ntri, const float
         static_assert(sizeof(vrt_probe) == sizeof(float4), "vrt_probe layout");
         BCHK(hipSetDevice(device));
         hipStream_t st = nullptr;
-        hipEvent_t e0, e1;
-        BCHK(hipEventCreate(&e0));
-        BCHK(hipEventCreate(&e1));
-        struct EvGuard {
-                hipEvent_t a, b;
-                ~EvGuard()
-                {
-                        (void)hipEventDestroy(a);
-                        (void)hipEventDestroy(b);
-                }
-        } evg{ e0, e1 };
+        Event e0, e1;
+        BCHK(e0.create());
+        BCHK(e1.create());
         Dev dpos, cnt, pa, pb, codes, codes_s, uniq, nuniq, temp, iall, keys, keys_s, inode, dnodes, dvox, dhas;
         Dev dprobes, qa, qb, pkeys, pkeys_s, dpref, dpnode, dphas;  // the probe frontier and its outputs
         BCHK(dpos.alloc((size_t)ntri * 36));
-        BCHK(hipMemcpy(dpos.p, pos, (size_t)ntri * 36, hipMemcpyHostToDevice));
+        BCHK(hipMemcpy(dpos, pos, (size_t)ntri * 36, hipMemcpyHostToDevice));
         if (nprobe > 0) {
                 BCHK(dprobes.alloc((size_t)nprobe * sizeof(float4)));
-                BCHK(hipMemcpy(dprobes.p, probes, (size_t)nprobe * sizeof(float4), hipMemcpyHostToDevice));
+                BCHK(hipMemcpy(dprobes, probes, (size_t)nprobe * sizeof(float4), hipMemcpyHostToDevice));
         }
         BCHK(hipEventRecord(e0, st));
         BCHK(cnt.alloc(16));
@@ -457,13 +433,13 @@ hipError_t build_tree_device(int device, const float *pos, int ntri, const float
         root.code = 0;
         // level 1 frontier
         BCHK(pa.alloc((size_t)std::max(1, ntri) * sizeof(Pair)));
-        BCHK(hipMemsetAsync(cnt.p, 0, 16, st));
+        BCHK(hipMemsetAsync(cnt, 0, 16, st));
         if (ntri > 0)
                 hipLaunchKernelGGL(k_seed, dim3(grid_of(ntri)), dim3(256), 0, st, ntri, dpos.as<float>(), root,
                                    pa.as<Pair>(), cnt.as<unsigned int>());
         BCHK(hipGetLastError());
         unsigned int hn = 0;
-        BCHK(hipMemcpy(&hn, cnt.p, 4, hipMemcpyDeviceToHost));
+        BCHK(hipMemcpy(&hn, cnt, 4, hipMemcpyDeviceToHost));
         int64_t n = hn;
         // the probes' counter is the second word of cnt
         unsigned int *const qcnt = cnt.as<unsigned int>() + 1;
@@ -494,7 +470,7 @@ hipError_t build_tree_device(int device, const float *pos, int ntri, const float
                                 BCHK(hipcub::DeviceRadixSort::SortKeys(nullptr, tb, pkeys.as<uint64_t>(),
                                                                        pkeys_s.as<uint64_t>(), (int)nq, 0, bits, st));
                                 BCHK(temp.alloc(tb));
-                                BCHK(hipcub::DeviceRadixSort::SortKeys(temp.p, tb, pkeys.as<uint64_t>(),
+                                BCHK(hipcub::DeviceRadixSort::SortKeys(temp, tb, pkeys.as<uint64_t>(),
                                                                        pkeys_s.as<uint64_t>(), (int)nq, 0, bits, st));
                         }
                         // leaf lists: sort (code << 32 | tri)
@@ -510,7 +486,7 @@ hipError_t build_tree_device(int device, const float *pos, int ntri, const float
                                 BCHK(hipcub::DeviceRadixSort::SortKeys(nullptr, tb, keys.as<uint64_t>(),
                                                                        keys_s.as<uint64_t>(), (int)n, 0, bits, st));
                                 BCHK(temp.alloc(tb));
-                                BCHK(hipcub::DeviceRadixSort::SortKeys(temp.p, tb, keys.as<uint64_t>(),
+                                BCHK(hipcub::DeviceRadixSort::SortKeys(temp, tb, keys.as<uint64_t>(),
                                                                        keys_s.as<uint64_t>(), (int)n, 0, bits, st));
                         }
                         break;
@@ -525,7 +501,7 @@ hipError_t build_tree_device(int device, const float *pos, int ntri, const float
                 const int64_t nc = n + nq;
                 BCHK(codes.alloc((size_t)std::max<int64_t>(1, nc) * 4));
                 BCHK(pb.alloc((size_t)std::max<int64_t>(1, 8 * n) * sizeof(Pair)));
-                BCHK(hipMemsetAsync(cnt.p, 0, 16, st));
+                BCHK(hipMemsetAsync(cnt, 0, 16, st));
                 if (n > 0)
                         hipLaunchKernelGGL(k_expand, dim3(grid_of(n)), dim3(256), 0, st, n, pa.as<Pair>(),
                                            dpos.as<float>(), codes.as<uint32_t>(), pb.as<Pair>(),
@@ -550,26 +526,26 @@ hipError_t build_tree_device(int device, const float *pos, int ntri, const float
                         BCHK(hipcub::DeviceSelect::Unique(nullptr, tb2, codes_s.as<uint32_t>(), uniq.as<uint32_t>(),
                                                           nuniq.as<int>(), (int)nc, st));
                         BCHK(temp.alloc(std::max(tb, tb2)));
-                        BCHK(hipcub::DeviceRadixSort::SortKeys(temp.p, tb, codes.as<uint32_t>(), codes_s.as<uint32_t>(),
+                        BCHK(hipcub::DeviceRadixSort::SortKeys(temp, tb, codes.as<uint32_t>(), codes_s.as<uint32_t>(),
                                                                (int)nc, 0, bits, st));
-                        BCHK(hipcub::DeviceSelect::Unique(temp.p, tb2, codes_s.as<uint32_t>(), uniq.as<uint32_t>(),
+                        BCHK(hipcub::DeviceSelect::Unique(temp, tb2, codes_s.as<uint32_t>(), uniq.as<uint32_t>(),
                                                           nuniq.as<int>(), (int)nc, st));
                         int hnu = 0;
-                        BCHK(hipMemcpy(&hnu, nuniq.p, 4, hipMemcpyDeviceToHost));
+                        BCHK(hipMemcpy(&hnu, nuniq, 4, hipMemcpyDeviceToHost));
                         nu = hnu;
                         const size_t o = h_iall.size();
                         h_iall.resize(o + (size_t)nu);
                         if (nu)
-                                BCHK(hipMemcpy(h_iall.data() + o, uniq.p, (size_t)nu * 4, hipMemcpyDeviceToHost));
+                                BCHK(hipMemcpy(h_iall.data() + o, uniq, (size_t)nu * 4, hipMemcpyDeviceToHost));
                 }
                 n_int[l] = nu;
-                BCHK(hipMemcpy(&hn, cnt.p, 4, hipMemcpyDeviceToHost));
+                BCHK(hipMemcpy(&hn, cnt, 4, hipMemcpyDeviceToHost));
                 n = hn;
-                std::swap(pa.p, pb.p);
+                std::swap(pa, pb);
                 if (nq > 0) {
                         BCHK(hipMemcpy(&hn, qcnt, 4, hipMemcpyDeviceToHost));
                         nq = hn;
-                        std::swap(qa.p, qb.p);
+                        std::swap(qa, qb);
                 }
                 if (nu == 0)
                         break;  // nothing below this level
@@ -582,7 +558,7 @@ hipError_t build_tree_device(int device, const float *pos, int ntri, const float
         out->level_begin.clear();
         BCHK(iall.alloc(std::max<size_t>(1, h_iall.size()) * 4));
         if (!h_iall.empty())
-                BCHK(hipMemcpy(iall.p, h_iall.data(), h_iall.size() * 4, hipMemcpyHostToDevice));
+                BCHK(hipMemcpy(iall, h_iall.data(), h_iall.size() * 4, hipMemcpyHostToDevice));
         BCHK(inode.alloc(std::max<int64_t>(1, ninternal) * 4));
         BCHK(dnodes.alloc((size_t)nnodes * sizeof(NodeRec)));
         BCHK(dvox.alloc((size_t)nnodes * 4));
@@ -626,7 +602,7 @@ hipError_t build_tree_device(int device, const float *pos, int ntri, const float
         const int nlevels = (int)out->level_begin.size() - 1;
         if (nprobe > 0) {
                 BCHK(dpnode.alloc((size_t)nnodes * sizeof(uint2)));
-                BCHK(hipMemsetAsync(dpnode.p, 0, (size_t)nnodes * sizeof(uint2), st));
+                BCHK(hipMemsetAsync(dpnode, 0, (size_t)nnodes * sizeof(uint2), st));
         }
         if (nprefs > 0 && nlevels == D) {
                 unsigned int *const lcnt = cnt.as<unsigned int>() + 2;
@@ -656,21 +632,21 @@ hipError_t build_tree_device(int device, const float *pos, int ntri, const float
         out->nodes.resize((size_t)nnodes);
         out->node_vox.resize((size_t)nnodes);
         out->refs.resize((size_t)nrefs);
-        BCHK(hipMemcpy(out->nodes.data(), dnodes.p, (size_t)nnodes * sizeof(NodeRec), hipMemcpyDeviceToHost));
-        BCHK(hipMemcpy(out->node_vox.data(), dvox.p, (size_t)nnodes * 4, hipMemcpyDeviceToHost));
+        BCHK(hipMemcpy(out->nodes.data(), dnodes, (size_t)nnodes * sizeof(NodeRec), hipMemcpyDeviceToHost));
+        BCHK(hipMemcpy(out->node_vox.data(), dvox, (size_t)nnodes * 4, hipMemcpyDeviceToHost));
         if (nrefs)
-                BCHK(hipMemcpy(out->refs.data(), keys_s.p, (size_t)nrefs * 8, hipMemcpyDeviceToHost));
+                BCHK(hipMemcpy(out->refs.data(), keys_s, (size_t)nrefs * 8, hipMemcpyDeviceToHost));
         out->pnode.clear();
         out->pref.clear();
         out->probe_leaves = 0;
         if (nprobe > 0) {
                 out->pnode.resize((size_t)nnodes);
-                BCHK(hipMemcpy(out->pnode.data(), dpnode.p, (size_t)nnodes * sizeof(uint2), hipMemcpyDeviceToHost));
+                BCHK(hipMemcpy(out->pnode.data(), dpnode, (size_t)nnodes * sizeof(uint2), hipMemcpyDeviceToHost));
         }
         if (nprefs > 0 && nlevels == D) {
                 unsigned int hl = 0;
                 out->pref.resize((size_t)nprefs);
-                BCHK(hipMemcpy(out->pref.data(), dpref.p, (size_t)nprefs * 4, hipMemcpyDeviceToHost));
+                BCHK(hipMemcpy(out->pref.data(), dpref, (size_t)nprefs * 4, hipMemcpyDeviceToHost));
                 BCHK(hipMemcpy(&hl, cnt.as<unsigned int>() + 2, 4, hipMemcpyDeviceToHost));
                 out->probe_leaves = hl;
         }

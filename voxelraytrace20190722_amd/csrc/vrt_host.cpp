@@ -337,23 +337,27 @@ uint32_t vox_of(uint32_t code, int depth)
 // so the copies of the first bands run beside the renders of the last.
 constexpr int kOutBands = 4;
 struct HostOut {
-        float *d_img = nullptr;   // nx*ny*3 floats; pixels outside the tile grid stay 0
-        float *h_pin = nullptr;   // pinned staging of d_img
-        size_t bytes = 0;
+        Staging img;  // nx*ny*3 floats (pixels outside the tile grid stay 0) and their pinned copy; on cp
         int nx = 0, ny = 0;
-        hipStream_t st2 = nullptr, cp = nullptr;
-        hipEvent_t ev_r[kOutBands] = {}, ev_c[kOutBands] = {};
-        hipEvent_t ev_j = nullptr;  // second render stream joined back
+        Stream st2, cp;
+        Event ev_r[kOutBands], ev_c[kOutBands];
+        Event ev_j;  // second render stream joined back
 };
 
 // One set of the full trace's scene scratch (vrt_scene::ts).
 struct TraceSet {
-        LMRec *lm = nullptr;  // nodes x (LMRec + float4 cone record) + the finiteness flag
-        void *rec = nullptr;  // split-trace records (64 B per sample), the cone step table
-        size_t rec_bytes = 0;
+        DevMem lm;   // nodes x (LMRec + float4 cone record) + the finiteness flag
+        DevMem rec;  // split-trace records (64 B per sample), the cone step table
         float steps_key[2] = { -1.f, -1.f };  // (mindist, maxdist) the step table holds
-        hipEvent_t ev = nullptr;  // its last user's work
-        bool live = false;
+        LastUse use;
+};
+
+// The side stream of a compaction set's deferred-pixel walk and its fork /
+// join events (SideLaunch is the view launch_secondary takes): all three or
+// none.
+struct SideStream {
+        Stream st;
+        Event fork, join;
 };
 
 struct vrt_scene {
@@ -382,7 +386,7 @@ struct vrt_scene {
         std::vector<uint32_t> pref;
         std::vector<vrt_sg> probe_sgs;
         int64_t probe_leaves = 0;
-        void *d_probe = nullptr;
+        DevMem d_probe;
         ProbeDev pdev{};
         // the stored SGs' device copy (in d_probe), read by the kernels that
         // shade a probe hit.  The host copy probe_sgs is what the host
@@ -391,7 +395,7 @@ struct vrt_scene {
         // before its next reader (sync_probe_sgs)
         float *d_sgs = nullptr;
         bool sgs_stale = false;
-        hipEvent_t sg_ev = nullptr;  // vrt_trace_frame_probes_device: the gather is done
+        Event sg_ev;  // vrt_trace_frame_probes_device: the gather is done
         // full trace: two sets of {light-map block (LMRec + cone-descent
         // records + finiteness flag), split-trace records}, taken by
         // alternate light-map builds so that one frame's cone-traced shading
@@ -402,51 +406,47 @@ struct vrt_scene {
         TraceSet ts[2];
         int ts_next = 0;
         int lm_cur = -1;
-        void *d_light = nullptr;
-        size_t light_bytes = 0;
+        DevMem d_light;
         // config-5 ray compaction (SpillQueues): round counters + two record
         // queues of spill_cap chunks each; two sets, used by alternate
         // frames (two config-5 frames in flight on two streams), each with
         // the event of its last launch
-        void *d_spill[2] = {};
+        DevMem d_spill[2];
         uint32_t spill_cap[2] = {};  // chunks per queue
         int64_t spill_px[2] = {};    // deferred-pixel list capacity (pixels)
-        hipEvent_t spill_ev[2] = {};
-        bool spill_live[2] = {};
+        LastUse spill_use[2];
         hipStream_t spill_stream[2] = {};  // the set's last user (a stream keeps its set)
-        // per set: the side stream of its deferred-pixel walk, fork / join
-        SideLaunch spill_side[2] = {};
+        SideStream spill_side[2];
         // multi-rank tile deals tabled on the device (RenderParams::tile_xy),
         // one per (tiles, ranks, rank) used, built on first use by a kernel
         // on that call's stream (ev), kept until the scene is destroyed
         struct DealMap {
                 int ntx, nty, nranks, rank;
-                uint32_t *d;
-                hipEvent_t ev;
+                DevMem d;
+                LastUse built;
         };
         std::vector<DealMap> dmaps;
-        uint32_t *h_spill = nullptr;       // pinned: per set, its last launch's round counters (ctr[0..7])
+        PinnedMem h_spill;                 // per set, its last launch's round counters (ctr[0..7])
         uint32_t spill_want = 0;           // queue-0 chunks the next launch sizes for (0: first estimate)
         int spill_next = 0;
         int spill_last = -1;  // the set the last config-5 launch compacted with (vrt_secondary_spill_counts)
         // device
-        void *d_mem = nullptr;
+        DevMem d_mem;
         DevScene dev{};
         // chain order: per axis the smallest spacing of the
         // two child centres over the internal nodes, 0 = off (chain_spacing)
         float ord_wmin[3] = {};
-        hipStream_t stream = nullptr;
-        hipEvent_t ev0 = nullptr, ev1 = nullptr;
+        Stream stream;
+        Event ev0, ev1;
         bool timed = false;
         // persistent-render work queues (WorkQueue, vrt_internal.h): a ring
         // of kQueueSlots counter sets, each with its bases and the event of
         // its last launch
         uint32_t *d_queue = nullptr;
         uint32_t q_base[kQueueSlots][8] = {};
-        hipEvent_t q_ev[kQueueSlots] = {};
-        bool q_live[kQueueSlots] = {};
+        LastUse q_use[kQueueSlots];
         int q_next = 0;
-        hipEvent_t lm_ev = nullptr;  // vrt_trace_frame_device: the light map is filtered
+        Event lm_ev;  // vrt_trace_frame_device: the light map is filtered
         // vrt_render's host-output path (render_to_host): a device image kept
         // between calls, its pinned host staging copy, a second render stream
         // and a copy stream, and an event per band
@@ -1013,8 +1013,8 @@ static int upload(vrt_scene *s, const vrt_scene_desc *d)
                 tot += align_up(sizes[i]);
         }
         off[10] = tot;
-        HIPCHK(hipMalloc(&s->d_mem, tot));
-        char *base = static_cast<char *>(s->d_mem);
+        HIPCHK(s->d_mem.alloc(tot));
+        char *base = s->d_mem.as<char>();
         HIPCHK(hipMemset(base + off[8], 0, kQueueSlots * kQueueBytes));
         HIPCHK(hipMemcpy(base + off[0], s->nodes.data(), sz_nodes, hipMemcpyHostToDevice));
         HIPCHK(hipMemcpy(base + off[1], s->node_vox.data(), sz_vox, hipMemcpyHostToDevice));
@@ -1075,8 +1075,8 @@ static int upload(vrt_scene *s, const vrt_scene_desc *d)
                 const size_t sz_pr = align_up(std::max<size_t>(1, s->pref.size()) * sizeof(uint32_t));
                 const size_t sz_pb = align_up(s->probes.size() * sizeof(vrt_probe));
                 const size_t sz_sg = align_up(s->probe_sgs.size() * sizeof(vrt_sg));
-                HIPCHK(hipMalloc(&s->d_probe, sz_pn + sz_pr + sz_pb + sz_sg));
-                char *pb = static_cast<char *>(s->d_probe);
+                HIPCHK(s->d_probe.alloc(sz_pn + sz_pr + sz_pb + sz_sg));
+                char *pb = s->d_probe.as<char>();
                 HIPCHK(hipMemcpy(pb, s->pnode.data(), s->pnode.size() * sizeof(uint2), hipMemcpyHostToDevice));
                 if (!s->pref.empty())
                         HIPCHK(hipMemcpy(pb + sz_pn, s->pref.data(), s->pref.size() * sizeof(uint32_t),
@@ -1093,13 +1093,13 @@ static int upload(vrt_scene *s, const vrt_scene_desc *d)
                 tot += sz_pn + sz_pr + sz_pb + sz_sg;
         }
         s->info.device_bytes = (int64_t)tot;
-        HIPCHK(hipStreamCreateWithFlags(&s->stream, hipStreamNonBlocking));
-        HIPCHK(hipEventCreate(&s->ev0));
-        HIPCHK(hipEventCreate(&s->ev1));
-        for (int k = 0; k < kQueueSlots; ++k)
-                HIPCHK(hipEventCreateWithFlags(&s->q_ev[k], hipEventDisableTiming));
+        HIPCHK(s->stream.create());
+        HIPCHK(s->ev0.create());
+        HIPCHK(s->ev1.create());
+        for (LastUse &q : s->q_use)
+                HIPCHK(q.create());
         for (TraceSet &t : s->ts)
-                HIPCHK(hipEventCreateWithFlags(&t.ev, hipEventDisableTiming));
+                HIPCHK(t.use.create());
         return VRT_OK;
 }
 
@@ -1295,95 +1295,31 @@ int vrt::scene_replicate(const vrt_scene *src, const vrt_scene_desc *d, int devi
         return VRT_OK;
 }
 
+// The owners release everything; what is left to do first is to wait for the
+// scene's work in flight.  A scene that was never uploaded (host-only: no
+// d_mem, need_device) holds nothing and touches no device.
 extern "C" void vrt_scene_destroy(vrt_scene *s)
 {
         if (!s)
                 return;
-        if (s->d_mem || s->ts[0].lm || s->ts[1].lm || s->d_light || s->ts[0].rec || s->ts[1].rec || s->d_spill[0] ||
-            s->d_spill[1] || s->stream || s->ev0 || s->ev1 || s->ts[0].ev || s->ts[1].ev) {
+        if (s->d_mem) {
                 (void)hipSetDevice(s->device);
                 if (s->stream)
                         (void)hipStreamSynchronize(s->stream);
                 // launches on callers' streams: every work-queue slot, trace
-                // set and compaction set records its last user's event
-                for (int k = 0; k < kQueueSlots; ++k)
-                        if (s->q_live[k])
-                                (void)hipEventSynchronize(s->q_ev[k]);
+                // set, compaction set and deal map records its last user's event
+                for (LastUse &q : s->q_use)
+                        (void)q.sync();
                 for (TraceSet &t : s->ts)
-                        if (t.live)
-                                (void)hipEventSynchronize(t.ev);
-                for (int k = 0; k < 2; ++k)
-                        if (s->spill_live[k])
-                                (void)hipEventSynchronize(s->spill_ev[k]);
-                if (s->d_mem)
-                        (void)hipFree(s->d_mem);
-                if (s->d_probe)
-                        (void)hipFree(s->d_probe);
-                for (TraceSet &t : s->ts) {
-                        if (t.lm)
-                                (void)hipFree(t.lm);
-                        if (t.rec)
-                                (void)hipFree(t.rec);
-                        if (t.ev)
-                                (void)hipEventDestroy(t.ev);
-                }
-                if (s->d_light)
-                        (void)hipFree(s->d_light);
-                if (s->h_spill)
-                        (void)hipHostFree(s->h_spill);
-                for (int k = 0; k < 2; ++k) {
-                        if (s->d_spill[k])
-                                (void)hipFree(s->d_spill[k]);
-                        if (s->spill_ev[k])
-                                (void)hipEventDestroy(s->spill_ev[k]);
-                        if (s->spill_side[k].st)
-                                (void)hipStreamDestroy(s->spill_side[k].st);
-                        if (s->spill_side[k].fork)
-                                (void)hipEventDestroy(s->spill_side[k].fork);
-                        if (s->spill_side[k].join)
-                                (void)hipEventDestroy(s->spill_side[k].join);
-                }
-                for (auto &m : s->dmaps) {
-                        (void)hipEventSynchronize(m.ev);
-                        (void)hipEventDestroy(m.ev);
-                        (void)hipFree(m.d);
-                }
-                if (s->ev0)
-                        (void)hipEventDestroy(s->ev0);
-                if (s->ev1)
-                        (void)hipEventDestroy(s->ev1);
-                for (int k = 0; k < kQueueSlots; ++k)
-                        if (s->q_ev[k])
-                                (void)hipEventDestroy(s->q_ev[k]);
-                if (s->lm_ev)
-                        (void)hipEventDestroy(s->lm_ev);
-                if (s->sg_ev)
-                        (void)hipEventDestroy(s->sg_ev);
-                HostOut &ho = s->ho;
-                if (ho.st2)
-                        (void)hipStreamSynchronize(ho.st2);
-                if (ho.cp)
-                        (void)hipStreamSynchronize(ho.cp);
-                if (ho.d_img)
-                        (void)hipFree(ho.d_img);
-                if (ho.h_pin)
-                        (void)hipHostFree(ho.h_pin);
-                for (int b = 0; b < kOutBands; ++b) {
-                        if (ho.ev_r[b])
-                                (void)hipEventDestroy(ho.ev_r[b]);
-                        if (ho.ev_c[b])
-                                (void)hipEventDestroy(ho.ev_c[b]);
-                }
-                if (ho.ev_j)
-                        (void)hipEventDestroy(ho.ev_j);
-                if (ho.st2)
-                        (void)hipStreamDestroy(ho.st2);
-                if (ho.cp)
-                        (void)hipStreamDestroy(ho.cp);
-                for (Staging *g : { &s->rays, &s->hits, &s->tb })
-                        g->release();
-                if (s->stream)
-                        (void)hipStreamDestroy(s->stream);
+                        (void)t.use.sync();
+                for (LastUse &u : s->spill_use)
+                        (void)u.sync();
+                for (auto &m : s->dmaps)
+                        (void)m.built.sync();
+                if (s->ho.st2)
+                        (void)hipStreamSynchronize(s->ho.st2);
+                if (s->ho.cp)
+                        (void)hipStreamSynchronize(s->ho.cp);
         }
         delete s;
 }
@@ -1578,8 +1514,7 @@ static int queue_take(vrt_scene *s, hipStream_t st, WorkQueue *q, int *slot)
 {
         *slot = s->q_next;
         s->q_next = (*slot + 1) % kQueueSlots;
-        if (s->q_live[*slot])
-                HIPCHK(hipStreamWaitEvent(st, s->q_ev[*slot], 0));
+        HIPCHK(s->q_use[*slot].wait(st));
         q->ctr = s->d_queue + (size_t)*slot * kQueueWords;
         q->defer = q->ctr + 8 * kQueueStride;
         std::memcpy(q->base, s->q_base[*slot], sizeof q->base);
@@ -1591,8 +1526,7 @@ static int queue_release(vrt_scene *s, int slot, hipStream_t st, const int slice
         for (int x = 0; x < 8; ++x)
                 if (slice_units[x] > 0)
                         s->q_base[slot][x] += (uint32_t)slice_units[x] + (uint32_t)waves;
-        HIPCHK(hipEventRecord(s->q_ev[slot], st));
-        s->q_live[slot] = true;
+        HIPCHK(s->q_use[slot].record(st));
         return VRT_OK;
 }
 
@@ -1605,8 +1539,7 @@ static void queue_reset(vrt_scene *s, int slot, hipStream_t st)
 {
         (void)hipMemsetAsync(s->d_queue + (size_t)slot * kQueueWords, 0, kQueueBytes, st);
         std::memset(s->q_base[slot], 0, sizeof s->q_base[slot]);
-        if (hipEventRecord(s->q_ev[slot], st) == hipSuccess)
-                s->q_live[slot] = true;
+        (void)s->q_use[slot].record(st);
 }
 
 // One render launch on stream st (caller holds s->mu).
@@ -1678,51 +1611,46 @@ static int spill_setup(vrt_scene *s, int64_t rays, int64_t pixels, hipStream_t s
         // two streams); else the next one
         int k = -1;
         for (int i = 0; i < 2 && k < 0; ++i)
-                if (s->spill_live[i] && s->spill_stream[i] == st)
+                if (s->spill_use[i].live && s->spill_stream[i] == st)
                         k = i;
         for (int i = 0; i < 2 && k < 0; ++i)
-                if (s->d_spill[i] && (!s->spill_live[i] || hipEventQuery(s->spill_ev[i]) == hipSuccess))
+                if (s->d_spill[i] && s->spill_use[i].done())
                         k = i;
         if (k < 0) {
                 k = s->spill_next;
                 s->spill_next ^= 1;
         }
-        if (!s->spill_ev[k])
-                HIPCHK(hipEventCreateWithFlags(&s->spill_ev[k], hipEventDisableTiming));
+        LastUse &use = s->spill_use[k];
+        if (!use.ev)
+                HIPCHK(use.create());
         if (!s->spill_side[k].st) {
                 // all three or none (a set without a side stream runs the
                 // deferred walk on the launch's stream)
-                SideLaunch sl{};
-                if (hipEventCreateWithFlags(&sl.fork, hipEventDisableTiming) == hipSuccess &&
-                    hipEventCreateWithFlags(&sl.join, hipEventDisableTiming) == hipSuccess &&
-                    hipStreamCreateWithFlags(&sl.st, hipStreamNonBlocking) == hipSuccess) {
-                        s->spill_side[k] = sl;
-                } else {
+                SideStream sl;
+                if (sl.fork.create(hipEventDisableTiming) == hipSuccess &&
+                    sl.join.create(hipEventDisableTiming) == hipSuccess && sl.st.create() == hipSuccess)
+                        s->spill_side[k] = std::move(sl);
+                else
                         (void)hipGetLastError();
-                        if (sl.fork)
-                                (void)hipEventDestroy(sl.fork);
-                        if (sl.join)
-                                (void)hipEventDestroy(sl.join);
-                }
         }
         if (!s->h_spill) {
-                HIPCHK(hipHostMalloc(reinterpret_cast<void **>(&s->h_spill), 16 * sizeof(uint32_t),
-                                     hipHostMallocDefault));
+                HIPCHK(s->h_spill.alloc(16 * sizeof(uint32_t)));
                 std::memset(s->h_spill, 0, 16 * sizeof(uint32_t));
         }
+        const uint32_t *h_ctr = s->h_spill.as<uint32_t>();
         // the deferred-pixel list holds one entry per pixel of the film
         const int64_t px = std::max<int64_t>(pixels, s->spill_px[k]);
         const uint32_t cap_max = spill_cap_max(spill_dpix_bytes(px));
         // what the finished launches of either set stopped: records queued
         // (ctr[2]) + records finished in place for want of room (ctr[5])
         for (int i = 0; i < 2; ++i)
-                if (s->spill_live[i] && s->spill_cap[i] && hipEventQuery(s->spill_ev[i]) == hipSuccess) {
-                        const uint64_t need = (uint64_t)s->h_spill[8 * i + 2] + s->h_spill[8 * i + 5];
+                if (s->spill_use[i].live && s->spill_cap[i] && s->spill_use[i].done()) {
+                        const uint64_t need = (uint64_t)h_ctr[8 * i + 2] + h_ctr[8 * i + 5];
                         const uint64_t w = (need * 5 / 4 + kSpillChunk - 1) / kSpillChunk;
                         s->spill_want = (uint32_t)std::min<uint64_t>(std::max<uint64_t>(s->spill_want, w), cap_max);
                 }
-        if (s->spill_live[k] && s->spill_stream[k] != st)
-                HIPCHK(hipStreamWaitEvent(st, s->spill_ev[k], 0));
+        if (s->spill_stream[k] != st)
+                HIPCHK(use.wait(st));
         // + one partly filled chunk per wave of a resident grid
         const int64_t partial = (int64_t)std::max(1, s->dev.sec_blocks) * 4;
         const int64_t est = s->spill_want ? (int64_t)s->spill_want : (rays / 32 + kSpillChunk - 1) / kSpillChunk;
@@ -1736,23 +1664,20 @@ static int spill_setup(vrt_scene *s, int64_t rays, int64_t pixels, hipStream_t s
                         // the set's users on any stream are ordered by its event
                         // (spill_done after each, a stream wait when a set
                         // changes stream): the last one's event covers them all
-                        if (s->spill_live[k])
-                                HIPCHK(hipEventSynchronize(s->spill_ev[k]));
-                        (void)hipFree(s->d_spill[k]);
-                        s->d_spill[k] = nullptr;
+                        HIPCHK(use.sync());
+                        s->d_spill[k].reset();
                         s->spill_cap[k] = 0;
                         s->spill_px[k] = 0;
                 }
-                if (hipMalloc(&s->d_spill[k], spill_set_bytes(c, px)) != hipSuccess) {
+                if (s->d_spill[k].alloc(spill_set_bytes(c, px)) != hipSuccess) {
                         (void)hipGetLastError();
-                        s->d_spill[k] = nullptr;
                         return VRT_OK;  // no compaction
                 }
                 s->spill_cap[k] = c;
                 s->spill_px[k] = px;
         }
         const size_t fb = ((size_t)s->spill_cap[k] * 4 + 255) & ~(size_t)255;
-        char *b = static_cast<char *>(s->d_spill[k]);
+        char *b = s->d_spill[k].as<char>();
         sq->ctr = reinterpret_cast<uint32_t *>(b);
         sq->fill[0] = reinterpret_cast<uint32_t *>(b + ctr_bytes);
         sq->fill[1] = reinterpret_cast<uint32_t *>(b + ctr_bytes + fb);
@@ -1771,9 +1696,9 @@ static int spill_setup(vrt_scene *s, int64_t rays, int64_t pixels, hipStream_t s
 // the set's event.
 static int spill_done(vrt_scene *s, int k, const SpillQueues &sq, hipStream_t st)
 {
-        HIPCHK(hipMemcpyAsync(s->h_spill + 8 * k, sq.ctr, 8 * sizeof(uint32_t), hipMemcpyDeviceToHost, st));
-        HIPCHK(hipEventRecord(s->spill_ev[k], st));
-        s->spill_live[k] = true;
+        HIPCHK(hipMemcpyAsync(s->h_spill.as<uint32_t>() + 8 * k, sq.ctr, 8 * sizeof(uint32_t), hipMemcpyDeviceToHost,
+                              st));
+        HIPCHK(s->spill_use[k].record(st));
         s->spill_stream[k] = st;
         return VRT_OK;
 }
@@ -1801,9 +1726,12 @@ static int secondary_launch(vrt_scene *s, const RenderParams &p, int spp, int ra
         }
         int waves = 0, units[8];
         s->spill_last = sq.nchunks > 0 ? set : -1;
+        SideLaunch side{};
+        if (set >= 0)
+                side = { s->spill_side[set].st, s->spill_side[set].fork, s->spill_side[set].join };
         const hipError_t e = launch_secondary(p, spp, rank, nranks, scene_res(s), d_prim, d_vis, s_hit, s_tri,
                                               s_vox, slot >= 0 ? &q : nullptr, st, &waves, units, &sq,
-                                              set >= 0 && s->spill_side[set].st ? &s->spill_side[set] : nullptr);
+                                              side.st ? &side : nullptr);
         if (set >= 0)
                 if (int rc = spill_done(s, set, sq, st))
                         return rc;
@@ -1821,15 +1749,13 @@ static int secondary_launch(vrt_scene *s, const RenderParams &p, int spp, int ra
 // user's stream waits for the previous user's (caller holds s->mu).
 static int ts_acquire(vrt_scene *s, int i, hipStream_t st)
 {
-        if (s->ts[i].live)
-                HIPCHK(hipStreamWaitEvent(st, s->ts[i].ev, 0));
+        HIPCHK(s->ts[i].use.wait(st));
         return VRT_OK;
 }
 
 static int ts_release(vrt_scene *s, int i, hipStream_t st)
 {
-        HIPCHK(hipEventRecord(s->ts[i].ev, st));
-        s->ts[i].live = true;
+        HIPCHK(s->ts[i].use.record(st));
         return VRT_OK;
 }
 
@@ -1879,9 +1805,9 @@ static int ensure_lm(vrt_scene *s, int i)
 {
         if (!s->ts[i].lm) {
                 const size_t n = s->nodes.size();
-                HIPCHK(hipMalloc(reinterpret_cast<void **>(&s->ts[i].lm), lm_set_bytes(n)));
+                HIPCHK(s->ts[i].lm.alloc(lm_set_bytes(n)));
                 const std::vector<float4> cells = cone_cells(s->nodes);
-                HIPCHK(hipMemcpy(reinterpret_cast<char *>(s->ts[i].lm) + n * (sizeof(LMRec) + sizeof(float4)) + 256,
+                HIPCHK(hipMemcpy(s->ts[i].lm.as<char>() + n * (sizeof(LMRec) + sizeof(float4)) + 256,
                                  cells.data(), cells.size() * sizeof(float4), hipMemcpyHostToDevice));
         }
         return VRT_OK;
@@ -1898,39 +1824,32 @@ static const uint32_t *deal_map(vrt_scene *s, int ntx, int nty, int nranks, int 
                 return nullptr;
         for (auto &m : s->dmaps)
                 if (m.ntx == ntx && m.nty == nty && m.nranks == nranks && m.rank == rank) {
-                        if (hipEventQuery(m.ev) != hipSuccess && hipStreamWaitEvent(st, m.ev, 0) != hipSuccess) {
+                        if (!m.built.done() && m.built.wait(st) != hipSuccess) {
                                 (void)hipGetLastError();
                                 return nullptr;
                         }
-                        return m.d;
+                        return m.d.as<uint32_t>();
                 }
         const int n = deal_count(tile_deal(ntx, nty, nranks), rank);
         if (n <= 0 || s->dmaps.size() >= kDealMaps)
                 return nullptr;
-        vrt_scene::DealMap m{ ntx, nty, nranks, rank, nullptr, nullptr };
-        if (hipMalloc(reinterpret_cast<void **>(&m.d), (size_t)n * sizeof(uint32_t)) != hipSuccess) {
-                (void)hipGetLastError();
-                return nullptr;
-        }
-        if (hipEventCreateWithFlags(&m.ev, hipEventDisableTiming) != hipSuccess ||
-            launch_deal_map(ntx, nty, nranks, rank, m.d, st) != hipSuccess || hipEventRecord(m.ev, st) != hipSuccess) {
-                (void)hipGetLastError();
-                // a launch that got as far as the stream finishes before the free
-                (void)hipStreamSynchronize(st);
-                if (m.ev)
-                        (void)hipEventDestroy(m.ev);
-                (void)hipFree(m.d);
-                return nullptr;
-        }
         try {
-                s->dmaps.push_back(m);
+                s->dmaps.reserve(kDealMaps);  // the push_back below cannot fail
         } catch (const std::bad_alloc &) {
-                (void)hipEventSynchronize(m.ev);
-                (void)hipEventDestroy(m.ev);
-                (void)hipFree(m.d);
                 return nullptr;
         }
-        return m.d;
+        vrt_scene::DealMap m{ ntx, nty, nranks, rank, {}, {} };
+        if (m.d.alloc((size_t)n * sizeof(uint32_t)) != hipSuccess || m.built.create() != hipSuccess ||
+            launch_deal_map(ntx, nty, nranks, rank, m.d.as<uint32_t>(), st) != hipSuccess ||
+            m.built.record(st) != hipSuccess) {
+                (void)hipGetLastError();
+                // a launch that got as far as the stream finishes before m frees the map
+                if (m.d)
+                        (void)hipStreamSynchronize(st);
+                return nullptr;
+        }
+        s->dmaps.push_back(std::move(m));
+        return s->dmaps.back().d.as<uint32_t>();
 }
 
 extern "C" int vrt_render_tiles_device(vrt_scene *s, const vrt_camera *cam,
@@ -2023,17 +1942,6 @@ extern "C" int vrt_rgbe_device(const float *d_img, int w, int h, int comp, uint8
         return VRT_OK;
 }
 
-namespace {
-struct DevBuf {
-        void *p = nullptr;
-        ~DevBuf()
-        {
-                if (p)
-                        (void)hipFree(p);
-        }
-};
-}  // namespace
-
 // memcpy of a large host range split over up to 4 threads (pinned staging
 // <-> the caller's pageable arrays: one core's memcpy is well below PCIe)
 void vrt::par_memcpy(void *dst, const void *src, size_t bytes)
@@ -2072,31 +1980,19 @@ static int render_to_host(vrt_scene *s, const vrt_camera *cam, const vrt_film *f
                 std::memset(rgb, 0, bytes);
                 return VRT_OK;
         }
-        if (!ho.st2) {
-                HIPCHK(hipStreamCreateWithFlags(&ho.st2, hipStreamNonBlocking));
-                HIPCHK(hipStreamCreateWithFlags(&ho.cp, hipStreamNonBlocking));
+        if (!ho.ev_j) {  // the last one made
+                HIPCHK(ho.st2.create());
+                HIPCHK(ho.cp.create());
                 for (int b = 0; b < kOutBands; ++b) {
-                        HIPCHK(hipEventCreateWithFlags(&ho.ev_r[b], hipEventDisableTiming));
-                        HIPCHK(hipEventCreateWithFlags(&ho.ev_c[b], hipEventDisableTiming));
+                        HIPCHK(ho.ev_r[b].create(hipEventDisableTiming));
+                        HIPCHK(ho.ev_c[b].create(hipEventDisableTiming));
                 }
-                HIPCHK(hipEventCreateWithFlags(&ho.ev_j, hipEventDisableTiming));
+                HIPCHK(ho.ev_j.create(hipEventDisableTiming));
         }
         if (ho.nx != nx || ho.ny != ny) {
-                if (ho.bytes < bytes) {
-                        HIPCHK(hipStreamSynchronize(ho.cp));
-                        if (ho.d_img)
-                                (void)hipFree(ho.d_img);
-                        if (ho.h_pin)
-                                (void)hipHostFree(ho.h_pin);
-                        ho.d_img = nullptr;
-                        ho.h_pin = nullptr;
-                        ho.bytes = 0;
-                        HIPCHK(hipMalloc(&ho.d_img, bytes));
-                        HIPCHK(hipHostMalloc(&ho.h_pin, bytes, hipHostMallocDefault));
-                        ho.bytes = bytes;
-                }
+                HIPCHK(ho.img.grow(bytes, ho.cp));  // the copy stream is the pair's last user
                 // pixels outside the tile grid are never written: zero once per film shape
-                HIPCHK(hipMemsetAsync(ho.d_img, 0, bytes, s->stream));
+                HIPCHK(hipMemsetAsync(ho.img.d, 0, bytes, s->stream));
                 ho.nx = nx;
                 ho.ny = ny;
         }
@@ -2115,7 +2011,7 @@ static int render_to_host(vrt_scene *s, const vrt_camera *cam, const vrt_film *f
                 p.tiles_this_rank = ntx * (r1 - r0);
                 p.sc.grid_div = nb > 1 ? 2 : 1;
                 p.image_layout = 1;
-                p.out = ho.d_img;
+                p.out = ho.img.d.as<float>();
                 if (int rc = render_launch(s, p, false, st))
                         return rc;
                 HIPCHK(hipEventRecord(ho.ev_r[b], st));
@@ -2123,8 +2019,7 @@ static int render_to_host(vrt_scene *s, const vrt_camera *cam, const vrt_film *f
                 // band b's rows (the last band also carries the rows below the grid)
                 off[b] = b == 0 ? 0 : (size_t)8 * r0 * nx * 12;
                 off[b + 1] = b + 1 == nb ? bytes : (size_t)8 * r1 * nx * 12;
-                HIPCHK(hipMemcpyAsync(reinterpret_cast<char *>(ho.h_pin) + off[b],
-                                      reinterpret_cast<const char *>(ho.d_img) + off[b], off[b + 1] - off[b],
+                HIPCHK(hipMemcpyAsync(ho.img.h.as<char>() + off[b], ho.img.d.as<char>() + off[b], off[b + 1] - off[b],
                                       hipMemcpyDeviceToHost, ho.cp));
                 HIPCHK(hipEventRecord(ho.ev_c[b], ho.cp));
         }
@@ -2144,8 +2039,7 @@ static int render_to_host(vrt_scene *s, const vrt_camera *cam, const vrt_film *f
                         const size_t n = off[b + 1] - off[b];
                         const size_t a = off[b] + ((n * j / nth) & ~(size_t)63);
                         const size_t e = j + 1 == nth ? off[b + 1] : off[b] + ((n * (j + 1) / nth) & ~(size_t)63);
-                        std::memcpy(reinterpret_cast<char *>(rgb) + a, reinterpret_cast<const char *>(ho.h_pin) + a,
-                                    e - a);
+                        std::memcpy(reinterpret_cast<char *>(rgb) + a, ho.img.h.as<char>() + a, e - a);
                 }
         };
         std::vector<std::thread> th;
@@ -2182,39 +2076,39 @@ extern "C" int vrt_render(vrt_scene *s, const vrt_camera *cam,
         if (want_cnt)
                 if (int rc = no_probe_scene(s, "vrt_render with instrumented counters"))
                         return rc;
-        DevBuf img, shit, stri, svox, srgb, scnt;
-        HIPCHK(hipMalloc(&img.p, npix * 3 * sizeof(float)));
-        HIPCHK(hipMemsetAsync(img.p, 0, npix * 3 * sizeof(float), s->stream));
+        DevMem img, shit, stri, svox, srgb, scnt;
+        HIPCHK(img.alloc(npix * 3 * sizeof(float)));
+        HIPCHK(hipMemsetAsync(img, 0, npix * 3 * sizeof(float), s->stream));
         RenderParams p;
         fill_render_params(s, cam, film, 0, 1, &p);
         p.sc.grid_div = 1;  // synchronous: one frame at a time, the whole chip
         p.image_layout = 1;
-        p.out = static_cast<float *>(img.p);
-        auto alloc_fill = [&](DevBuf &b, size_t bytes, int byte) -> hipError_t {
-                hipError_t e = hipMalloc(&b.p, bytes);
+        p.out = img.as<float>();
+        auto alloc_fill = [&](DevMem &b, size_t bytes, int byte) -> hipError_t {
+                hipError_t e = b.alloc(bytes);
                 if (e != hipSuccess)
                         return e;
-                return hipMemsetAsync(b.p, byte, bytes, s->stream);
+                return hipMemsetAsync(b, byte, bytes, s->stream);
         };
         if (samples && samples->hit) {
                 HIPCHK(alloc_fill(shit, ns * 4, 0));
-                p.so.hit = static_cast<int32_t *>(shit.p);
+                p.so.hit = shit.as<int32_t>();
         }
         if (samples && samples->tri) {
                 HIPCHK(alloc_fill(stri, ns * 4, 0xFF));
-                p.so.tri = static_cast<int32_t *>(stri.p);
+                p.so.tri = stri.as<int32_t>();
         }
         if (samples && samples->voxel) {
                 HIPCHK(alloc_fill(svox, ns * 4, 0xFF));
-                p.so.vox = static_cast<uint32_t *>(svox.p);
+                p.so.vox = svox.as<uint32_t>();
         }
         if (samples && samples->rgb) {
                 HIPCHK(alloc_fill(srgb, ns * 12, 0));
-                p.so.rgb = static_cast<float *>(srgb.p);
+                p.so.rgb = srgb.as<float>();
         }
         if (want_cnt) {
                 HIPCHK(alloc_fill(scnt, ns * 16, 0));
-                p.so.cnt = static_cast<uint32_t *>(scnt.p);
+                p.so.cnt = scnt.as<uint32_t>();
         }
         HIPCHK(hipEventRecord(s->ev0, s->stream));
         if (int rc = render_launch(s, p, want_cnt, s->stream))
@@ -2222,19 +2116,19 @@ extern "C" int vrt_render(vrt_scene *s, const vrt_camera *cam,
         HIPCHK(hipEventRecord(s->ev1, s->stream));
         s->timed = true;
         HIPCHK(hipStreamSynchronize(s->stream));
-        HIPCHK(hipMemcpy(rgb, img.p, npix * 3 * sizeof(float), hipMemcpyDeviceToHost));
+        HIPCHK(hipMemcpy(rgb, img, npix * 3 * sizeof(float), hipMemcpyDeviceToHost));
         if (p.so.hit)
-                HIPCHK(hipMemcpy(samples->hit, shit.p, ns * 4, hipMemcpyDeviceToHost));
+                HIPCHK(hipMemcpy(samples->hit, shit, ns * 4, hipMemcpyDeviceToHost));
         if (p.so.tri)
-                HIPCHK(hipMemcpy(samples->tri, stri.p, ns * 4, hipMemcpyDeviceToHost));
+                HIPCHK(hipMemcpy(samples->tri, stri, ns * 4, hipMemcpyDeviceToHost));
         if (p.so.vox)
-                HIPCHK(hipMemcpy(samples->voxel, svox.p, ns * 4, hipMemcpyDeviceToHost));
+                HIPCHK(hipMemcpy(samples->voxel, svox, ns * 4, hipMemcpyDeviceToHost));
         if (p.so.rgb)
-                HIPCHK(hipMemcpy(samples->rgb, srgb.p, ns * 12, hipMemcpyDeviceToHost));
+                HIPCHK(hipMemcpy(samples->rgb, srgb, ns * 12, hipMemcpyDeviceToHost));
         std::vector<uint32_t> cnt;
         if (want_cnt) {
                 cnt.resize(ns * 4);
-                HIPCHK(hipMemcpy(cnt.data(), scnt.p, ns * 16, hipMemcpyDeviceToHost));
+                HIPCHK(hipMemcpy(cnt.data(), scnt, ns * 16, hipMemcpyDeviceToHost));
                 if (samples && samples->counters)
                         std::memcpy(samples->counters, cnt.data(), ns * 16);
         }
@@ -2308,12 +2202,9 @@ extern "C" int vrt_scene_scratch_bytes(vrt_scene *s, int64_t *bytes, int64_t *sp
         for (int k = 0; k < 2; ++k)
                 if (s->d_spill[k])
                         sp += (int64_t)spill_set_bytes(s->spill_cap[k], s->spill_px[k]);
-        int64_t t = sp + (int64_t)s->light_bytes + (int64_t)s->ho.bytes + (int64_t)s->tb.cap;
-        for (const TraceSet &ts : s->ts) {
-                if (ts.lm)
-                        t += (int64_t)lm_set_bytes(s->nodes.size());
-                t += (int64_t)ts.rec_bytes;
-        }
+        int64_t t = sp + (int64_t)s->d_light.size() + (int64_t)s->ho.img.cap + (int64_t)s->tb.cap;
+        for (const TraceSet &ts : s->ts)
+                t += (int64_t)(ts.lm.size() + ts.rec.size());
         for (const auto &m : s->dmaps)  // the tabled multi-rank deals
                 t += (int64_t)deal_count(tile_deal(m.ntx, m.nty, m.nranks), m.rank) * (int64_t)sizeof(uint32_t);
         *bytes = t;
@@ -2334,7 +2225,7 @@ extern "C" int vrt_secondary_spill_counts(vrt_scene *s, int64_t counts[4])
         if (s->spill_last < 0 || !s->d_spill[s->spill_last])
                 return VRT_OK;
         HIPCHK(hipSetDevice(s->device));
-        HIPCHK(hipEventSynchronize(s->spill_ev[s->spill_last]));  // the set's last launch
+        HIPCHK(s->spill_use[s->spill_last].sync());  // the set's last launch
         std::vector<uint32_t> c((size_t)kSpillMaxRounds * kSpillCtrStride);
         HIPCHK(hipMemcpy(c.data(), s->d_spill[s->spill_last], c.size() * 4, hipMemcpyDeviceToHost));
         for (int r = 0; r < 4 && r < kSpillMaxRounds; ++r)
@@ -2354,7 +2245,7 @@ extern "C" int vrt_secondary_spill_stats(vrt_scene *s, int64_t stats[7])
         if (s->spill_last < 0 || !s->d_spill[s->spill_last])
                 return VRT_OK;
         HIPCHK(hipSetDevice(s->device));
-        HIPCHK(hipEventSynchronize(s->spill_ev[s->spill_last]));
+        HIPCHK(s->spill_use[s->spill_last].sync());
         uint32_t c[8];
         HIPCHK(hipMemcpy(c, s->d_spill[s->spill_last], sizeof c, hipMemcpyDeviceToHost));
         stats[0] = c[2];                     // records queued (spill_close)
@@ -2383,43 +2274,43 @@ extern "C" int vrt_render_secondary(vrt_scene *s, const vrt_camera *cam,
         const size_t npix = (size_t)film->nx * film->ny;
         const size_t ns = npix * (size_t)spp;
         const size_t narea = (size_t)(8 * (film->nx / 8)) * (8 * (film->ny / 8));
-        DevBuf dvis, dprim, dh, dt, dv;
-        HIPCHK(hipMalloc(&dvis.p, npix * 4));
-        HIPCHK(hipMemsetAsync(dvis.p, 0, npix * 4, s->stream));
-        HIPCHK(hipMalloc(&dprim.p, std::max<size_t>(1, narea) * 32));
+        DevMem dvis, dprim, dh, dt, dv;
+        HIPCHK(dvis.alloc(npix * 4));
+        HIPCHK(hipMemsetAsync(dvis, 0, npix * 4, s->stream));
+        HIPCHK(dprim.alloc(std::max<size_t>(1, narea) * 32));
         if (s_hit) {
-                HIPCHK(hipMalloc(&dh.p, ns * 4));
-                HIPCHK(hipMemsetAsync(dh.p, 0, ns * 4, s->stream));
+                HIPCHK(dh.alloc(ns * 4));
+                HIPCHK(hipMemsetAsync(dh, 0, ns * 4, s->stream));
         }
         if (s_tri) {
-                HIPCHK(hipMalloc(&dt.p, ns * 4));
-                HIPCHK(hipMemsetAsync(dt.p, 0xFF, ns * 4, s->stream));
+                HIPCHK(dt.alloc(ns * 4));
+                HIPCHK(hipMemsetAsync(dt, 0xFF, ns * 4, s->stream));
         }
         if (s_vox) {
-                HIPCHK(hipMalloc(&dv.p, ns * 4));
-                HIPCHK(hipMemsetAsync(dv.p, 0xFF, ns * 4, s->stream));
+                HIPCHK(dv.alloc(ns * 4));
+                HIPCHK(hipMemsetAsync(dv, 0xFF, ns * 4, s->stream));
         }
         RenderParams p;
         fill_render_params(s, cam, film, 0, 1, &p);
         HIPCHK(hipEventRecord(s->ev0, s->stream));
-        if (int rc = secondary_launch(s, p, spp, 0, 1, static_cast<float *>(dprim.p), static_cast<float *>(dvis.p),
-                                      static_cast<int32_t *>(dh.p), static_cast<int32_t *>(dt.p),
-                                      static_cast<uint32_t *>(dv.p), s->stream))
+        if (int rc = secondary_launch(s, p, spp, 0, 1, dprim.as<float>(), dvis.as<float>(),
+                                      dh.as<int32_t>(), dt.as<int32_t>(),
+                                      dv.as<uint32_t>(), s->stream))
                 return rc;
         HIPCHK(hipEventRecord(s->ev1, s->stream));
         s->timed = true;
         HIPCHK(hipStreamSynchronize(s->stream));
-        HIPCHK(hipMemcpy(vis, dvis.p, npix * 4, hipMemcpyDeviceToHost));
+        HIPCHK(hipMemcpy(vis, dvis, npix * 4, hipMemcpyDeviceToHost));
         if (s_hit)
-                HIPCHK(hipMemcpy(s_hit, dh.p, ns * 4, hipMemcpyDeviceToHost));
+                HIPCHK(hipMemcpy(s_hit, dh, ns * 4, hipMemcpyDeviceToHost));
         if (s_tri)
-                HIPCHK(hipMemcpy(s_tri, dt.p, ns * 4, hipMemcpyDeviceToHost));
+                HIPCHK(hipMemcpy(s_tri, dt, ns * 4, hipMemcpyDeviceToHost));
         if (s_vox)
-                HIPCHK(hipMemcpy(s_vox, dv.p, ns * 4, hipMemcpyDeviceToHost));
+                HIPCHK(hipMemcpy(s_vox, dv, ns * 4, hipMemcpyDeviceToHost));
         if (rays) {
                 std::vector<float> prim(narea * 8);
                 if (narea)
-                        HIPCHK(hipMemcpy(prim.data(), dprim.p, narea * 32, hipMemcpyDeviceToHost));
+                        HIPCHK(hipMemcpy(prim.data(), dprim, narea * 32, hipMemcpyDeviceToHost));
                 int64_t hits = 0;
                 for (size_t i = 0; i < narea; ++i)
                         hits += prim[8 * i] != 0.f;
@@ -2470,20 +2361,12 @@ extern "C" int vrt_scene_min_voxel(const vrt_scene *s, int levels, float *res)
 
 static hipError_t ensure_light_scratch(vrt_scene *s, size_t bytes)
 {
-        if (s->light_bytes >= bytes)
+        if (s->d_light.size() >= bytes)
                 return hipSuccess;
-        if (s->d_light) {
-                hipError_t e = hipStreamSynchronize(s->stream);
-                if (e != hipSuccess)
+        if (s->d_light)  // used on the scene's stream only
+                if (hipError_t e = hipStreamSynchronize(s->stream))
                         return e;
-                (void)hipFree(s->d_light);
-                s->d_light = nullptr;
-                s->light_bytes = 0;
-        }
-        hipError_t e = hipMalloc(&s->d_light, bytes);
-        if (e == hipSuccess)
-                s->light_bytes = bytes;
-        return e;
+        return s->d_light.alloc(bytes);
 }
 
 // The light pass + filter of VRT/main.cc:75-100 on the scene's stream
@@ -2502,7 +2385,7 @@ static int lightmap_enqueue(vrt_scene *s, int set, const vrt_camera *light_cam, 
         // one block: light map, cone-descent records, finiteness flag
         if (int rc = ensure_lm(s, set))
                 return rc;
-        LMRec *d_lm = s->ts[set].lm;
+        LMRec *d_lm = s->ts[set].lm.as<LMRec>();
         float4 *d_cc = reinterpret_cast<float4 *>(d_lm + nnodes);
         uint32_t *d_bad = reinterpret_cast<uint32_t *>(d_cc + nnodes);
         if (int rc = ts_acquire(s, set, s->stream))  // a trace render may still read this set
@@ -2523,7 +2406,7 @@ static int lightmap_enqueue(vrt_scene *s, int set, const vrt_camera *light_cam, 
         const size_t bend = align_up((size_t)nnodes * 4);
         const size_t need = 2 * b8 + 2 * b4 + b24 + align_up(sort_bytes) + 256 + bseg + bend;
         HIPCHK(ensure_light_scratch(s, need));
-        char *base = static_cast<char *>(s->d_light);
+        char *base = s->d_light.as<char>();
         uint64_t *k_in = reinterpret_cast<uint64_t *>(base);
         uint64_t *k_out = reinterpret_cast<uint64_t *>(base + b8);
         uint32_t *v_in = reinterpret_cast<uint32_t *>(base + 2 * b8);
@@ -2641,8 +2524,7 @@ extern "C" int vrt_lightmap_nodes(vrt_scene *s, uint64_t *key, float *coverage, 
         // the set may be filled on the scene stream and read on callers'
         // streams (trace frames): its last user's event covers both
         HIPCHK(hipStreamSynchronize(s->stream));
-        if (s->ts[s->lm_cur].live)
-                HIPCHK(hipEventSynchronize(s->ts[s->lm_cur].ev));
+        HIPCHK(s->ts[s->lm_cur].use.sync());
         HIPCHK(hipMemcpy(lm.data(), s->ts[s->lm_cur].lm, n * sizeof(LMRec), hipMemcpyDeviceToHost));
         for (size_t l = 0; l + 1 < s->level_begin.size(); ++l)
                 for (int64_t i = s->level_begin[l]; i < s->level_begin[l + 1]; ++i) {
@@ -2679,25 +2561,19 @@ static int trace_scratch_n(vrt_scene *s, int set, const TraceParams &tp, size_t 
         // records, its deferred-sample count (512 B) and list
         const size_t head = (size_t)kConeSteps * 16 + 256;
         const size_t need = head + nslots * 64 + 512 + nslots * 4;
-        if (t.rec_bytes < need) {
-                if (t.rec) {
-                        // every user of the set's scratch is ordered by its event
-                        // (ts_acquire waits for it, ts_release records it)
-                        if (t.live)
-                                HIPCHK(hipEventSynchronize(t.ev));
-                        (void)hipFree(t.rec);
-                        t.rec = nullptr;
-                        t.rec_bytes = 0;
-                }
-                HIPCHK(hipMalloc(&t.rec, need));
-                t.rec_bytes = need;
+        if (t.rec.size() < need) {
+                // every user of the set's scratch is ordered by its event
+                // (ts_acquire waits for it, ts_release records it)
+                if (t.rec)
+                        HIPCHK(t.use.sync());
+                HIPCHK(t.rec.alloc(need));
                 t.steps_key[0] = t.steps_key[1] = -1.f;
         }
         // the step table depends on mindist and maxdist only: rebuilt when
         // they change (the set's users are ordered by its event); the key is
         // committed only once k_cone_steps is enqueued (steps_commit)
         out->build_steps = !(t.steps_key[0] == tp.mindist && t.steps_key[1] == tp.maxdist);
-        char *b = static_cast<char *>(t.rec);
+        char *b = t.rec.as<char>();
         out->steps = reinterpret_cast<float4 *>(b);
         out->nsteps = reinterpret_cast<int *>(b + (size_t)kConeSteps * 16);
         out->rec = reinterpret_cast<float4 *>(b + head);
@@ -2790,8 +2666,8 @@ static void fill_trace_light(vrt_scene *s, int set, float min_voxel, TraceParams
 {
         if (!(min_voxel > 0.f))
                 vrt_scene_min_voxel(s, 0, &min_voxel);
-        tp->lm = s->ts[set].lm;
-        tp->cc = reinterpret_cast<const float4 *>(s->ts[set].lm + s->nodes.size());
+        tp->lm = s->ts[set].lm.as<LMRec>();
+        tp->cc = reinterpret_cast<const float4 *>(tp->lm + s->nodes.size());
         tp->lm_bad = reinterpret_cast<const uint32_t *>(tp->cc + s->nodes.size());
         tp->cells = reinterpret_cast<const float4 *>(reinterpret_cast<const char *>(tp->lm_bad) + 256);
         // float mindist = 1.414f * min_voxel_size; maxdist = length(root.aabb.size())
@@ -2875,11 +2751,44 @@ static int64_t batch_chunk()
         return (g_test_flags.load() & VRT_TEST_SMALL_BATCH_CHUNK) ? 200 : kBatchChunk;
 }
 
-// One batched call on stream st over device arrays (caller holds s->mu, the
-// device is set, a light map exists): the current set's light map and step
-// table, taken and released through the set's event like a frame.  io.rays
-// set: trace(); io.isects set: cone_trace.
-static int batch_enqueue(vrt_scene *s, const BatchIO &io, float min_voxel, hipStream_t st)
+// The checks of the six batched calls (vrt_trace_batch, vrt_cone_trace_batch,
+// vrt_probe_gather and their _device forms), in one order: a null scene or n
+// < 0; n == 0 is VRT_OK whatever the scene is (*empty: nothing to do); a
+// host-only scene; null pointers (ptrs: the call's are all set); the gather's
+// point count (points set); the cone step; then, under the scene's lock, the
+// light map.  VRT_OK and not *empty: *lk holds s->mu, a light map exists and
+// the device is set.
+static int batch_begin(vrt_scene *s, int64_t n, bool ptrs, const float *points, int npoints, float min_voxel,
+                       std::unique_lock<std::mutex> *lk, bool *empty)
+{
+        *empty = n == 0;
+        if (!s || n < 0)
+                return fail(VRT_E_INVALID, "bad argument");
+        if (n == 0)
+                return VRT_OK;
+        if (need_device(s))
+                return VRT_E_NODEVICE;
+        if (!ptrs)
+                return fail(VRT_E_INVALID, "null argument");
+        if (points && (npoints < 1 || npoints > kProbeMaxPoints))
+                return fail(VRT_E_INVALID, "bad argument: %d points (1..%d)", npoints, kProbeMaxPoints);
+        if (int rc = trace_ok(s, min_voxel))
+                return rc;
+        *lk = std::unique_lock<std::mutex>(s->mu);
+        if (s->lm_cur < 0)
+                return fail(VRT_E_INVALID, "no light map: call vrt_lightmap_build first");
+        HIPCHK(hipSetDevice(s->device));
+        return VRT_OK;
+}
+
+// One launch on stream st over the current trace set (caller holds s->mu,
+// the device is set, a light map exists): the set's light map and step table
+// and `nslots` records of its block behind the first rec_skip, taken and
+// released through the set's event like a frame -- after a failed launch too.
+// launch(tp) enqueues the work; `what` names it in the message.
+template <class Launch>
+static int trace_set_launch(vrt_scene *s, float min_voxel, size_t rec_skip, size_t nslots, const char *what,
+                            hipStream_t st, Launch launch)
 {
         const int set = s->lm_cur;
         TraceParams tp0, tp;
@@ -2887,19 +2796,16 @@ static int batch_enqueue(vrt_scene *s, const BatchIO &io, float min_voxel, hipSt
         tp0.r.sc = s->dev;
         tp0.r.test_flags = g_test_flags.load();
         fill_trace_light(s, set, min_voxel, &tp0);
-        const int64_t chunk = batch_chunk();
-        const size_t nslots = io.rays ? (size_t)std::min(io.n, chunk) : 0;
-        if (int rc = trace_scratch_n(s, set, tp0, nslots, &tp))
+        if (int rc = trace_scratch_n(s, set, tp0, rec_skip + nslots, &tp))
                 return rc;
+        tp.rec += 4 * rec_skip;
         if (int rc = ts_acquire(s, set, st))
                 return rc;
         (void)hipGetLastError();  // a leftover error of an earlier call is not this launch's
-        // trace() marches with even_invisible = true: the mixed march on a probe scene
-        const ProbeDev *pd = s->probes.empty() ? nullptr : &s->pdev;
-        const hipError_t e = io.rays ? launch_trace_batch(tp, io, chunk, st, pd) : launch_cones_batch(tp, io, st);
+        const hipError_t e = launch(tp);
         if (e != hipSuccess) {
                 (void)ts_release(s, set, st);
-                return fail(VRT_E_DEVICE, "batched trace launch failed: %s", hipGetErrorString(e));
+                return fail(VRT_E_DEVICE, "%s launch failed: %s", what, hipGetErrorString(e));
         }
         if (tp.build_steps) {  // k_cone_steps is enqueued (steps_commit)
                 s->ts[set].steps_key[0] = tp.mindist;
@@ -2908,38 +2814,76 @@ static int batch_enqueue(vrt_scene *s, const BatchIO &io, float min_voxel, hipSt
         return ts_release(s, set, st);
 }
 
-// n == 0 is VRT_OK whatever the scene is (*empty: nothing to do); only then
-// does a host-only scene count
-static int batch_args_ok(vrt_scene *s, const void *in, int64_t n, const void *rgb, bool *empty)
+// Host arrays chunk by chunk through the staging s->tb (caller holds s->mu):
+// m = min(n, chunk) elements of `in` (in_sz bytes each) at its front, behind
+// them the output arrays that are laid out (m elements each, never more than
+// one chunk).  Per chunk of c elements: stage in, enqueue(d_in, d_out, c) on
+// the scene's stream, the outputs back, one host sync, host_step(h_out, c),
+// and the caller's arrays are filled.  d_out[k] / h_out[k]: output k on the
+// device / in the pinned copy, null when it is not laid out.
+struct ChunkOut {
+        void *host;   // the caller's array, or null
+        size_t sz;    // bytes per element
+        bool staged;  // laid out: the caller wants it, or the host step reads it
+};
+constexpr int kChunkOuts = 5;
+template <class Enqueue, class HostStep>
+static int chunked_host(vrt_scene *s, const void *in, size_t in_sz, int64_t n, int64_t chunk, const ChunkOut *out,
+                        int nout, Enqueue enqueue, HostStep host_step)
 {
-        *empty = false;
-        if (!s || n < 0)
-                return fail(VRT_E_INVALID, "bad argument");
-        if (n == 0) {
-                *empty = true;
-                return VRT_OK;
+        const int64_t m = std::min(n, chunk);
+        const size_t in_bytes = (size_t)m * in_sz;
+        size_t off[kChunkOuts], end = in_bytes;
+        for (int k = 0; k < nout; ++k) {
+                off[k] = end;
+                end += out[k].staged ? (size_t)m * out[k].sz : 0;
         }
-        if (need_device(s))
-                return VRT_E_NODEVICE;
-        if (!in || !rgb)
-                return fail(VRT_E_INVALID, "null argument");
+        HIPCHK(s->tb.grow(end, s->stream));
+        char *d = s->tb.d.as<char>(), *h = s->tb.h.as<char>();
+        char *d_out[kChunkOuts], *h_out[kChunkOuts];
+        for (int k = 0; k < nout; ++k) {
+                d_out[k] = out[k].staged ? d + off[k] : nullptr;
+                h_out[k] = out[k].staged ? h + off[k] : nullptr;
+        }
+        for (int64_t b = 0; b < n; b += m) {
+                const int64_t c = std::min(m, n - b);
+                par_memcpy(h, static_cast<const char *>(in) + (size_t)b * in_sz, (size_t)c * in_sz);
+                HIPCHK(hipMemcpyAsync(d, h, (size_t)c * in_sz, hipMemcpyHostToDevice, s->stream));
+                if (int rc = enqueue(d, d_out, c))
+                        return rc;
+                HIPCHK(hipMemcpyAsync(h + in_bytes, d + in_bytes, end - in_bytes, hipMemcpyDeviceToHost, s->stream));
+                HIPCHK(hipStreamSynchronize(s->stream));
+                if (int rc = host_step(h_out, c))
+                        return rc;
+                for (int k = 0; k < nout; ++k)
+                        if (out[k].host)
+                                par_memcpy(static_cast<char *>(out[k].host) + (size_t)b * out[k].sz, h_out[k],
+                                           (size_t)c * out[k].sz);
+        }
         return VRT_OK;
+}
+
+// One batched trace() (io.rays set) or cone_trace (io.isects set) over device
+// arrays on stream st.  trace() marches with even_invisible = true: the mixed
+// march on a probe scene.
+static int batch_enqueue(vrt_scene *s, const BatchIO &io, float min_voxel, hipStream_t st)
+{
+        const int64_t chunk = batch_chunk();
+        const ProbeDev *pd = s->probes.empty() ? nullptr : &s->pdev;
+        return trace_set_launch(s, min_voxel, 0, io.rays ? (size_t)std::min(io.n, chunk) : 0, "batched trace", st,
+                                [&](const TraceParams &tp) {
+                                        return io.rays ? launch_trace_batch(tp, io, chunk, st, pd)
+                                                       : launch_cones_batch(tp, io, st);
+                                });
 }
 
 extern "C" int vrt_trace_batch_device(vrt_scene *s, const vrt_ray *d_rays, int64_t n, float min_voxel,
                                       float *d_rgb, const vrt_trace_parts *d_parts, void *stream)
 {
+        std::unique_lock<std::mutex> lk;
         bool empty;
-        if (int rc = batch_args_ok(s, d_rays, n, d_rgb, &empty))
+        if (int rc = batch_begin(s, n, d_rays && d_rgb, nullptr, 0, min_voxel, &lk, &empty); rc || empty)
                 return rc;
-        if (empty)
-                return VRT_OK;
-        if (int rc = trace_ok(s, min_voxel))
-                return rc;
-        std::lock_guard<std::mutex> lk(s->mu);
-        if (s->lm_cur < 0)
-                return fail(VRT_E_INVALID, "no light map: call vrt_lightmap_build first");
-        HIPCHK(hipSetDevice(s->device));
         BatchIO io{};
         io.rays = reinterpret_cast<const float *>(d_rays);
         io.n = n;
@@ -2956,17 +2900,10 @@ extern "C" int vrt_trace_batch_device(vrt_scene *s, const vrt_ray *d_rays, int64
 extern "C" int vrt_cone_trace_batch_device(vrt_scene *s, const vrt_isect *d_isects, int64_t n, float min_voxel,
                                            float *d_rgb, void *stream)
 {
+        std::unique_lock<std::mutex> lk;
         bool empty;
-        if (int rc = batch_args_ok(s, d_isects, n, d_rgb, &empty))
+        if (int rc = batch_begin(s, n, d_isects && d_rgb, nullptr, 0, min_voxel, &lk, &empty); rc || empty)
                 return rc;
-        if (empty)
-                return VRT_OK;
-        if (int rc = trace_ok(s, min_voxel))
-                return rc;
-        std::lock_guard<std::mutex> lk(s->mu);
-        if (s->lm_cur < 0)
-                return fail(VRT_E_INVALID, "no light map: call vrt_lightmap_build first");
-        HIPCHK(hipSetDevice(s->device));
         BatchIO io{};
         io.isects = reinterpret_cast<const float *>(d_isects);
         io.n = n;
@@ -2974,103 +2911,69 @@ extern "C" int vrt_cone_trace_batch_device(vrt_scene *s, const vrt_isect *d_isec
         return batch_enqueue(s, io, min_voxel, static_cast<hipStream_t>(stream));
 }
 
-// Host arrays: chunk by chunk through the staging s->tb (in: `in_sz` bytes
-// per element at offset 0; out: the requested arrays behind it, out_sz[k]
-// bytes per element each), one host sync per chunk (caller holds s->mu).
 static void probe_shade(const vrt_scene *s, const vrt_hit *hits, int64_t n, float *rgb, float *albedo);
 static int fetch_probe_sgs(vrt_scene *s);
 
+// trace() (rays) or cone_trace over host arrays; out: rgb, hits, indirect,
+// direct, albedo (caller holds s->mu)
 static int batch_host(vrt_scene *s, const void *in, size_t in_sz, bool rays, int64_t n, float min_voxel,
-                      void *const out[5], const size_t out_sz[5])
+                      void *const out[5])
 {
-        const int64_t m = std::min(n, batch_chunk());
         // trace() on a probe scene: the chunk's hit records come back
         // whether or not the caller asked for them, and the rays that ended
         // on a probe get their colour here (LightProbe::eval, the C
         // library's expf) before the chunk is handed out
         const bool shade = rays && !s->probes.empty();
-        bool want[5];
-        for (int k = 0; k < 5; ++k)
-                want[k] = out[k] != nullptr || (k == 1 && shade);
-        size_t per = in_sz;
-        for (int k = 0; k < 5; ++k)
-                per += want[k] ? out_sz[k] : 0;
-        HIPCHK(s->tb.grow((size_t)m * per, s->stream));
-        char *d = static_cast<char *>(s->tb.d), *h = static_cast<char *>(s->tb.h);
-        for (int64_t b = 0; b < n; b += m) {
-                const int64_t c = std::min(m, n - b);
-                par_memcpy(h, static_cast<const char *>(in) + (size_t)b * in_sz, (size_t)c * in_sz);
-                HIPCHK(hipMemcpyAsync(d, h, (size_t)c * in_sz, hipMemcpyHostToDevice, s->stream));
-                BatchIO io{};
-                (rays ? io.rays : io.isects) = reinterpret_cast<const float *>(d);
-                io.n = c;
-                size_t off = (size_t)m * in_sz, o5[5] = {};
-                for (int k = 0; k < 5; ++k) {
-                        o5[k] = off;
-                        off += want[k] ? (size_t)m * out_sz[k] : 0;
-                }
-                io.rgb = reinterpret_cast<float *>(d + o5[0]);
-                io.hits = want[1] ? reinterpret_cast<uint32_t *>(d + o5[1]) : nullptr;
-                io.indirect = out[2] ? reinterpret_cast<float *>(d + o5[2]) : nullptr;
-                io.direct = out[3] ? reinterpret_cast<float *>(d + o5[3]) : nullptr;
-                io.albedo = out[4] ? reinterpret_cast<float *>(d + o5[4]) : nullptr;
-                if (int rc = batch_enqueue(s, io, min_voxel, s->stream))
-                        return rc;
-                HIPCHK(hipMemcpyAsync(h + (size_t)m * in_sz, d + (size_t)m * in_sz, off - (size_t)m * in_sz,
-                                      hipMemcpyDeviceToHost, s->stream));
-                HIPCHK(hipStreamSynchronize(s->stream));
-                if (shade) {
+        const ChunkOut co[5] = { { out[0], 12, true },
+                                 { out[1], sizeof(vrt_hit), out[1] || shade },
+                                 { out[2], 12, out[2] != nullptr },
+                                 { out[3], 12, out[3] != nullptr },
+                                 { out[4], 12, out[4] != nullptr } };
+        return chunked_host(
+                s, in, in_sz, n, batch_chunk(), co, 5,
+                [&](char *d_in, char *const *d, int64_t c) {
+                        BatchIO io{};
+                        (rays ? io.rays : io.isects) = reinterpret_cast<const float *>(d_in);
+                        io.n = c;
+                        io.rgb = reinterpret_cast<float *>(d[0]);
+                        io.hits = reinterpret_cast<uint32_t *>(d[1]);
+                        io.indirect = reinterpret_cast<float *>(d[2]);
+                        io.direct = reinterpret_cast<float *>(d[3]);
+                        io.albedo = reinterpret_cast<float *>(d[4]);
+                        return batch_enqueue(s, io, min_voxel, s->stream);
+                },
+                [&](char *const *h, int64_t c) {
+                        if (!shade)
+                                return (int)VRT_OK;
                         if (int rc = fetch_probe_sgs(s))  // a device gather may hold the latest SGs
                                 return rc;
-                        probe_shade(s, reinterpret_cast<const vrt_hit *>(h + o5[1]), c,
-                                    reinterpret_cast<float *>(h + o5[0]),
-                                    out[4] ? reinterpret_cast<float *>(h + o5[4]) : nullptr);
-                }
-                for (int k = 0; k < 5; ++k)
-                        if (out[k])
-                                par_memcpy(static_cast<char *>(out[k]) + (size_t)b * out_sz[k], h + o5[k],
-                                           (size_t)c * out_sz[k]);
-        }
-        return VRT_OK;
+                        probe_shade(s, reinterpret_cast<const vrt_hit *>(h[1]), c, reinterpret_cast<float *>(h[0]),
+                                    reinterpret_cast<float *>(h[4]));
+                        return (int)VRT_OK;
+                });
 }
 
 extern "C" int vrt_trace_batch(vrt_scene *s, const vrt_ray *rays, int64_t n, float min_voxel, float *rgb,
                                const vrt_trace_parts *parts)
 {
         static_assert(sizeof(vrt_isect) == 24, "vrt_isect layout");
+        std::unique_lock<std::mutex> lk;
         bool empty;
-        if (int rc = batch_args_ok(s, rays, n, rgb, &empty))
+        if (int rc = batch_begin(s, n, rays && rgb, nullptr, 0, min_voxel, &lk, &empty); rc || empty)
                 return rc;
-        if (empty)
-                return VRT_OK;
-        if (int rc = trace_ok(s, min_voxel))
-                return rc;
-        std::lock_guard<std::mutex> lk(s->mu);
-        if (s->lm_cur < 0)
-                return fail(VRT_E_INVALID, "no light map: call vrt_lightmap_build first");
-        HIPCHK(hipSetDevice(s->device));
         void *const out[5] = { rgb, parts ? parts->hits : nullptr, parts ? parts->indirect : nullptr,
                                parts ? parts->direct : nullptr, parts ? parts->albedo : nullptr };
-        const size_t out_sz[5] = { 12, sizeof(vrt_hit), 12, 12, 12 };
-        return batch_host(s, rays, sizeof(vrt_ray), true, n, min_voxel, out, out_sz);
+        return batch_host(s, rays, sizeof(vrt_ray), true, n, min_voxel, out);
 }
 
 extern "C" int vrt_cone_trace_batch(vrt_scene *s, const vrt_isect *isects, int64_t n, float min_voxel, float *rgb)
 {
+        std::unique_lock<std::mutex> lk;
         bool empty;
-        if (int rc = batch_args_ok(s, isects, n, rgb, &empty))
+        if (int rc = batch_begin(s, n, isects && rgb, nullptr, 0, min_voxel, &lk, &empty); rc || empty)
                 return rc;
-        if (empty)
-                return VRT_OK;
-        if (int rc = trace_ok(s, min_voxel))
-                return rc;
-        std::lock_guard<std::mutex> lk(s->mu);
-        if (s->lm_cur < 0)
-                return fail(VRT_E_INVALID, "no light map: call vrt_lightmap_build first");
-        HIPCHK(hipSetDevice(s->device));
         void *const out[5] = { rgb, nullptr, nullptr, nullptr, nullptr };
-        const size_t out_sz[5] = { 12, sizeof(vrt_hit), 12, 12, 12 };
-        return batch_host(s, isects, sizeof(vrt_isect), false, n, min_voxel, out, out_sz);
+        return batch_host(s, isects, sizeof(vrt_isect), false, n, min_voxel, out);
 }
 
 // ---- light probes (gi::LightProbe, gi::SG; VRT/voxel_octree.cc:497-632) ----
@@ -3162,63 +3065,22 @@ static int64_t probe_chunk(int npoints)
         return std::max<int64_t>(1, kBatchChunk / ((int64_t)kProbeSGs * npoints));
 }
 
-// One gather on stream st over device arrays (caller holds s->mu, the device
-// is set, a light map exists), as batch_enqueue: the current set's light
-// map, step table and record block, taken and released through its event.
-// rec_skip: records at the front of the set's block that belong to a frame in
-// flight (vrt_trace_frame_probes_device: the view's primary records, which the
-// cones + film pass reads after this gather); the gather's own follow them.
+// One gather on stream st over device arrays, as batch_enqueue.  rec_skip:
+// records at the front of the set's block that belong to a frame in flight
+// (vrt_trace_frame_probes_device: the view's primary records, which the cones
+// + film pass reads after this gather); the gather's own follow them.
 static int probe_enqueue(vrt_scene *s, const ProbeIO &io0, const float *host_points, float min_voxel,
                          hipStream_t st, size_t rec_skip = 0)
 {
-        const int set = s->lm_cur;
-        TraceParams tp0, tp;
-        std::memset(&tp0, 0, sizeof tp0);
-        tp0.r.sc = s->dev;
-        tp0.r.test_flags = g_test_flags.load();
-        fill_trace_light(s, set, min_voxel, &tp0);
         ProbeIO io = io0;
         io.res = min_voxel;
         if (!(io.res > 0.f))
                 vrt_scene_min_voxel(s, 0, &io.res);
         const int64_t chunk = probe_chunk(io.npoints);
-        const size_t nslots = (size_t)std::min(io.n, chunk) * kProbeSGs * io.npoints;
-        if (int rc = trace_scratch_n(s, set, tp0, rec_skip + nslots, &tp))
-                return rc;
-        tp.rec += 4 * rec_skip;
-        if (int rc = ts_acquire(s, set, st))
-                return rc;
-        (void)hipGetLastError();  // a leftover error of an earlier call is not this launch's
-        const hipError_t e = launch_probe_gather(tp, io, host_points, chunk, st);
-        if (e != hipSuccess) {
-                (void)ts_release(s, set, st);
-                return fail(VRT_E_DEVICE, "probe gather launch failed: %s", hipGetErrorString(e));
-        }
-        if (tp.build_steps) {  // k_cone_steps is enqueued (steps_commit)
-                s->ts[set].steps_key[0] = tp.mindist;
-                s->ts[set].steps_key[1] = tp.maxdist;
-        }
-        return ts_release(s, set, st);
-}
-
-// the arguments both variants share; *empty: n == 0, nothing to do
-static int probe_args_ok(vrt_scene *s, const void *probes, int64_t n, const float *light_color,
-                         const float *points, int npoints, const void *sgs, bool *empty)
-{
-        *empty = false;
-        if (!s || n < 0)
-                return fail(VRT_E_INVALID, "bad argument");
-        if (n == 0) {
-                *empty = true;
-                return VRT_OK;
-        }
-        if (need_device(s))
-                return VRT_E_NODEVICE;
-        if (!probes || !light_color || !sgs)
-                return fail(VRT_E_INVALID, "null argument");
-        if (points && (npoints < 1 || npoints > kProbeMaxPoints))
-                return fail(VRT_E_INVALID, "bad argument: %d points (1..%d)", npoints, kProbeMaxPoints);
-        return VRT_OK;
+        return trace_set_launch(s, min_voxel, rec_skip, (size_t)std::min(io.n, chunk) * kProbeSGs * io.npoints,
+                                "probe gather", st, [&](const TraceParams &tp) {
+                                        return launch_probe_gather(tp, io, host_points, chunk, st);
+                                });
 }
 
 // the reference's own points (every LightProbe draws the same 100)
@@ -3236,17 +3098,11 @@ extern "C" int vrt_probe_gather_device(vrt_scene *s, const vrt_probe *d_probes, 
                                        const float light_color[3], const float *points, int npoints,
                                        vrt_sg *d_sgs, float *d_terms, void *stream)
 {
+        std::unique_lock<std::mutex> lk;
         bool empty;
-        if (int rc = probe_args_ok(s, d_probes, n, light_color, points, npoints, d_sgs, &empty))
+        if (int rc = batch_begin(s, n, d_probes && light_color && d_sgs, points, npoints, min_voxel, &lk, &empty);
+            rc || empty)
                 return rc;
-        if (empty)
-                return VRT_OK;
-        if (int rc = trace_ok(s, min_voxel))
-                return rc;
-        std::lock_guard<std::mutex> lk(s->mu);
-        if (s->lm_cur < 0)
-                return fail(VRT_E_INVALID, "no light map: call vrt_lightmap_build first");
-        HIPCHK(hipSetDevice(s->device));
         ProbeIO io{};
         io.probes = reinterpret_cast<const float *>(d_probes);
         io.n = n;
@@ -3259,52 +3115,33 @@ extern "C" int vrt_probe_gather_device(vrt_scene *s, const vrt_probe *d_probes, 
 }
 
 // Host arrays: chunk by chunk through the batched trace's staging (one
-// chunk's probes, SGs and terms), one host sync per chunk.
+// chunk's probes, SGs and terms).
 extern "C" int vrt_probe_gather(vrt_scene *s, const vrt_probe *probes, int64_t n, float min_voxel,
                                 const float light_color[3], const float *points, int npoints, vrt_sg *sgs,
                                 float *terms)
 {
+        std::unique_lock<std::mutex> lk;
         bool empty;
-        if (int rc = probe_args_ok(s, probes, n, light_color, points, npoints, sgs, &empty))
+        if (int rc = batch_begin(s, n, probes && light_color && sgs, points, npoints, min_voxel, &lk, &empty);
+            rc || empty)
                 return rc;
-        if (empty)
-                return VRT_OK;
-        if (int rc = trace_ok(s, min_voxel))
-                return rc;
-        std::lock_guard<std::mutex> lk(s->mu);
-        if (s->lm_cur < 0)
-                return fail(VRT_E_INVALID, "no light map: call vrt_lightmap_build first");
-        HIPCHK(hipSetDevice(s->device));
         const int np = points ? npoints : 100;
         const float *pts = points ? points : probe_default_points();
-        const int64_t m = std::min(n, probe_chunk(np));
-        const size_t sg_sz = (size_t)kProbeSGs * sizeof(vrt_sg), tm_sz = terms ? (size_t)kProbeSGs * np * 12 : 0;
-        const size_t o_sg = (size_t)m * sizeof(vrt_probe), o_tm = o_sg + (size_t)m * sg_sz;
-        HIPCHK(s->tb.grow(o_tm + (size_t)m * tm_sz, s->stream));
-        char *d = static_cast<char *>(s->tb.d), *h = static_cast<char *>(s->tb.h);
-        for (int64_t b = 0; b < n; b += m) {
-                const int64_t c = std::min(m, n - b);
-                std::memcpy(h, probes + b, (size_t)c * sizeof(vrt_probe));
-                HIPCHK(hipMemcpyAsync(d, h, (size_t)c * sizeof(vrt_probe), hipMemcpyHostToDevice, s->stream));
-                ProbeIO io{};
-                io.probes = reinterpret_cast<const float *>(d);
-                io.n = c;
-                io.npoints = np;
-                std::memcpy(io.light, light_color, sizeof io.light);
-                io.sgs = reinterpret_cast<float *>(d + o_sg);
-                io.terms = terms ? reinterpret_cast<float *>(d + o_tm) : nullptr;
-                if (int rc = probe_enqueue(s, io, pts, min_voxel, s->stream))
-                        return rc;
-                HIPCHK(hipMemcpyAsync(h + o_sg, d + o_sg, (size_t)c * sg_sz, hipMemcpyDeviceToHost, s->stream));
-                if (terms)
-                        HIPCHK(hipMemcpyAsync(h + o_tm, d + o_tm, (size_t)c * tm_sz, hipMemcpyDeviceToHost,
-                                              s->stream));
-                HIPCHK(hipStreamSynchronize(s->stream));
-                std::memcpy(reinterpret_cast<char *>(sgs) + (size_t)b * sg_sz, h + o_sg, (size_t)c * sg_sz);
-                if (terms)
-                        par_memcpy(reinterpret_cast<char *>(terms) + (size_t)b * tm_sz, h + o_tm, (size_t)c * tm_sz);
-        }
-        return VRT_OK;
+        const ChunkOut co[2] = { { sgs, (size_t)kProbeSGs * sizeof(vrt_sg), true },
+                                 { terms, (size_t)kProbeSGs * np * 12, terms != nullptr } };
+        return chunked_host(
+                s, probes, sizeof(vrt_probe), n, probe_chunk(np), co, 2,
+                [&](char *d_in, char *const *d, int64_t c) {
+                        ProbeIO io{};
+                        io.probes = reinterpret_cast<const float *>(d_in);
+                        io.n = c;
+                        io.npoints = np;
+                        std::memcpy(io.light, light_color, sizeof io.light);
+                        io.sgs = reinterpret_cast<float *>(d[0]);
+                        io.terms = reinterpret_cast<float *>(d[1]);
+                        return probe_enqueue(s, io, pts, min_voxel, s->stream);
+                },
+                [](char *const *, int64_t) { return (int)VRT_OK; });
 }
 
 // ---- light probes as scene voxels (vrt_scene_create_probes) ----------------
@@ -3376,8 +3213,7 @@ static int probe_sgs_quiesce(vrt_scene *s)
         HIPCHK(hipSetDevice(s->device));
         HIPCHK(hipStreamSynchronize(s->stream));
         for (TraceSet &t : s->ts)
-                if (t.live)
-                        HIPCHK(hipEventSynchronize(t.ev));
+                HIPCHK(t.use.sync());
         return VRT_OK;
 }
 
@@ -3583,13 +3419,13 @@ extern "C" int vrt_expf_model_device(int device, const float *x, int64_t n, int 
         if (n == 0)
                 return VRT_OK;
         HIPCHK(hipSetDevice(device));
-        DevBuf dx, dy;
-        HIPCHK(hipMalloc(&dx.p, (size_t)n * 4));
-        HIPCHK(hipMalloc(&dy.p, (size_t)n * 4));
-        HIPCHK(hipMemcpy(dx.p, x, (size_t)n * 4, hipMemcpyHostToDevice));
-        HIPCHK(launch_expf_model(static_cast<const float *>(dx.p), n, flavour, static_cast<float *>(dy.p), nullptr));
+        DevMem dx, dy;
+        HIPCHK(dx.alloc((size_t)n * 4));
+        HIPCHK(dy.alloc((size_t)n * 4));
+        HIPCHK(hipMemcpy(dx, x, (size_t)n * 4, hipMemcpyHostToDevice));
+        HIPCHK(launch_expf_model(dx.as<float>(), n, flavour, dy.as<float>(), nullptr));
         HIPCHK(hipDeviceSynchronize());
-        HIPCHK(hipMemcpy(y, dy.p, (size_t)n * 4, hipMemcpyDeviceToHost));
+        HIPCHK(hipMemcpy(y, dy, (size_t)n * 4, hipMemcpyDeviceToHost));
         return VRT_OK;
 }
 
@@ -3635,33 +3471,23 @@ extern "C" int vrt_expf_selftest(int device, uint32_t first_bits, uint64_t count
                 // while the host compares chunk c - 1
                 constexpr uint64_t kChunk = (uint64_t)1 << 24;
                 const uint64_t m = std::min(count, kChunk);
-                struct Bufs {
-                        void *d[2] = {}, *h[2] = {};
-                        hipStream_t st = nullptr;
-                        ~Bufs()
-                        {
-                                for (int k = 0; k < 2; ++k) {
-                                        if (d[k])
-                                                (void)hipFree(d[k]);
-                                        if (h[k])
-                                                (void)hipHostFree(h[k]);
-                                }
-                                if (st)
-                                        (void)hipStreamDestroy(st);
-                        }
+                struct {
+                        DevMem d[2];
+                        PinnedMem h[2];
+                        Stream st;
                 } bf;
                 if (count > 0) {
-                        HIPCHK(hipStreamCreateWithFlags(&bf.st, hipStreamNonBlocking));
+                        HIPCHK(bf.st.create());
                         for (int k = 0; k < (count > kChunk ? 2 : 1); ++k) {
-                                HIPCHK(hipMalloc(&bf.d[k], m * 4));
-                                HIPCHK(hipHostMalloc(&bf.h[k], m * 4, hipHostMallocDefault));
+                                HIPCHK(bf.d[k].alloc(m * 4));
+                                HIPCHK(bf.h[k].alloc(m * 4));
                         }
                 }
                 auto enqueue = [&](uint64_t k0) -> int {
                         const int b = (int)((k0 / kChunk) & 1);
                         const uint64_t c = std::min(kChunk, count - k0);
                         HIPCHK(launch_selftest_expf(first_bits + (uint32_t)k0 * stride, stride, (int64_t)c, flavour,
-                                                    static_cast<float *>(bf.d[b]), bf.st));
+                                                    bf.d[b].as<float>(), bf.st));
                         HIPCHK(hipMemcpyAsync(bf.h[b], bf.d[b], c * 4, hipMemcpyDeviceToHost, bf.st));
                         return VRT_OK;
                 };
@@ -3675,7 +3501,7 @@ extern "C" int vrt_expf_selftest(int device, uint32_t first_bits, uint64_t count
                                 if (int rc = enqueue(k0 + kChunk))
                                         return rc;
                         expf_compare(first_bits, stride, k0, std::min(kChunk, count - k0), flavour,
-                                     static_cast<const float *>(bf.h[(k0 / kChunk) & 1]), &bad, &first_k);
+                                     bf.h[(k0 / kChunk) & 1].as<float>(), &bad, &first_k);
                 }
         }
         *mismatches = bad;
@@ -3863,26 +3689,26 @@ static int render_trace_host(vrt_scene *s, FramePath fp, const vrt_camera *cam, 
                 return fail(VRT_E_INVALID, "no light map: call vrt_lightmap_build first");
         HIPCHK(hipSetDevice(s->device));
         const size_t npix = (size_t)film->nx * film->ny, ns = npix * 4;
-        DevBuf img, dh, dr;
-        HIPCHK(hipMalloc(&img.p, npix * 12));
-        HIPCHK(hipMemsetAsync(img.p, 0, npix * 12, s->stream));
+        DevMem img, dh, dr;
+        HIPCHK(img.alloc(npix * 12));
+        HIPCHK(hipMemsetAsync(img, 0, npix * 12, s->stream));
         if (s_hit) {
-                HIPCHK(hipMalloc(&dh.p, ns * 4));
-                HIPCHK(hipMemsetAsync(dh.p, 0, ns * 4, s->stream));
+                HIPCHK(dh.alloc(ns * 4));
+                HIPCHK(hipMemsetAsync(dh, 0, ns * 4, s->stream));
         }
         if (s_rgb) {
-                HIPCHK(hipMalloc(&dr.p, ns * 12));
-                HIPCHK(hipMemsetAsync(dr.p, 0, ns * 12, s->stream));
+                HIPCHK(dr.alloc(ns * 12));
+                HIPCHK(hipMemsetAsync(dr, 0, ns * 12, s->stream));
         }
-        if (int rc = view_enqueue(s, fp, cam, film, min_voxel, 0, 1, 1, static_cast<float *>(img.p),
-                                  static_cast<int32_t *>(dh.p), static_cast<float *>(dr.p), s->stream))
+        if (int rc = view_enqueue(s, fp, cam, film, min_voxel, 0, 1, 1, img.as<float>(),
+                                  dh.as<int32_t>(), dr.as<float>(), s->stream))
                 return rc;
         HIPCHK(hipStreamSynchronize(s->stream));
-        HIPCHK(hipMemcpy(rgb, img.p, npix * 12, hipMemcpyDeviceToHost));
+        HIPCHK(hipMemcpy(rgb, img, npix * 12, hipMemcpyDeviceToHost));
         if (s_hit)
-                HIPCHK(hipMemcpy(s_hit, dh.p, ns * 4, hipMemcpyDeviceToHost));
+                HIPCHK(hipMemcpy(s_hit, dh, ns * 4, hipMemcpyDeviceToHost));
         if (s_rgb)
-                HIPCHK(hipMemcpy(s_rgb, dr.p, ns * 12, hipMemcpyDeviceToHost));
+                HIPCHK(hipMemcpy(s_rgb, dr, ns * 12, hipMemcpyDeviceToHost));
         return VRT_OK;
 }
 
@@ -3909,9 +3735,9 @@ static int trace_frame_device(vrt_scene *s, FramePath fp, const vrt_camera *ligh
         HIPCHK(hipSetDevice(s->device));
         hipStream_t st = static_cast<hipStream_t>(stream);
         if (!s->lm_ev)
-                HIPCHK(hipEventCreateWithFlags(&s->lm_ev, hipEventDisableTiming));
+                HIPCHK(s->lm_ev.create(hipEventDisableTiming));
         if (fp.probe && !s->sg_ev)
-                HIPCHK(hipEventCreateWithFlags(&s->sg_ev, hipEventDisableTiming));
+                HIPCHK(s->sg_ev.create(hipEventDisableTiming));
         const bool gather = fp.probe && light_color != nullptr;
         // alternate sets: this frame's light pass waits only for the frame
         // before last (the set's previous user), so it runs beside the
@@ -4036,24 +3862,24 @@ extern "C" int vrt_device_selftest(int device, const double *mt_in,
         if (int rc = check_device(device))
                 return rc;
         HIPCHK(hipSetDevice(device));
-        DevBuf a, b, c, d;
+        DevMem a, b, c, d;
         if (mt_in) {
-                HIPCHK(hipMalloc(&a.p, (size_t)n * 15 * 8));
-                HIPCHK(hipMalloc(&b.p, (size_t)n * 4 * 8));
-                HIPCHK(hipMemcpy(a.p, mt_in, (size_t)n * 15 * 8, hipMemcpyHostToDevice));
+                HIPCHK(a.alloc((size_t)n * 15 * 8));
+                HIPCHK(b.alloc((size_t)n * 4 * 8));
+                HIPCHK(hipMemcpy(a, mt_in, (size_t)n * 15 * 8, hipMemcpyHostToDevice));
         }
         if (sat_in) {
-                HIPCHK(hipMalloc(&c.p, (size_t)n * 15 * 4));
-                HIPCHK(hipMalloc(&d.p, (size_t)n * 4));
-                HIPCHK(hipMemcpy(c.p, sat_in, (size_t)n * 15 * 4, hipMemcpyHostToDevice));
+                HIPCHK(c.alloc((size_t)n * 15 * 4));
+                HIPCHK(d.alloc((size_t)n * 4));
+                HIPCHK(hipMemcpy(c, sat_in, (size_t)n * 15 * 4, hipMemcpyHostToDevice));
         }
-        HIPCHK(launch_selftest(static_cast<double *>(a.p), static_cast<double *>(b.p),
-                               static_cast<float *>(c.p), static_cast<int32_t *>(d.p), n, nullptr));
+        HIPCHK(launch_selftest(a.as<double>(), b.as<double>(),
+                               c.as<float>(), d.as<int32_t>(), n, nullptr));
         HIPCHK(hipDeviceSynchronize());
         if (mt_in)
-                HIPCHK(hipMemcpy(mt_out, b.p, (size_t)n * 4 * 8, hipMemcpyDeviceToHost));
+                HIPCHK(hipMemcpy(mt_out, b, (size_t)n * 4 * 8, hipMemcpyDeviceToHost));
         if (sat_in)
-                HIPCHK(hipMemcpy(sat_out, d.p, (size_t)n * 4, hipMemcpyDeviceToHost));
+                HIPCHK(hipMemcpy(sat_out, d, (size_t)n * 4, hipMemcpyDeviceToHost));
         return VRT_OK;
 }
 
@@ -4066,13 +3892,13 @@ extern "C" int vrt_device_selftest_chain(int device, const float *cases, int64_t
         if (n == 0)
                 return VRT_OK;
         HIPCHK(hipSetDevice(device));
-        DevBuf din, dout;
-        HIPCHK(hipMalloc(&din.p, (size_t)n * 21 * sizeof(float)));
-        HIPCHK(hipMalloc(&dout.p, (size_t)n * 6 * sizeof(uint32_t)));
-        HIPCHK(hipMemcpy(din.p, cases, (size_t)n * 21 * sizeof(float), hipMemcpyHostToDevice));
-        HIPCHK(launch_selftest_chain(static_cast<float *>(din.p), n, static_cast<uint32_t *>(dout.p), nullptr));
+        DevMem din, dout;
+        HIPCHK(din.alloc((size_t)n * 21 * sizeof(float)));
+        HIPCHK(dout.alloc((size_t)n * 6 * sizeof(uint32_t)));
+        HIPCHK(hipMemcpy(din, cases, (size_t)n * 21 * sizeof(float), hipMemcpyHostToDevice));
+        HIPCHK(launch_selftest_chain(din.as<float>(), n, dout.as<uint32_t>(), nullptr));
         HIPCHK(hipDeviceSynchronize());
-        HIPCHK(hipMemcpy(out, dout.p, (size_t)n * 6 * sizeof(uint32_t), hipMemcpyDeviceToHost));
+        HIPCHK(hipMemcpy(out, dout, (size_t)n * 6 * sizeof(uint32_t), hipMemcpyDeviceToHost));
         return VRT_OK;
 }
 
@@ -4099,30 +3925,30 @@ extern "C" int vrt_device_selftest_order(int device, const float *dist, const ui
         if (int rc = check_device(device))
                 return rc;
         HIPCHK(hipSetDevice(device));
-        DevBuf dd, dh, dout, ddep, dlen, darg;
+        DevMem dd, dh, dout, ddep, dlen, darg;
         if (n > 0) {
-                HIPCHK(hipMalloc(&dd.p, (size_t)n * 8 * sizeof(float)));
-                HIPCHK(hipMalloc(&dh.p, (size_t)n * sizeof(uint32_t)));
-                HIPCHK(hipMalloc(&dout.p, (size_t)n * 6 * sizeof(uint32_t)));
-                HIPCHK(hipMemcpy(dd.p, dist, (size_t)n * 8 * sizeof(float), hipMemcpyHostToDevice));
-                HIPCHK(hipMemcpy(dh.p, hit_mask, (size_t)n * sizeof(uint32_t), hipMemcpyHostToDevice));
+                HIPCHK(dd.alloc((size_t)n * 8 * sizeof(float)));
+                HIPCHK(dh.alloc((size_t)n * sizeof(uint32_t)));
+                HIPCHK(dout.alloc((size_t)n * 6 * sizeof(uint32_t)));
+                HIPCHK(hipMemcpy(dd, dist, (size_t)n * 8 * sizeof(float), hipMemcpyHostToDevice));
+                HIPCHK(hipMemcpy(dh, hit_mask, (size_t)n * sizeof(uint32_t), hipMemcpyHostToDevice));
         }
         if (m > 0) {
-                HIPCHK(hipMalloc(&ddep.p, std::max<size_t>(1, (size_t)m * stride) * sizeof(float)));
-                HIPCHK(hipMalloc(&dlen.p, (size_t)m * sizeof(int32_t)));
-                HIPCHK(hipMalloc(&darg.p, (size_t)m * sizeof(int32_t)));
+                HIPCHK(ddep.alloc(std::max<size_t>(1, (size_t)m * stride) * sizeof(float)));
+                HIPCHK(dlen.alloc((size_t)m * sizeof(int32_t)));
+                HIPCHK(darg.alloc((size_t)m * sizeof(int32_t)));
                 if (stride > 0)
-                        HIPCHK(hipMemcpy(ddep.p, depth, (size_t)m * stride * sizeof(float), hipMemcpyHostToDevice));
-                HIPCHK(hipMemcpy(dlen.p, len, (size_t)m * sizeof(int32_t), hipMemcpyHostToDevice));
+                        HIPCHK(hipMemcpy(ddep, depth, (size_t)m * stride * sizeof(float), hipMemcpyHostToDevice));
+                HIPCHK(hipMemcpy(dlen, len, (size_t)m * sizeof(int32_t), hipMemcpyHostToDevice));
         }
-        HIPCHK(launch_selftest_order(static_cast<float *>(dd.p), static_cast<uint32_t *>(dh.p), n,
-                                     static_cast<uint32_t *>(dout.p), static_cast<float *>(ddep.p),
-                                     static_cast<int32_t *>(dlen.p), m, stride, static_cast<int32_t *>(darg.p),
+        HIPCHK(launch_selftest_order(dd.as<float>(), dh.as<uint32_t>(), n,
+                                     dout.as<uint32_t>(), ddep.as<float>(),
+                                     dlen.as<int32_t>(), m, stride, darg.as<int32_t>(),
                                      nullptr));
         HIPCHK(hipDeviceSynchronize());
         if (n > 0)
-                HIPCHK(hipMemcpy(orders, dout.p, (size_t)n * 6 * sizeof(uint32_t), hipMemcpyDeviceToHost));
+                HIPCHK(hipMemcpy(orders, dout, (size_t)n * 6 * sizeof(uint32_t), hipMemcpyDeviceToHost));
         if (m > 0)
-                HIPCHK(hipMemcpy(argmin, darg.p, (size_t)m * sizeof(int32_t), hipMemcpyDeviceToHost));
+                HIPCHK(hipMemcpy(argmin, darg, (size_t)m * sizeof(int32_t), hipMemcpyDeviceToHost));
         return VRT_OK;
 }

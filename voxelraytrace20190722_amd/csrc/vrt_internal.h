@@ -598,10 +598,107 @@ int scene_replicate(const vrt_scene *src, const vrt_scene_desc *d, int device, v
 void par_memcpy(void *dst, const void *src, size_t bytes);
 // the process-wide vrt_set_test_flags value
 int test_flags();
-// A grow-only staging pair kept in a scene between calls: cap bytes on the
-// device and as many pinned on the host, used on one stream only.
+// Owners of the HIP resources the host keeps (device and pinned memory,
+// events, streams): move-only, empty when default-constructed, released by
+// the destructor.  An empty owner makes no HIP call, so a host-only scene is
+// made and destroyed on a machine without a device; none has static storage
+// duration (nothing calls into HIP during process teardown).  An owner
+// converts to its handle where a HIP call takes one; whoever releases a
+// resource that work in flight may still use waits for that work first.
+template <class H, hipError_t (*Release)(H)>
+class Owner {
+public:
+        Owner() = default;
+        Owner(Owner &&o) noexcept : h_(o.h_) { o.h_ = nullptr; }
+        Owner &operator=(Owner &&o) noexcept
+        {
+                if (this != &o) {
+                        reset();
+                        h_ = o.h_;
+                        o.h_ = nullptr;
+                }
+                return *this;
+        }
+        ~Owner() { reset(); }
+        void reset()
+        {
+                if (h_)
+                        (void)Release(h_);
+                h_ = nullptr;
+        }
+        H get() const { return h_; }
+        operator H() const { return h_; }
+
+protected:
+        H h_ = nullptr;
+};
+// alloc() releases what was held; size(): the bytes held
+struct DevMem : Owner<void *, hipFree> {
+        hipError_t alloc(size_t bytes)
+        {
+                reset();
+                const hipError_t e = hipMalloc(&h_, bytes);
+                if (e != hipSuccess)
+                        h_ = nullptr;
+                n_ = bytes;
+                return e;
+        }
+        template <class T> T *as() const { return static_cast<T *>(h_); }
+        size_t size() const { return h_ ? n_ : 0; }
+
+private:
+        size_t n_ = 0;
+};
+struct PinnedMem : Owner<void *, hipHostFree> {
+        hipError_t alloc(size_t bytes)
+        {
+                reset();
+                const hipError_t e = hipHostMalloc(&h_, bytes, hipHostMallocDefault);
+                if (e != hipSuccess)
+                        h_ = nullptr;
+                return e;
+        }
+        template <class T> T *as() const { return static_cast<T *>(h_); }
+};
+struct Event : Owner<hipEvent_t, hipEventDestroy> {
+        hipError_t create(unsigned flags = hipEventDefault)
+        {
+                reset();
+                return hipEventCreateWithFlags(&h_, flags);
+        }
+};
+struct Stream : Owner<hipStream_t, hipStreamDestroy> {
+        hipError_t create(unsigned flags = hipStreamNonBlocking)
+        {
+                reset();
+                return hipStreamCreateWithFlags(&h_, flags);
+        }
+};
+// The event of a resource's last user and whether there was one: the next
+// user's stream waits for it, the user records it behind its work, the host
+// waits for it before the resource goes.  Before the first record() (the
+// event may not exist yet) wait() and sync() do nothing and done() is true.
+struct LastUse {
+        Event ev;
+        bool live = false;
+        hipError_t create() { return ev.create(hipEventDisableTiming); }
+        hipError_t wait(hipStream_t st) const { return live ? hipStreamWaitEvent(st, ev, 0) : hipSuccess; }
+        hipError_t record(hipStream_t st)
+        {
+                const hipError_t e = hipEventRecord(ev, st);
+                if (e == hipSuccess)
+                        live = true;
+                return e;
+        }
+        hipError_t sync() const { return live ? hipEventSynchronize(ev) : hipSuccess; }
+        bool done() const { return !live || hipEventQuery(ev) == hipSuccess; }
+};
+
+// A grow-only staging pair kept between calls: cap bytes on the device and
+// as many pinned on the host, used on one stream only.
 struct Staging {
-        void *d = nullptr, *h = nullptr;
+        DevMem d;
+        PinnedMem h;
         size_t cap = 0;
         // room for `bytes`; growing waits for the stream's work on the old pair
         hipError_t grow(size_t bytes, hipStream_t st)
@@ -610,22 +707,15 @@ struct Staging {
                         return hipSuccess;
                 if (hipError_t e = hipStreamSynchronize(st))
                         return e;
-                release();
-                if (hipError_t e = hipMalloc(&d, bytes))
+                cap = 0;
+                d.reset();
+                h.reset();
+                if (hipError_t e = d.alloc(bytes))
                         return e;
-                if (hipError_t e = hipHostMalloc(&h, bytes, hipHostMallocDefault))
+                if (hipError_t e = h.alloc(bytes))
                         return e;
                 cap = bytes;
                 return hipSuccess;
-        }
-        void release()
-        {
-                if (d)
-                        (void)hipFree(d);
-                if (h)
-                        (void)hipHostFree(h);
-                d = h = nullptr;
-                cap = 0;
         }
 };
 

@@ -29,15 +29,13 @@ struct vrt_multi {
         std::vector<vrt_scene *> sc;    // rank i's replica of the scene
         std::vector<ncclComm_t> comm;   // ncclCommInitAll over devs (empty: virtual ranks)
         bool virt = false;              // VRT_TEST_VIRTUAL_RANKS: n ranks on one device, copies for the gather
-        std::vector<hipStream_t> st;    // rank i's render + collective stream
-        std::vector<hipEvent_t> ev;     // rank i: its part of a frame queued
-        std::vector<float *> send;      // ranks >= 1: packed tile buffer (tpr * 192 floats)
-        float *gath = nullptr;          // rank 0: n * tpr * 192 floats (its own share in place)
+        std::vector<Stream> st;         // rank i's render + collective stream
+        std::vector<Event> ev;          // rank i: its part of a frame queued
+        std::vector<DevMem> send;       // ranks >= 1: packed tile buffer (tpr * 192 floats)
+        DevMem gath;                    // rank 0: n * tpr * 192 floats (its own share in place)
         size_t tpr_cap = 0;             // tiles per rank the buffers hold
-        float *d_img = nullptr;         // vrt_render_multi: image on rank 0's device
-        float *h_pin = nullptr;         // and its pinned staging copy
-        size_t img_bytes = 0;
-        hipEvent_t ev_in = nullptr;     // caller's stream -> rank 0's stream
+        Staging img;                    // vrt_render_multi: image on rank 0's device, its pinned copy; on st[0]
+        Event ev_in;                    // caller's stream -> rank 0's stream
         std::mutex mu;
 };
 
@@ -82,13 +80,11 @@ void free_buffers(vrt_multi *m)
         for (size_t i = 0; i < m->send.size(); ++i)
                 if (m->send[i]) {
                         (void)hipSetDevice(m->devs[i]);
-                        (void)hipFree(m->send[i]);
-                        m->send[i] = nullptr;
+                        m->send[i].reset();
                 }
         if (m->gath) {
                 (void)hipSetDevice(m->devs[0]);
-                (void)hipFree(m->gath);
-                m->gath = nullptr;
+                m->gath.reset();
         }
         m->tpr_cap = 0;
 }
@@ -121,7 +117,7 @@ int gather(vrt_multi *m, size_t count)
                 for (int i = 1; i < n; ++i)
                         HIPCHK(hipStreamWaitEvent(m->st[i], m->ev[0], 0));
                 for (int i = 1; i < n; ++i) {
-                        HIPCHK(hipMemcpyAsync(m->gath + (size_t)i * count, m->send[i], count * sizeof(float),
+                        HIPCHK(hipMemcpyAsync(m->gath.as<float>() + (size_t)i * count, m->send[i], count * sizeof(float),
                                               hipMemcpyDeviceToDevice, m->st[i]));
                         HIPCHK(hipEventRecord(m->ev[i], m->st[i]));
                         HIPCHK(hipStreamWaitEvent(m->st[0], m->ev[i], 0));
@@ -131,7 +127,7 @@ int gather(vrt_multi *m, size_t count)
         // one RCCL gather to rank 0 (in place for rank 0: sendbuff == recvbuff + 0)
         NCCLCHK(ncclGroupStart());
         for (int i = 0; i < n; ++i) {
-                const ncclResult_t r = ncclGather(i == 0 ? m->gath : m->send[i], i == 0 ? m->gath : nullptr, count,
+                const ncclResult_t r = ncclGather(i == 0 ? m->gath.get() : m->send[i].get(), i == 0 ? m->gath.get() : nullptr, count,
                                                   ncclFloat32, 0, m->comm[i], m->st[i]);
                 if (r != ncclSuccess) {
                         (void)ncclGroupEnd();
@@ -154,10 +150,10 @@ int render_multi(vrt_multi *m, const vrt_camera *cam, const vrt_film *film, floa
                 free_buffers(m);
                 for (int i = 1; i < n; ++i) {
                         HIPCHK(hipSetDevice(m->devs[i]));
-                        HIPCHK(hipMalloc(&m->send[i], count * sizeof(float)));
+                        HIPCHK(m->send[i].alloc(count * sizeof(float)));
                 }
                 HIPCHK(hipSetDevice(m->devs[0]));
-                HIPCHK(hipMalloc(&m->gath, (size_t)n * count * sizeof(float)));
+                HIPCHK(m->gath.alloc((size_t)n * count * sizeof(float)));
                 m->tpr_cap = (size_t)tpr;
         }
         HIPCHK(hipSetDevice(m->devs[0]));
@@ -168,7 +164,7 @@ int render_multi(vrt_multi *m, const vrt_camera *cam, const vrt_film *film, floa
         if (tpr > 0) {
                 // each rank's share, packed tile-major (vrt_render_tiles_device)
                 for (int i = 0; i < n; ++i) {
-                        float *dst = i == 0 ? m->gath : m->send[i];
+                        float *dst = (i == 0 ? m->gath : m->send[i]).as<float>();
                         if (int rc = vrt_render_tiles_device(m->sc[i], cam, film, i, n, 0, dst, m->st[i]))
                                 return rc;
                 }
@@ -177,7 +173,7 @@ int render_multi(vrt_multi *m, const vrt_camera *cam, const vrt_film *film, floa
         }
         HIPCHK(hipSetDevice(m->devs[0]));
         if (tpr > 0) {
-                if (int rc = vrt_unpack_tiles_device(film, n, m->gath, d_image, m->st[0]))
+                if (int rc = vrt_unpack_tiles_device(film, n, m->gath.as<float>(), d_image, m->st[0]))
                         return rc;
         } else {
                 HIPCHK(hipMemsetAsync(d_image, 0, (size_t)film->nx * film->ny * 12, m->st[0]));
@@ -200,25 +196,17 @@ extern "C" void vrt_multi_destroy(vrt_multi *m)
         for (ncclComm_t c : m->comm)
                 if (c)
                         (void)ncclCommDestroy(c);
+        // each rank's resources go with its device current
         free_buffers(m);
-        if (m->d_img || m->h_pin || m->ev_in) {
-                (void)hipSetDevice(m->devs[0]);
-                if (m->d_img)
-                        (void)hipFree(m->d_img);
-                if (m->h_pin)
-                        (void)hipHostFree(m->h_pin);
-                if (m->ev_in)
-                        (void)hipEventDestroy(m->ev_in);
-        }
         for (size_t i = 0; i < m->st.size(); ++i) {
                 (void)hipSetDevice(m->devs[i]);
-                if (m->ev[i])
-                        (void)hipEventDestroy(m->ev[i]);
-                if (m->st[i])
-                        (void)hipStreamDestroy(m->st[i]);
+                m->ev[i].reset();
+                m->st[i].reset();
         }
         for (vrt_scene *s : m->sc)
                 vrt_scene_destroy(s);
+        if (m->img.d || m->ev_in)  // rank 0's image pair and event
+                (void)hipSetDevice(m->devs[0]);
         delete m;
 }
 
@@ -250,9 +238,9 @@ extern "C" int vrt_scene_create_multi(const vrt_scene_desc *desc, int max_depth,
         const int n = (int)devs.size();
         m->devs = devs;
         m->sc.assign(n, nullptr);
-        m->st.assign(n, nullptr);
-        m->ev.assign(n, nullptr);
-        m->send.assign(n, nullptr);
+        m->st.resize(n);
+        m->ev.resize(n);
+        m->send.resize(n);
         // no probes in a multi-device scene: VRT_BUILD_DEVICE_PROBES is refused too
         if (flags & ~VRT_BUILD_DEVICE)
                 return set_error(VRT_E_INVALID, "vrt_scene_create_multi: unknown flags %#x", flags);
@@ -278,11 +266,11 @@ extern "C" int vrt_scene_create_multi(const vrt_scene_desc *desc, int max_depth,
                         return set_error(rcs[i], "replica on device %d: %s", devs[i], errs[i].c_str());
         for (int i = 0; i < n; ++i) {
                 HIPCHK(hipSetDevice(devs[i]));
-                HIPCHK(hipStreamCreateWithFlags(&m->st[i], hipStreamNonBlocking));
-                HIPCHK(hipEventCreateWithFlags(&m->ev[i], hipEventDisableTiming));
+                HIPCHK(m->st[i].create());
+                HIPCHK(m->ev[i].create(hipEventDisableTiming));
         }
         HIPCHK(hipSetDevice(devs[0]));
-        HIPCHK(hipEventCreateWithFlags(&m->ev_in, hipEventDisableTiming));
+        HIPCHK(m->ev_in.create(hipEventDisableTiming));
         m->virt = virt;
         if (!virt) {
                 m->comm.assign(n, nullptr);
@@ -337,27 +325,15 @@ extern "C" int vrt_render_multi(vrt_multi *m, const vrt_camera *cam, const vrt_f
         DeviceGuard g;
         const size_t bytes = (size_t)film->nx * film->ny * 12;
         HIPCHK(hipSetDevice(m->devs[0]));
-        if (bytes > m->img_bytes) {
-                HIPCHK(hipStreamSynchronize(m->st[0]));
-                if (m->d_img)
-                        (void)hipFree(m->d_img);
-                if (m->h_pin)
-                        (void)hipHostFree(m->h_pin);
-                m->d_img = nullptr;
-                m->h_pin = nullptr;
-                m->img_bytes = 0;
-                HIPCHK(hipMalloc(&m->d_img, bytes));
-                HIPCHK(hipHostMalloc(&m->h_pin, bytes, hipHostMallocDefault));
-                m->img_bytes = bytes;
-        }
+        HIPCHK(m->img.grow(bytes, m->st[0]));
         // the unpack writes every pixel (zero outside the tile grid)
-        if (int rc = render_multi(m, cam, film, m->d_img, nullptr))
+        if (int rc = render_multi(m, cam, film, m->img.d.as<float>(), nullptr))
                 return rc;
         HIPCHK(hipSetDevice(m->devs[0]));
-        HIPCHK(hipMemcpyAsync(m->h_pin, m->d_img, bytes, hipMemcpyDeviceToHost, m->st[0]));
+        HIPCHK(hipMemcpyAsync(m->img.h, m->img.d, bytes, hipMemcpyDeviceToHost, m->st[0]));
         if (int rc = sync_all(m))
                 return rc;
-        par_memcpy(rgb, m->h_pin, bytes);
+        par_memcpy(rgb, m->img.h, bytes);
         return VRT_OK;
 }
 
