@@ -427,6 +427,11 @@ int vrt_lightmap_build(vrt_scene *s, const vrt_camera *light_cam,
  * illum[6][3].  coverage / illum may be NULL. */
 int vrt_lightmap_nodes(vrt_scene *s, uint64_t *key, float *coverage,
                        float *illum);
+/* Diagnostics of the last light-map build (vrt_lightmap_build or a one-call
+ * frame): stats = {light samples (64 * (nx/8) * (ny/8) * 4), samples that
+ * hit, samples whose walk passed the triangle-test budget and was handed to
+ * the tail walk}.  All 0 before the first build. */
+int vrt_lightmap_stats(vrt_scene *s, int64_t stats[3]);
 /* min component of root.size() / powf(2, levels) -- the reference's Res
  * (VRT/main.cc:69-70); levels <= 0 uses the scene's max_depth. */
 int vrt_scene_min_voxel(const vrt_scene *s, int levels, float *res);

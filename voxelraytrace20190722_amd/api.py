@@ -576,6 +576,13 @@ class VoxelOctree:
         o = np.argsort(key, kind="stable")
         return key[o], cov[o], ill[o]
 
+    def lightmap_stats(self):
+        """The last light-map build (vrt_lightmap_stats): {samples, hits,
+        deferred: samples handed to the tail walk}."""
+        c = (C.c_int64 * 3)()
+        check(lib().vrt_lightmap_stats(self.h, c), "vrt_lightmap_stats")
+        return dict(zip(("samples", "hits", "deferred"), list(c)))
+
     def render_trace(self, cam, film, min_voxel=0.0, samples=False):
         """trace() render (cone tracing) -> (ny, nx, 3) [+ per-sample hit / rgb]."""
         rgb = np.zeros((film.ny, film.nx, 3), np.float32)

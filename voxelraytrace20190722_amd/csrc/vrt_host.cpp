@@ -406,6 +406,7 @@ struct vrt_scene {
         TraceSet ts[2];
         int ts_next = 0;
         int lm_cur = -1;
+        int64_t lm_stats[3] = {};  // the last build's samples, hits, tail samples (vrt_lightmap_stats)
         DevMem d_light;
         // config-5 ray compaction (SpillQueues): round counters + two record
         // queues of spill_cap chunks each; two sets, used by alternate
@@ -2443,9 +2444,15 @@ static int lightmap_enqueue(vrt_scene *s, int set, const vrt_camera *light_cam, 
                 if (int rc = overlap())
                         return rc;
         // the sort takes its length on the host: the one mid-build sync
-        unsigned int nhit = 0;
-        HIPCHK(hipMemcpyAsync(&nhit, d_count, sizeof nhit, hipMemcpyDeviceToHost, s->stream));
+        // (the same copy reaches to the tail's sample count, final once
+        // k_light has run: for vrt_lightmap_stats)
+        unsigned int ctrs[33] = {};  // d_count at word 0, d_tail_n at word 32
+        HIPCHK(hipMemcpyAsync(ctrs, d_count, sizeof ctrs, hipMemcpyDeviceToHost, s->stream));
         HIPCHK(hipStreamSynchronize(s->stream));
+        const unsigned int nhit = ctrs[0], ntail = ctrs[32];
+        s->lm_stats[0] = ns;
+        s->lm_stats[1] = nhit;
+        s->lm_stats[2] = ntail;
 #ifdef VRT_LIGHT_DIAG
         {
                 static int ndump = 0;
@@ -2461,11 +2468,7 @@ static int lightmap_enqueue(vrt_scene *s, int set, const vrt_camera *light_cam, 
         }
 #endif
 #ifdef VRT_LIGHT_TAIL_REPORT
-        {
-                unsigned int ntail = 0;
-                HIPCHK(hipMemcpy(&ntail, d_tail_n, sizeof ntail, hipMemcpyDeviceToHost));
-                std::fprintf(stderr, "light pass: %u of %lld samples deferred, %u hits\n", ntail, (long long)ns, nhit);
-        }
+        std::fprintf(stderr, "light pass: %u of %lld samples deferred, %u hits\n", ntail, (long long)ns, nhit);
 #endif
         if (nhit > 0)
                 HIPCHK(sort_pairs_u64(temp, &sort_bytes, k_in, k_out, v_in, v_out, nhit, kbits + lbits, s->stream));
@@ -2506,6 +2509,18 @@ extern "C" int vrt_lightmap_build(vrt_scene *s, const vrt_camera *light_cam,
         HIPCHK(hipStreamSynchronize(s->stream));
         if (hits)
                 *hits = (int64_t)nhit;
+        return VRT_OK;
+}
+
+extern "C" int vrt_lightmap_stats(vrt_scene *s, int64_t stats[3])
+{
+        if (s && need_device(s))
+                return VRT_E_NODEVICE;
+        if (!s || !stats)
+                return fail(VRT_E_INVALID, "null argument");
+        std::lock_guard<std::mutex> lk(s->mu);
+        for (int r = 0; r < 3; ++r)
+                stats[r] = s->lm_stats[r];  // read at the build's own sync
         return VRT_OK;
 }
 

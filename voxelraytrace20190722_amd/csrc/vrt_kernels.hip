@@ -4589,7 +4589,9 @@ __device__ __forceinline__ int split_level_of(float x, const float *up)
 {
         const int e = (int)(__float_as_uint(x) >> 23) - 127;
         if (e >= 63)
-                return e;  // unreachable for finite scenes (maxdist/mindist < 2^63)
+                return e;  // past the table: a caller's min_voxel far below the scene's size
+                           // (1e-20, say) gets here; no node lies that deep, so the
+                           // exponent serves (cone_march_fast clamps it to 63)
         return x >= up[e] ? e + 1 : e;
 }
 
