@@ -709,6 +709,61 @@ int vrt_trace_frame_probes_device(vrt_scene *s, const vrt_camera *light_cam, con
                                   float min_voxel, int rank, int nranks, int image_layout, float *d_out,
                                   void *stream, int64_t *hits);
 
+/* ---- trace() frames and probe scenes on the multi-device handle -----------
+ * vrt_scene_create_multi with light probes: flags as vrt_scene_create_probes
+ * (0 builds on the host, VRT_BUILD_DEVICE | VRT_BUILD_DEVICE_PROBES on rank
+ * 0's device, anything else is VRT_E_INVALID), checked after the mask and the
+ * devices' visibility as vrt_scene_create_multi checks its own.  Every replica
+ * holds rank 0's probes, probe lists and masks and stored SGs.  nprobe == 0 or
+ * probes == NULL is vrt_scene_create_multi.  vrt_multi_set_probe_sgs:
+ * vrt_scene_set_probe_sgs (14 * nprobe records) on every rank. */
+int vrt_scene_create_multi_probes(const vrt_scene_desc *desc, const vrt_probe *probes, int32_t nprobe,
+                                  int max_depth, uint32_t device_mask, int flags, vrt_multi **out);
+int vrt_multi_set_probe_sgs(vrt_multi *m, const vrt_sg *sgs);
+/* How the ranks share a light-map build.  REPLICATED (the default): every rank
+ * marches the whole light film.  SHARDED: rank i marches its tiles of the
+ * light film's tile deal (the view's deal, vrt_tile_deal_map), the ranks
+ * exchange their hit lists (RCCL on each rank's scene stream), and every rank
+ * sorts and sums the union: a hit's key holds its index in the canonical
+ * order, which does not depend on who marched it, so every rank ends with the
+ * single-device light map, bit for bit, in either mode.  After a sharded build
+ * vrt_lightmap_stats on a rank's scene reports that rank's share.  A 1-rank
+ * handle builds the whole map in either mode.  Other values: VRT_E_INVALID. */
+#define VRT_MULTI_LIGHT_REPLICATED 0
+#define VRT_MULTI_LIGHT_SHARDED 1
+int vrt_multi_set_light_mode(vrt_multi *m, int mode);
+/* The light map on every rank (vrt_lightmap_build's values); *hits (may be
+ * NULL) is the light pass's hit count: in sharded mode the sum of the ranks',
+ * in replicated mode every rank's own, which must agree (VRT_E_DEVICE if the
+ * replicas diverged).  Returns when every rank's map is built. */
+int vrt_lightmap_build_multi(vrt_multi *m, const vrt_camera *light_cam, const vrt_film *light_film, int64_t *hits);
+/* The cone-traced view over the ranks' current light maps (VRT_E_INVALID
+ * unless every rank has one): rank i shades its tiles of the deal, packed
+ * tile-major, then the gather and unpack of vrt_render_multi.  The image
+ * (nx*ny*3, index y*nx+x, zero outside the tile grid) is vrt_render_trace's
+ * bit for bit, for any rank count; on a probe handle, vrt_render_trace_probes'.
+ * Host array, or d_image on rank 0's device with the stream ordering of
+ * vrt_render_multi_device. */
+int vrt_render_trace_multi(vrt_multi *m, const vrt_camera *cam, const vrt_film *film, float min_voxel, float *rgb);
+int vrt_render_trace_multi_device(vrt_multi *m, const vrt_camera *cam, const vrt_film *film, float min_voxel,
+                                  float *d_image, void *stream);
+/* The reference main() frame in one call: the light-map build above and,
+ * beside each rank's light march, the primary march of its share of the view.
+ * The light march is enqueued on every rank before the host waits for any
+ * rank's hit count (one sync per rank).  On a probe handle each rank's work is
+ * vrt_trace_frame_probes_device's: with light_color (float[3]) every rank
+ * gathers the scene's probes behind the filter (identical SGs everywhere),
+ * with NULL the stored SGs are kept; without probes light_color is ignored.
+ * Arguments are checked as the per-rank calls check them, before anything is
+ * enqueued; after a failure on any rank nothing collective is enqueued and
+ * every rank's streams are synchronised before the error is returned. */
+int vrt_trace_frame_multi(vrt_multi *m, const vrt_camera *light_cam, const vrt_film *light_film,
+                          const float *light_color, const vrt_camera *cam, const vrt_film *film,
+                          float min_voxel, float *rgb, int64_t *hits);
+int vrt_trace_frame_multi_device(vrt_multi *m, const vrt_camera *light_cam, const vrt_film *light_film,
+                                 const float *light_color, const vrt_camera *cam, const vrt_film *film,
+                                 float min_voxel, float *d_image, void *stream, int64_t *hits);
+
 /* ---- output (VRT/stb_image_write.h:178,723-757) ------------------------- */
 /* Byte-identical to stbi_write_hdr: returns 1 on success, 0 on failure. */
 int vrt_write_hdr(const char *filename, int w, int h, int comp,

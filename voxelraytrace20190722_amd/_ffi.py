@@ -105,6 +105,8 @@ VRT_OBJ_PARSE_ONLY = 1
 VRT_BUILD_DEVICE = 1
 VRT_BUILD_DEVICE_PROBES = 4
 VRT_MARCH_EVEN_INVISIBLE = 1
+VRT_MULTI_LIGHT_REPLICATED = 0
+VRT_MULTI_LIGHT_SHARDED = 1
 
 _P = C.c_void_p
 SIGNATURES = {
@@ -227,6 +229,17 @@ SIGNATURES = {
     "vrt_render_multi": (C.c_int, [_P, C.POINTER(Camera), C.POINTER(Film), f32p]),
     "vrt_render_multi_device": (C.c_int, [_P, C.POINTER(Camera), C.POINTER(Film), _P, _P]),
     "vrt_multi_tile_map": (C.c_int, [C.POINTER(Film), C.c_uint32, i32p, i32p]),
+    "vrt_scene_create_multi_probes": (C.c_int, [C.POINTER(SceneDesc), C.POINTER(Probe), C.c_int32, C.c_int,
+                                                C.c_uint32, C.c_int, C.POINTER(_P)]),
+    "vrt_multi_set_probe_sgs": (C.c_int, [_P, C.POINTER(SGRec)]),
+    "vrt_multi_set_light_mode": (C.c_int, [_P, C.c_int]),
+    "vrt_lightmap_build_multi": (C.c_int, [_P, C.POINTER(Camera), C.POINTER(Film), i64p]),
+    "vrt_render_trace_multi": (C.c_int, [_P, C.POINTER(Camera), C.POINTER(Film), C.c_float, f32p]),
+    "vrt_render_trace_multi_device": (C.c_int, [_P, C.POINTER(Camera), C.POINTER(Film), C.c_float, _P, _P]),
+    "vrt_trace_frame_multi": (C.c_int, [_P, C.POINTER(Camera), C.POINTER(Film), f32p, C.POINTER(Camera),
+                                        C.POINTER(Film), C.c_float, f32p, i64p]),
+    "vrt_trace_frame_multi_device": (C.c_int, [_P, C.POINTER(Camera), C.POINTER(Film), f32p, C.POINTER(Camera),
+                                               C.POINTER(Film), C.c_float, _P, _P, i64p]),
     "vrt_status_string": (C.c_char_p, [C.c_int]),
     "vrt_last_error": (C.c_char_p, []),
 }

@@ -752,24 +752,39 @@ class MultiOctree:
     device's share of the tile deal + one ncclGather to the first device +
     unpack there -- render_mt (VRT/camera.h:42-68) over a node's GPUs."""
 
-    def __init__(self, scene, max_depth, device_mask=1, build_on_device=False, virtual_ranks=None):
+    def __init__(self, scene, max_depth, device_mask=1, build_on_device=False, virtual_ranks=None, probes=None,
+                 light_mode="replicated"):
         """virtual_ranks=n (test hook, VRT_TEST_VIRTUAL_RANKS_N): n ranks on
         the one device of device_mask, the RCCL gather replaced by
-        device-to-device copies -- the n-rank frame on a one-GPU box."""
-        self.scene = scene
+        device-to-device copies -- the n-rank frame on a one-GPU box.
+        probes: as VoxelOctree's (vrt_scene_create_multi_probes); every rank
+        holds the same probe scene.  light_mode: "replicated" (every rank
+        marches the whole light film) or "sharded" (each its tiles of the
+        light film's deal, hit lists exchanged), see light_mode."""
+        self.scene_data = scene  # keeps the arrays alive for the descriptor
         h = C.c_void_p()
         d = scene.desc()
         flags = _ffi.VRT_BUILD_DEVICE if build_on_device else 0
+        self.probes = _probes_arg(probes)
+        if build_on_device and self.probes is not None:
+            flags |= _ffi.VRT_BUILD_DEVICE_PROBES
+
+        def create():
+            if self.probes is None:
+                return lib().vrt_scene_create_multi(C.byref(d), int(max_depth), int(device_mask), flags, C.byref(h))
+            return lib().vrt_scene_create_multi_probes(C.byref(d), self.probes.ctypes.data_as(C.POINTER(_ffi.Probe)),
+                                                       len(self.probes), int(max_depth), int(device_mask), flags,
+                                                       C.byref(h))
         if virtual_ranks:
             prev = lib().vrt_test_flags()  # restored afterwards: a caller's own test flags stay set
             lib().vrt_set_test_flags((prev & 0xFF & ~TEST_VIRTUAL_RANKS) | TEST_VIRTUAL_RANKS
                                      | (int(virtual_ranks) << 8))
             try:
-                rc = lib().vrt_scene_create_multi(C.byref(d), int(max_depth), int(device_mask), flags, C.byref(h))
+                rc = create()
             finally:
                 lib().vrt_set_test_flags(prev)
         else:
-            rc = lib().vrt_scene_create_multi(C.byref(d), int(max_depth), int(device_mask), flags, C.byref(h))
+            rc = create()
         check(rc, "vrt_scene_create_multi")
         self.h = h
         n = C.c_int32()
@@ -781,6 +796,9 @@ class MultiOctree:
         check(lib().vrt_multi_scene(self.h, 0, C.byref(s0)), "vrt_multi_scene")
         self.info = _ffi.SceneInfo()
         check(lib().vrt_scene_info(s0, C.byref(self.info)), "vrt_scene_info")
+        self.max_depth = int(max_depth)
+        self._light_mode = "replicated"
+        self.light_mode = light_mode
 
     def close(self):
         if self.h:
@@ -809,6 +827,110 @@ class MultiOctree:
         check(lib().vrt_render_multi_device(self.h, C.byref(cam.c), C.byref(film.c), C.c_void_p(d_image_ptr),
                                             C.c_void_p(stream_ptr) if stream_ptr else None),
               "vrt_render_multi_device")
+
+
+    # ---- trace() frames (light pass + filter + cone-traced view) ----
+    LIGHT_MODES = {"replicated": _ffi.VRT_MULTI_LIGHT_REPLICATED, "sharded": _ffi.VRT_MULTI_LIGHT_SHARDED}
+
+    @property
+    def light_mode(self):
+        """How the ranks share a light-map build (vrt_multi_set_light_mode):
+        "replicated" or "sharded"; the light map is the same bits either way."""
+        return self._light_mode
+
+    @light_mode.setter
+    def light_mode(self, mode):
+        check(lib().vrt_multi_set_light_mode(self.h, self.LIGHT_MODES.get(mode, -1) if isinstance(mode, str)
+                                             else int(mode)), "vrt_multi_set_light_mode")
+        self._light_mode = mode if isinstance(mode, str) else {v: k for k, v in self.LIGHT_MODES.items()}[int(mode)]
+
+    def scene(self, rank):
+        """Rank `rank`'s scene (vrt_multi_scene) as a VoxelOctree that borrows
+        the handle's: lightmap_nodes(), lightmap_stats(), probe_sgs, ..."""
+        s = C.c_void_p()
+        check(lib().vrt_multi_scene(self.h, int(rank), C.byref(s)), "vrt_multi_scene")
+        return _RankScene(self, s)
+
+    def min_voxel(self, levels=0):
+        return self.scene(0).min_voxel(levels)
+
+    @property
+    def probe_sgs(self):
+        """Rank 0's stored SGs (every rank holds the same)."""
+        return self.scene(0).probe_sgs
+
+    @probe_sgs.setter
+    def probe_sgs(self, sgs):
+        """The stored SGs of every rank (vrt_multi_set_probe_sgs)."""
+        n = self.scene(0).probe_info()[0]
+        a, d, s = (np.asarray(sgs[k], np.float32) for k in ("a", "d", "s"))
+        if a.shape != (n, PROBE_SGS, 3) or d.shape != a.shape or s.shape != (n, PROBE_SGS):
+            raise ValueError(f"sgs must hold a, d ({n}, 14, 3) and s ({n}, 14), got {a.shape}, {d.shape}, {s.shape}")
+        rec = np.ascontiguousarray(np.concatenate([a, d, s[:, :, None]], axis=2))
+        check(lib().vrt_multi_set_probe_sgs(self.h, rec.ctypes.data_as(C.POINTER(_ffi.SGRec))),
+              "vrt_multi_set_probe_sgs")
+
+    def lightmap(self, light_cam, light_film):
+        """The light map on every rank (vrt_lightmap_build_multi); returns the
+        light pass's hit count."""
+        h = C.c_int64()
+        check(lib().vrt_lightmap_build_multi(self.h, C.byref(light_cam.c), C.byref(light_film.c), C.byref(h)),
+              "vrt_lightmap_build_multi")
+        return h.value
+
+    def render_trace(self, cam, film, min_voxel=0.0):
+        """The cone-traced view over the ranks' light maps -> (ny, nx, 3)."""
+        rgb = np.zeros((film.ny, film.nx, 3), np.float32)
+        check(lib().vrt_render_trace_multi(self.h, C.byref(cam.c), C.byref(film.c), float(min_voxel),
+                                           ptr(rgb, _ffi.f32p)), "vrt_render_trace_multi")
+        return rgb
+
+    def render_trace_device(self, cam, film, d_image_ptr, min_voxel=0.0, stream_ptr=None):
+        check(lib().vrt_render_trace_multi_device(self.h, C.byref(cam.c), C.byref(film.c), float(min_voxel),
+                                                  C.c_void_p(d_image_ptr),
+                                                  C.c_void_p(stream_ptr) if stream_ptr else None),
+              "vrt_render_trace_multi_device")
+
+    def trace_frame(self, light_cam, light_film, cam, film, min_voxel=0.0, light_color=None):
+        """The reference main() frame (vrt_trace_frame_multi) -> ((ny, nx, 3)
+        image, light hits).  light_color: on a probe handle, gather the probes
+        behind the filter on every rank (None keeps the stored SGs)."""
+        rgb = np.zeros((film.ny, film.nx, 3), np.float32)
+        h = C.c_int64()
+        lc = None if light_color is None else _f3(light_color)
+        check(lib().vrt_trace_frame_multi(self.h, C.byref(light_cam.c), C.byref(light_film.c), ptr(lc, _ffi.f32p),
+                                          C.byref(cam.c), C.byref(film.c), float(min_voxel), ptr(rgb, _ffi.f32p),
+                                          C.byref(h)), "vrt_trace_frame_multi")
+        return rgb, h.value
+
+    def trace_frame_device(self, light_cam, light_film, cam, film, d_image_ptr, min_voxel=0.0, light_color=None,
+                           stream_ptr=None):
+        """trace_frame into a device image on the first device, ordered on
+        stream_ptr as render_device is; returns the light pass's hit count."""
+        h = C.c_int64()
+        lc = None if light_color is None else _f3(light_color)
+        check(lib().vrt_trace_frame_multi_device(self.h, C.byref(light_cam.c), C.byref(light_film.c),
+                                                 ptr(lc, _ffi.f32p), C.byref(cam.c), C.byref(film.c),
+                                                 float(min_voxel), C.c_void_p(d_image_ptr),
+                                                 C.c_void_p(stream_ptr) if stream_ptr else None, C.byref(h)),
+              "vrt_trace_frame_multi_device")
+        return h.value
+
+
+class _RankScene(VoxelOctree):
+    """One rank's scene of a MultiOctree: the handle owns it."""
+
+    def __init__(self, multi, h):
+        self.multi = multi  # keeps the handle alive
+        self.scene = multi.scene_data
+        self.probes = multi.probes
+        self.h = h
+        self.max_depth = multi.max_depth
+        self.info = _ffi.SceneInfo()
+        check(lib().vrt_scene_info(self.h, C.byref(self.info)), "vrt_scene_info")
+
+    def close(self):
+        self.h = None
 
 
 def multi_tile_map(film, device_mask):

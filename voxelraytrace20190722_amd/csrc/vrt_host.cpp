@@ -1282,6 +1282,13 @@ int vrt::scene_replicate(const vrt_scene *src, const vrt_scene_desc *d, int devi
                 s->tex_bytes = src->tex_bytes;
                 s->info = src->info;
                 s->level_begin = src->level_begin;
+                // a probe scene's probes, per-node probe lists and masks, leaf
+                // lists and stored SGs (upload() makes their device copy)
+                s->probes = src->probes;
+                s->pnode = src->pnode;
+                s->pref = src->pref;
+                s->probe_sgs = src->probe_sgs;
+                s->probe_leaves = src->probe_leaves;
         } catch (const std::bad_alloc &) {
                 return fail(VRT_E_NOMEM, "scene replica: out of host memory");
         }
@@ -2370,13 +2377,32 @@ static hipError_t ensure_light_scratch(vrt_scene *s, size_t bytes)
         return s->d_light.alloc(bytes);
 }
 
-// The light pass + filter of VRT/main.cc:75-100 on the scene's stream
-// (caller holds s->mu).  `overlap` (may be empty) is called right after the
-// light pass is enqueued, before the one mid-build host sync, so work it
-// enqueues on another stream runs beside the light pass; on return the
-// filter is enqueued and *lm_done (if given) recorded after it.
-static int lightmap_enqueue(vrt_scene *s, int set, const vrt_camera *light_cam, const vrt_film *light_film,
-                            unsigned int *hits, const std::function<int()> &overlap, hipEvent_t lm_done)
+// One light-map build between its three steps: where its lists and counters
+// lie in the scene's light scratch, and what the host read at the sync.
+struct LightBuild {
+        int set = 0, kbits = 1, lbits = 1;
+        int64_t ns = 0;        // samples of the whole light film (what the scratch holds)
+        int64_t ns_rank = 0;   // samples this rank marches
+        size_t sort_bytes = 0;
+        int64_t max_seg = 1;
+        uint64_t *k_in = nullptr, *k_out = nullptr;
+        uint32_t *v_in = nullptr, *v_out = nullptr;
+        float *samp = nullptr;
+        void *temp = nullptr;
+        unsigned int *d_count = nullptr, *d_nseg = nullptr, *d_tail_n = nullptr;
+        uint32_t *d_seg = nullptr, *d_seg_end = nullptr;
+        LMRec *d_lm = nullptr;
+        float4 *d_cc = nullptr;
+        uint32_t *d_bad = nullptr;
+        unsigned int nhit = 0;  // this rank's hits (light_wait)
+};
+
+// The light pass + filter of VRT/main.cc:75-100 on the scene's stream in
+// three steps (caller holds s->mu).  Step 1: the leaf case of the filter and
+// the light march of rank `rank` of `nranks` of the light film's tile deal
+// (0 of 1: the whole film) into the compact hit lists.
+static int light_begin(vrt_scene *s, int set, const vrt_camera *light_cam, const vrt_film *light_film, int rank,
+                       int nranks, LightBuild *b)
 {
         const int64_t nnodes = (int64_t)s->nodes.size();
         const int ptx = light_film->nx / 8, pty = light_film->ny / 8;
@@ -2386,9 +2412,11 @@ static int lightmap_enqueue(vrt_scene *s, int set, const vrt_camera *light_cam, 
         // one block: light map, cone-descent records, finiteness flag
         if (int rc = ensure_lm(s, set))
                 return rc;
-        LMRec *d_lm = s->ts[set].lm.as<LMRec>();
-        float4 *d_cc = reinterpret_cast<float4 *>(d_lm + nnodes);
-        uint32_t *d_bad = reinterpret_cast<uint32_t *>(d_cc + nnodes);
+        b->set = set;
+        b->ns = ns;
+        b->d_lm = s->ts[set].lm.as<LMRec>();
+        b->d_cc = reinterpret_cast<float4 *>(b->d_lm + nnodes);
+        b->d_bad = reinterpret_cast<uint32_t *>(b->d_cc + nnodes);
         if (int rc = ts_acquire(s, set, s->stream))  // a trace render may still read this set
                 return rc;
         // scratch (sized for every sample hitting): 64-bit keys and 32-bit
@@ -2402,61 +2430,69 @@ static int lightmap_enqueue(vrt_scene *s, int set, const vrt_camera *light_cam, 
                 ++lbits;
         HIPCHK(sort_pairs_u64(nullptr, &sort_bytes, nullptr, nullptr, nullptr, nullptr, ns, kbits + lbits, s->stream));
         const size_t b4 = align_up((size_t)ns * 4), b8 = align_up((size_t)ns * 8), b24 = align_up((size_t)ns * 48);
-        const int64_t max_seg = std::max<int64_t>(1, s->info.nonempty_leaves);
-        const size_t bseg = align_up((size_t)max_seg * 4);
+        b->max_seg = std::max<int64_t>(1, s->info.nonempty_leaves);
+        const size_t bseg = align_up((size_t)b->max_seg * 4);
         const size_t bend = align_up((size_t)nnodes * 4);
         const size_t need = 2 * b8 + 2 * b4 + b24 + align_up(sort_bytes) + 256 + bseg + bend;
         HIPCHK(ensure_light_scratch(s, need));
         char *base = s->d_light.as<char>();
-        uint64_t *k_in = reinterpret_cast<uint64_t *>(base);
-        uint64_t *k_out = reinterpret_cast<uint64_t *>(base + b8);
-        uint32_t *v_in = reinterpret_cast<uint32_t *>(base + 2 * b8);
-        uint32_t *v_out = reinterpret_cast<uint32_t *>(base + 2 * b8 + b4);
-        float *samp = reinterpret_cast<float *>(base + 2 * b8 + 2 * b4);
-        void *temp = base + 2 * b8 + 2 * b4 + b24;
+        b->kbits = kbits;
+        b->lbits = lbits;
+        b->sort_bytes = sort_bytes;
+        b->k_in = reinterpret_cast<uint64_t *>(base);
+        b->k_out = reinterpret_cast<uint64_t *>(base + b8);
+        b->v_in = reinterpret_cast<uint32_t *>(base + 2 * b8);
+        b->v_out = reinterpret_cast<uint32_t *>(base + 2 * b8 + b4);
+        b->samp = reinterpret_cast<float *>(base + 2 * b8 + 2 * b4);
+        b->temp = base + 2 * b8 + 2 * b4 + b24;
         char *ctr = base + 2 * b8 + 2 * b4 + b24 + align_up(sort_bytes);
-        unsigned int *d_count = reinterpret_cast<unsigned int *>(ctr);
-        unsigned int *d_nseg = reinterpret_cast<unsigned int *>(ctr + 64);
-        unsigned int *d_tail_n = reinterpret_cast<unsigned int *>(ctr + 128);
-        uint32_t *d_seg = reinterpret_cast<uint32_t *>(ctr + 256);
-        uint32_t *d_seg_end = reinterpret_cast<uint32_t *>(ctr + 256 + bseg);
+        b->d_count = reinterpret_cast<unsigned int *>(ctr);
+        b->d_nseg = reinterpret_cast<unsigned int *>(ctr + 64);
+        b->d_tail_n = reinterpret_cast<unsigned int *>(ctr + 128);
+        b->d_seg = reinterpret_cast<uint32_t *>(ctr + 256);
+        b->d_seg_end = reinterpret_cast<uint32_t *>(ctr + 256 + bseg);
         LightParams lp;
         std::memset(&lp, 0, sizeof lp);
-        fill_render_params(s, light_cam, light_film, 0, 1, &lp.r);
+        fill_render_params(s, light_cam, light_film, rank, nranks, &lp.r);
+        lp.r.tile_xy = deal_map(s, ptx, pty, nranks, rank, s->stream);  // null for one rank
+        b->ns_rank = (int64_t)lp.r.tiles_this_rank * 256;
         lp.ptx = ptx;
         lp.pty = pty;
         lp.kbits = kbits;
-        lp.count = d_count;
-        lp.keys = k_in;
-        lp.vals = v_in;
-        lp.samp = samp;
-        lp.tail_n = d_tail_n;
-        lp.tail = v_out;  // free until the sort
+        lp.count = b->d_count;
+        lp.keys = b->k_in;
+        lp.vals = b->v_in;
+        lp.samp = b->samp;
+        lp.tail_n = b->d_tail_n;
+        lp.tail = b->v_out;  // free until the sort
         HIPCHK(hipEventRecord(s->ev0, s->stream));
         // cone_trace_init_filter's leaf case first: it also zeroes the
         // counters the passes below add to (no memsets)
-        HIPCHK(launch_lm_leaves(s->dev.nodes, nnodes, d_lm, d_bad, d_count, d_tail_n, d_nseg, s->stream));
+        HIPCHK(launch_lm_leaves(s->dev.nodes, nnodes, b->d_lm, b->d_bad, b->d_count, b->d_tail_n, b->d_nseg, s->stream));
         // a leaf whose list holds probes only is non-empty too: coverage 1
         if (!s->probes.empty())
-                HIPCHK(launch_lm_probe_leaves(s->dev.nodes, s->pdev.pnode, nnodes, d_lm, s->stream));
+                HIPCHK(launch_lm_probe_leaves(s->dev.nodes, s->pdev.pnode, nnodes, b->d_lm, s->stream));
         HIPCHK(launch_light(lp, s->stream));
-        if (overlap)
-                if (int rc = overlap())
-                        return rc;
-        // the sort takes its length on the host: the one mid-build sync
-        // (the same copy reaches to the tail's sample count, final once
-        // k_light has run: for vrt_lightmap_stats)
+        return VRT_OK;
+}
+
+// Step 2: the sort takes its length on the host, the one mid-build sync (the
+// same copy reaches to the tail's sample count, final once k_light has run:
+// for vrt_lightmap_stats).
+static int light_wait(vrt_scene *s, LightBuild *b)
+{
         unsigned int ctrs[33] = {};  // d_count at word 0, d_tail_n at word 32
-        HIPCHK(hipMemcpyAsync(ctrs, d_count, sizeof ctrs, hipMemcpyDeviceToHost, s->stream));
+        HIPCHK(hipMemcpyAsync(ctrs, b->d_count, sizeof ctrs, hipMemcpyDeviceToHost, s->stream));
         HIPCHK(hipStreamSynchronize(s->stream));
         const unsigned int nhit = ctrs[0], ntail = ctrs[32];
-        s->lm_stats[0] = ns;
+        b->nhit = nhit;
+        s->lm_stats[0] = b->ns_rank;
         s->lm_stats[1] = nhit;
         s->lm_stats[2] = ntail;
 #ifdef VRT_LIGHT_DIAG
         {
                 static int ndump = 0;
-                const size_t nw = (size_t)std::min<int64_t>(ns / 64, 1 << 20);
+                const size_t nw = (size_t)std::min<int64_t>(b->ns / 64, 1 << 20);
                 std::vector<uint32_t> d(nw * 8);
                 HIPCHK(light_diag_copy(d.data(), d.size() * 4));
                 char name[64];
@@ -2468,23 +2504,56 @@ static int lightmap_enqueue(vrt_scene *s, int set, const vrt_camera *light_cam, 
         }
 #endif
 #ifdef VRT_LIGHT_TAIL_REPORT
-        std::fprintf(stderr, "light pass: %u of %lld samples deferred, %u hits\n", ntail, (long long)ns, nhit);
+        std::fprintf(stderr, "light pass: %u of %lld samples deferred, %u hits\n", ntail, (long long)b->ns_rank, nhit);
 #endif
-        if (nhit > 0)
-                HIPCHK(sort_pairs_u64(temp, &sort_bytes, k_in, k_out, v_in, v_out, nhit, kbits + lbits, s->stream));
-        HIPCHK(launch_lm_accum(nhit, k_out, v_out, kbits, samp, d_seg, d_nseg, max_seg, d_seg_end, d_lm,
-                               s->stream));
+        return VRT_OK;
+}
+
+// Step 3: sort the `total` hits of the lists (merged: the ranks' lists were
+// exchanged into them, so the slots are renumbered first), the per-leaf sums
+// in canonical order, the filter's internal levels; *lm_done (if given) is
+// recorded after it.
+static int light_finish(vrt_scene *s, LightBuild *b, unsigned int total, bool merged, hipEvent_t lm_done)
+{
+        const int64_t nnodes = (int64_t)s->nodes.size();
+        if (merged)
+                HIPCHK(launch_lm_slots(b->v_in, total, s->stream));
+        if (total > 0)
+                HIPCHK(sort_pairs_u64(b->temp, &b->sort_bytes, b->k_in, b->k_out, b->v_in, b->v_out, total,
+                                      b->kbits + b->lbits, s->stream));
+        HIPCHK(launch_lm_accum(total, b->k_out, b->v_out, b->kbits, b->samp, b->d_seg, b->d_nseg, b->max_seg,
+                               b->d_seg_end, b->d_lm, s->stream));
         // cone_trace_init_filter: internal levels bottom-up
         const int nlev = (int)s->level_begin.size() - 1;
         for (int l = nlev; l >= 1; --l)
-                HIPCHK(launch_lm_level(s->dev.nodes, s->level_begin[l - 1], s->level_begin[l], d_lm, s->stream));
-        HIPCHK(launch_lm_aux(s->dev.nodes, d_lm, nnodes, d_cc, d_bad, s->stream));
+                HIPCHK(launch_lm_level(s->dev.nodes, s->level_begin[l - 1], s->level_begin[l], b->d_lm, s->stream));
+        HIPCHK(launch_lm_aux(s->dev.nodes, b->d_lm, nnodes, b->d_cc, b->d_bad, s->stream));
         HIPCHK(hipEventRecord(s->ev1, s->stream));
         if (lm_done)
                 HIPCHK(hipEventRecord(lm_done, s->stream));
         s->timed = true;
-        s->lm_cur = set;
-        *hits = nhit;
+        s->lm_cur = b->set;
+        return VRT_OK;
+}
+
+// The three steps in one call.  `overlap` (may be empty) is called right after
+// the light pass is enqueued, before the mid-build host sync, so work it
+// enqueues on another stream runs beside the light pass; on return the filter
+// is enqueued and *lm_done (if given) recorded after it.
+static int lightmap_enqueue(vrt_scene *s, int set, const vrt_camera *light_cam, const vrt_film *light_film,
+                            unsigned int *hits, const std::function<int()> &overlap, hipEvent_t lm_done)
+{
+        LightBuild b;
+        if (int rc = light_begin(s, set, light_cam, light_film, 0, 1, &b))
+                return rc;
+        if (overlap)
+                if (int rc = overlap())
+                        return rc;
+        if (int rc = light_wait(s, &b))
+                return rc;
+        if (int rc = light_finish(s, &b, b.nhit, false, lm_done))
+                return rc;
+        *hits = b.nhit;
         return VRT_OK;
 }
 
@@ -3738,88 +3807,244 @@ static int render_trace_host(vrt_scene *s, FramePath fp, const vrt_camera *cam, 
 // sync); the image is ordered on `stream`.  The gather's records follow the
 // view's in the set's block, and the gather builds the step table (the
 // primary march does not read it).
+//
+// In three steps, for the single-scene calls (one after the other) and the
+// multi-device handle (each step on every rank before the next), so the ranks'
+// light passes do not queue behind each other's host sync:
+//   frame_begin   the light march of the job's share of the light film and,
+//                 beside it, the view's primary march;
+//   frame_wait    the mid-build sync: the rank's hit count and its lists;
+//   frame_finish  sort + sums + filter over `total` hits, the optional probe
+//                 gather, the cones + film pass.
+// A job without a view camera (the handle's light-map build, or a view with no
+// tile) is the light-map build alone.  The job holds s->mu from frame_begin to
+// frame_finish / frame_abort, which free it.
+struct vrt::FrameJob {
+        vrt_scene *s = nullptr;
+        std::unique_lock<std::mutex> lk;
+        FramePath fp{ "", true };
+        bool view = false, gather = false;
+        bool started = false;  // something is enqueued: a failure takes the bail path
+        int set = 0;
+        hipStream_t st = nullptr;
+        float min_voxel = 0.f;
+        float light[3] = {};
+        size_t view_slots = 0;
+        TraceParams tp;
+        LightBuild lb;
+};
+
+// whatever was enqueued on either stream (the light pass and the gather on
+// the scene's, the primary march on the caller's) finishes before the set's
+// next user starts
+static int frame_bail(FrameJob *j, int rc)
+{
+        vrt_scene *s = j->s;
+        if (j->started && j->view) {
+                if (hipEventRecord(s->lm_ev, s->stream) == hipSuccess)
+                        (void)hipStreamWaitEvent(j->st, s->lm_ev, 0);
+                (void)ts_release(s, j->set, j->st);
+        }
+        delete j;
+        return rc;
+}
+
+int vrt::frame_check(vrt_scene *s, const FrameArgs &a)
+{
+        // without a light film: the view over the current light map alone
+        FramePath fp{ a.what, true };
+        const bool has_light = a.light_film != nullptr;
+        return frame_args_ok(s, &fp, a.cam && (a.light_cam || !has_light), has_light, a.light_film, a.film, a.rank,
+                             a.nranks, a.image_layout, a.min_voxel);
+}
+
+int vrt::frame_begin(vrt_scene *s, const FrameArgs &a, FrameJob **out)
+{
+        *out = nullptr;
+        FramePath fp{ a.what, a.may_probe };
+        if (a.cam) {
+                if (int rc = frame_args_ok(s, &fp, a.light_cam && a.d_out, true, a.light_film, a.film, a.rank, a.nranks,
+                                           a.image_layout, a.min_voxel))
+                        return rc;
+        } else {
+                if (s && need_device(s))
+                        return VRT_E_NODEVICE;
+                if (!s || !a.light_cam)
+                        return fail(VRT_E_INVALID, "null argument");
+                if (int rc = film_ok(a.light_film))
+                        return rc;
+        }
+        if (a.light_nranks < 1 || a.light_rank < 0 || a.light_rank >= a.light_nranks)
+                return fail(VRT_E_INVALID, "light rank %d of %d", a.light_rank, a.light_nranks);
+        std::unique_ptr<FrameJob> job(new (std::nothrow) FrameJob);
+        if (!job)
+                return fail(VRT_E_NOMEM, "frame job alloc");
+        FrameJob *j = job.get();
+        j->s = s;
+        j->lk = std::unique_lock<std::mutex>(s->mu);
+        j->fp = fp;
+        j->view = a.cam != nullptr;
+        j->st = a.stream;
+        j->min_voxel = a.min_voxel;
+        HIPCHK(hipSetDevice(s->device));
+        if (j->view && !s->lm_ev)
+                HIPCHK(s->lm_ev.create(hipEventDisableTiming));
+        if (j->view && fp.probe && !s->sg_ev)
+                HIPCHK(s->sg_ev.create(hipEventDisableTiming));
+        j->gather = j->view && fp.probe && a.light_color != nullptr;
+        if (j->gather)
+                std::memcpy(j->light, a.light_color, sizeof j->light);
+        // alternate sets: this frame's light pass waits only for the frame
+        // before last (the set's previous user), so it runs beside the
+        // previous frame's cone-traced shading
+        const int set = j->set = s->ts_next;
+        s->ts_next ^= 1;
+        if (j->view) {
+                if (int rc = ensure_lm(s, set))  // the trace parameters point into it
+                        return rc;
+                TraceParams tp0;
+                fill_trace_params(s, set, a.cam, a.film, a.min_voxel, a.rank, a.nranks, &tp0);
+                tp0.r.image_layout = a.image_layout;
+                tp0.r.out = a.d_out;
+                // the view's records first, then (gather) one chunk of the gather's
+                const int64_t nprobe = (int64_t)s->probes.size();
+                j->view_slots = (size_t)tp0.r.tiles_this_rank * 256;
+                const size_t gather_slots =
+                        j->gather ? (size_t)std::min(nprobe, probe_chunk(100)) * kProbeSGs * 100 : 0;
+                if (int rc = trace_scratch_n(s, set, tp0, j->view_slots + gather_slots, &j->tp))
+                        return rc;
+                if (j->gather)
+                        j->tp.build_steps = 0;  // the gather builds the table, on the scene's stream
+        }
+        j->started = true;
+        job.release();
+        if (int rc = light_begin(s, set, a.light_cam, a.light_film, a.light_rank, a.light_nranks, &j->lb))
+                return frame_bail(j, rc);
+        if (j->view) {
+                // the view's primary march beside the light pass (its records
+                // wait only for the previous frame's users of the scratch)
+                if (int rc = ts_acquire(s, set, j->st))
+                        return frame_bail(j, rc);
+                if (hipError_t e = frame_prim(s, set, j->tp, j->fp, j->st))
+                        return frame_bail(j, fail(VRT_E_DEVICE, "primary march launch failed: %s", hipGetErrorString(e)));
+        }
+        *out = j;
+        return VRT_OK;
+}
+
+int vrt::frame_wait(FrameJob *j, LightList *l)
+{
+        vrt_scene *s = j->s;
+        if (hipSetDevice(s->device) != hipSuccess)
+                return frame_bail(j, fail(VRT_E_DEVICE, "hipSetDevice failed"));
+        if (int rc = light_wait(s, &j->lb))
+                return frame_bail(j, rc);
+        if (l) {
+                l->keys = j->lb.k_in;
+                l->samp = j->lb.samp;
+                l->n = j->lb.nhit;
+                l->cap = (uint64_t)j->lb.ns;
+                l->stream = s->stream;
+        }
+        return VRT_OK;
+}
+
+int vrt::frame_finish(FrameJob *j, unsigned int total, bool merged)
+{
+        vrt_scene *s = j->s;
+        const int set = j->set;
+        if (hipSetDevice(s->device) != hipSuccess)
+                return frame_bail(j, fail(VRT_E_DEVICE, "hipSetDevice failed"));
+        if (int rc = light_finish(s, &j->lb, total, merged, j->view ? s->lm_ev.get() : nullptr))
+                return frame_bail(j, rc);
+        if (!j->view) {
+                const int rc = ts_release(s, set, s->stream);
+                delete j;
+                return rc;
+        }
+        hipEvent_t last = s->lm_ev;  // what the cones + film pass waits for
+        if (j->gather) {
+                ProbeIO io{};
+                io.probes = reinterpret_cast<const float *>(s->pdev.probes);
+                io.n = (int64_t)s->probes.size();
+                io.npoints = 100;
+                std::memcpy(io.light, j->light, sizeof io.light);
+                io.sgs = s->d_sgs;
+                // the other set's last user may still read the device SGs
+                if (int rc = ts_acquire(s, set ^ 1, s->stream))
+                        return frame_bail(j, rc);
+                s->sgs_stale = true;
+                if (int rc = probe_enqueue(s, io, probe_default_points(), j->min_voxel, s->stream, j->view_slots))
+                        return frame_bail(j, rc);
+                last = s->sg_ev;
+                if (hipError_t e = hipEventRecord(last, s->stream))
+                        return frame_bail(j, fail(VRT_E_DEVICE, "hipEventRecord failed: %s", hipGetErrorString(e)));
+        }
+        hipError_t e = hipStreamWaitEvent(j->st, last, 0);
+        if (e == hipSuccess)
+                e = frame_cones(s, j->tp, j->fp, j->st);
+        if (e != hipSuccess)
+                return frame_bail(j, fail(VRT_E_DEVICE, "cone pass launch failed: %s", hipGetErrorString(e)));
+        const int rc = ts_release(s, set, j->st);
+        delete j;
+        return rc;
+}
+
+void vrt::frame_abort(FrameJob *j)
+{
+        if (j) {
+                (void)hipSetDevice(j->s->device);
+                (void)frame_bail(j, VRT_OK);
+        }
+}
+
+bool vrt::scene_has_lightmap(vrt_scene *s)
+{
+        std::lock_guard<std::mutex> lk(s->mu);
+        return s->lm_cur >= 0;
+}
+
+int vrt::scene_stream_sync(vrt_scene *s)
+{
+        std::lock_guard<std::mutex> lk(s->mu);
+        HIPCHK(hipSetDevice(s->device));
+        HIPCHK(hipStreamSynchronize(s->stream));
+        return VRT_OK;
+}
+
 static int trace_frame_device(vrt_scene *s, FramePath fp, const vrt_camera *light_cam, const vrt_film *light_film,
                               const float *light_color, const vrt_camera *cam, const vrt_film *film,
                               float min_voxel, int rank, int nranks, int image_layout, float *d_out, void *stream,
                               int64_t *hits)
 {
-        if (int rc = frame_args_ok(s, &fp, light_cam && cam && d_out, true, light_film, film, rank, nranks,
-                                   image_layout, min_voxel))
+        if (!cam)  // a job without a view is the handle's; here a null argument
+                return frame_args_ok(s, &fp, false, true, light_film, film, rank, nranks, image_layout, min_voxel);
+        FrameArgs a{};
+        a.what = fp.what;
+        a.may_probe = fp.may_probe;
+        a.light_cam = light_cam;
+        a.light_film = light_film;
+        a.light_color = light_color;
+        a.light_rank = 0;
+        a.light_nranks = 1;
+        a.cam = cam;
+        a.film = film;
+        a.min_voxel = min_voxel;
+        a.rank = rank;
+        a.nranks = nranks;
+        a.image_layout = image_layout;
+        a.d_out = d_out;
+        a.stream = static_cast<hipStream_t>(stream);
+        FrameJob *j = nullptr;
+        if (int rc = frame_begin(s, a, &j))
                 return rc;
-        std::lock_guard<std::mutex> lk(s->mu);
-        HIPCHK(hipSetDevice(s->device));
-        hipStream_t st = static_cast<hipStream_t>(stream);
-        if (!s->lm_ev)
-                HIPCHK(s->lm_ev.create(hipEventDisableTiming));
-        if (fp.probe && !s->sg_ev)
-                HIPCHK(s->sg_ev.create(hipEventDisableTiming));
-        const bool gather = fp.probe && light_color != nullptr;
-        // alternate sets: this frame's light pass waits only for the frame
-        // before last (the set's previous user), so it runs beside the
-        // previous frame's cone-traced shading
-        const int set = s->ts_next;
-        s->ts_next ^= 1;
-        if (int rc = ensure_lm(s, set))  // the trace parameters point into it
+        LightList l{};
+        if (int rc = frame_wait(j, &l))
                 return rc;
-        TraceParams tp0, tp;
-        fill_trace_params(s, set, cam, film, min_voxel, rank, nranks, &tp0);
-        tp0.r.image_layout = image_layout;
-        tp0.r.out = d_out;
-        // the view's records first, then (gather) one chunk of the gather's
-        const int64_t nprobe = (int64_t)s->probes.size();
-        const size_t view_slots = (size_t)tp0.r.tiles_this_rank * 256;
-        const size_t gather_slots = gather ? (size_t)std::min(nprobe, probe_chunk(100)) * kProbeSGs * 100 : 0;
-        if (int rc = trace_scratch_n(s, set, tp0, view_slots + gather_slots, &tp))
-                return rc;
-        if (gather)
-                tp.build_steps = 0;  // the gather builds the table, on the scene's stream
-        unsigned int nhit = 0;
-        auto overlap = [&]() -> int {
-                // the view's primary march beside the light pass (its records
-                // wait only for the previous frame's users of the scratch)
-                if (int rc = ts_acquire(s, set, st))
-                        return rc;
-                HIPCHK(frame_prim(s, set, tp, fp, st));
-                return VRT_OK;
-        };
-        auto bail = [&](int rc) {
-                // whatever was enqueued on either stream (the light pass and
-                // the gather on the scene's, the primary march on the
-                // caller's) finishes before the set's next user starts
-                if (hipEventRecord(s->lm_ev, s->stream) == hipSuccess)
-                        (void)hipStreamWaitEvent(st, s->lm_ev, 0);
-                (void)ts_release(s, set, st);
-                return rc;
-        };
-        if (int rc = lightmap_enqueue(s, set, light_cam, light_film, &nhit, overlap, s->lm_ev))
-                return bail(rc);
-        hipEvent_t last = s->lm_ev;  // what the cones + film pass waits for
-        if (gather) {
-                ProbeIO io{};
-                io.probes = reinterpret_cast<const float *>(s->pdev.probes);
-                io.n = nprobe;
-                io.npoints = 100;
-                std::memcpy(io.light, light_color, sizeof io.light);
-                io.sgs = s->d_sgs;
-                // the other set's last user may still read the device SGs
-                if (int rc = ts_acquire(s, set ^ 1, s->stream))
-                        return bail(rc);
-                s->sgs_stale = true;
-                if (int rc = probe_enqueue(s, io, probe_default_points(), min_voxel, s->stream, view_slots))
-                        return bail(rc);
-                last = s->sg_ev;
-                if (hipError_t e = hipEventRecord(last, s->stream))
-                        return bail(fail(VRT_E_DEVICE, "hipEventRecord failed: %s", hipGetErrorString(e)));
-        }
-        hipError_t e = hipStreamWaitEvent(st, last, 0);
-        if (e == hipSuccess)
-                e = frame_cones(s, tp, fp, st);
-        if (e != hipSuccess)
-                return bail(fail(VRT_E_DEVICE, "cone pass launch failed: %s", hipGetErrorString(e)));
-        if (int rc = ts_release(s, set, st))
+        if (int rc = frame_finish(j, l.n, false))
                 return rc;
         if (hits)
-                *hits = (int64_t)nhit;
+                *hits = (int64_t)l.n;
         return VRT_OK;
 }
 

@@ -594,6 +594,45 @@ hipError_t build_tree_device(int device, const float *pos, int ntri, const float
 // Host helpers shared by vrt_host.cpp and vrt_multi.cpp (hidden symbols).
 // scene_replicate: src's host-side build uploaded to another device.
 int scene_replicate(const vrt_scene *src, const vrt_scene_desc *d, int device, vrt_scene **out);
+// The trace() frame of one scene in three steps (vrt_host.cpp, "the trace()
+// frames"): frame_begin enqueues the light march of rank light_rank of
+// light_nranks of the light film's tile deal and, with a view camera, the
+// view's primary march on `stream`; frame_wait is the build's one host sync
+// and gives the rank's hit lists; frame_finish sorts `total` hits (merged:
+// other ranks' lists were appended behind the rank's own), filters, and
+// enqueues the cones + film pass.  cam == nullptr: the light map alone.  A
+// failed step has released the job; frame_abort releases one that is not
+// going on.  frame_check: the arguments alone, nothing enqueued.
+struct FrameJob;
+struct FrameArgs {
+        const char *what;
+        bool may_probe;
+        const vrt_camera *light_cam;
+        const vrt_film *light_film;
+        const float *light_color;
+        int light_rank, light_nranks;
+        const vrt_camera *cam;
+        const vrt_film *film;
+        float min_voxel;
+        int rank, nranks, image_layout;
+        float *d_out;
+        hipStream_t stream;
+};
+struct LightList {
+        uint64_t *keys;  // n keys (leaf << kbits | canonical sample index), room for cap
+        float *samp;     // n records of 6 floats, room for 2 * cap
+        unsigned int n;
+        uint64_t cap;
+        hipStream_t stream;  // the scene's stream, where the lists are written and read
+};
+int frame_check(vrt_scene *s, const FrameArgs &a);
+int frame_begin(vrt_scene *s, const FrameArgs &a, FrameJob **out);
+int frame_wait(FrameJob *j, LightList *l);
+int frame_finish(FrameJob *j, unsigned int total, bool merged);
+void frame_abort(FrameJob *j);
+bool scene_has_lightmap(vrt_scene *s);
+// the scene's own stream (light pass, filter, probe gather) is idle
+int scene_stream_sync(vrt_scene *s);
 // memcpy of a large host range over up to 4 threads.
 void par_memcpy(void *dst, const void *src, size_t bytes);
 // the process-wide vrt_set_test_flags value
@@ -780,6 +819,8 @@ hipError_t light_diag_copy(void *host, size_t bytes);  // VRT_LIGHT_DIAG builds
 // seg_start: max_seg entries (>= non-empty leaves), nseg zeroed (by
 // launch_lm_leaves); seg_end: one entry per node (each hit leaf's run end is
 // written)
+// vals[i] = i for i < n: the slots of a hit list merged from several ranks'
+hipError_t launch_lm_slots(uint32_t *vals, int64_t n, hipStream_t st);
 hipError_t launch_lm_accum(int64_t n, const uint64_t *keys_sorted, const uint32_t *vals_sorted, int kbits,
                            const float *samp, uint32_t *seg_start, unsigned int *nseg,
                            int64_t max_seg, uint32_t *seg_end, LMRec *lm, hipStream_t st);

@@ -4435,6 +4435,15 @@ __global__ __launch_bounds__(64, VRT_TAIL_WAVES_PER_EU) void k_light_tail(LightP
         }
 }
 
+// A hit list merged from several ranks' lists (the sharded light pass of the
+// multi-device handle): each record's slot is its position in the merged list.
+__global__ __launch_bounds__(256) void k_lm_slots(int64_t n, uint32_t *__restrict__ vals)
+{
+        const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+        if (i < n)
+                vals[i] = (uint32_t)i;
+}
+
 // Permute the per-sample records into the sorted (leaf, canonical) order so
 // the serial per-leaf sums below stream contiguous memory.
 __global__ __launch_bounds__(256) void k_lm_gather(int64_t n, const uint32_t *__restrict__ vals,
@@ -5577,6 +5586,14 @@ hipError_t launch_light(const LightParams &p, hipStream_t st)
         if (VRT_LIGHT_BUDGET > 0 || (p.r.test_flags & VRT_TEST_LIGHT_TAIL))
                 hipLaunchKernelGGL(p.r.sc.wide_leaves ? k_light_tail<true> : k_light_tail<false>,
                                    dim3(VRT_LIGHT_TAIL_GRID), dim3(64), 0, st, p);
+        return hipGetLastError();
+}
+
+hipError_t launch_lm_slots(uint32_t *vals, int64_t n, hipStream_t st)
+{
+        if (n <= 0)
+                return hipSuccess;
+        hipLaunchKernelGGL(k_lm_slots, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, n, vals);
         return hipGetLastError();
 }
 

@@ -16,6 +16,7 @@
 #include <rccl/rccl.h>
 
 #include <cstring>
+#include <functional>
 #include <memory>
 #include <mutex>
 #include <string>
@@ -36,6 +37,8 @@ struct vrt_multi {
         size_t tpr_cap = 0;             // tiles per rank the buffers hold
         Staging img;                    // vrt_render_multi: image on rank 0's device, its pinned copy; on st[0]
         Event ev_in;                    // caller's stream -> rank 0's stream
+        int light_mode = VRT_MULTI_LIGHT_REPLICATED;  // vrt_multi_set_light_mode
+        std::vector<Event> ev_x;        // virtual ranks, sharded light pass: rank i has read the others' hit lists
         std::mutex mu;
 };
 
@@ -138,8 +141,15 @@ int gather(vrt_multi *m, size_t count)
         return VRT_OK;
 }
 
-// One frame into d_image on rank 0's device (caller holds m->mu).
-int render_multi(vrt_multi *m, const vrt_camera *cam, const vrt_film *film, float *d_image, hipStream_t caller)
+// What every rank enqueues for one frame: dst[i] is rank i's packed tile
+// buffer (tpr * 192 floats, written on m->st[i]), or null when the film has no
+// tile.  It enqueues nothing collective, and after a failure it has
+// synchronised whatever it started.
+using RankWork = std::function<int(const std::vector<float *> &dst)>;
+
+// One frame into d_image on rank 0's device (caller holds m->mu): the ranks'
+// work, the gather, the unpack.
+int frame_multi(vrt_multi *m, const vrt_film *film, float *d_image, hipStream_t caller, const RankWork &work)
 {
         const int n = (int)m->devs.size();
         const int tpr = vrt_tiles_per_rank(film, n);
@@ -161,16 +171,16 @@ int render_multi(vrt_multi *m, const vrt_camera *cam, const vrt_film *film, floa
                 HIPCHK(hipEventRecord(m->ev_in, caller));
                 HIPCHK(hipStreamWaitEvent(m->st[0], m->ev_in, 0));
         }
-        if (tpr > 0) {
-                // each rank's share, packed tile-major (vrt_render_tiles_device)
-                for (int i = 0; i < n; ++i) {
-                        float *dst = (i == 0 ? m->gath : m->send[i]).as<float>();
-                        if (int rc = vrt_render_tiles_device(m->sc[i], cam, film, i, n, 0, dst, m->st[i]))
-                                return rc;
-                }
+        // each rank's share, packed tile-major
+        std::vector<float *> dst(n, nullptr);
+        if (tpr > 0)
+                for (int i = 0; i < n; ++i)
+                        dst[i] = (i == 0 ? m->gath : m->send[i]).as<float>();
+        if (int rc = work(dst))
+                return rc;
+        if (tpr > 0)
                 if (int rc = gather(m, count))
                         return rc;
-        }
         HIPCHK(hipSetDevice(m->devs[0]));
         if (tpr > 0) {
                 if (int rc = vrt_unpack_tiles_device(film, n, m->gath.as<float>(), d_image, m->st[0]))
@@ -183,6 +193,237 @@ int render_multi(vrt_multi *m, const vrt_camera *cam, const vrt_film *film, floa
                 HIPCHK(hipStreamWaitEvent(caller, m->ev[0], 0));
         }
         return VRT_OK;
+}
+
+// A frame call's two outputs: the host array rgb (through m->img), or d_image
+// ordered on `stream` (null: complete on return).
+int frame_out(vrt_multi *m, const vrt_film *film, float *rgb, float *d_image, void *stream, const RankWork &work)
+{
+        std::lock_guard<std::mutex> lk(m->mu);
+        DeviceGuard g;
+        if (!rgb) {
+                if (int rc = frame_multi(m, film, d_image, static_cast<hipStream_t>(stream), work))
+                        return rc;
+                if (!stream)  // no caller stream: the image is complete on return
+                        return sync_all(m);
+                return VRT_OK;
+        }
+        const size_t bytes = (size_t)film->nx * film->ny * 12;
+        HIPCHK(hipSetDevice(m->devs[0]));
+        HIPCHK(m->img.grow(bytes, m->st[0]));
+        // the unpack writes every pixel (zero outside the tile grid)
+        if (int rc = frame_multi(m, film, m->img.d.as<float>(), nullptr, work))
+                return rc;
+        HIPCHK(hipSetDevice(m->devs[0]));
+        HIPCHK(hipMemcpyAsync(m->img.h, m->img.d, bytes, hipMemcpyDeviceToHost, m->st[0]));
+        if (int rc = sync_all(m))
+                return rc;
+        par_memcpy(rgb, m->img.h, bytes);
+        return VRT_OK;
+}
+
+bool film_bad(const vrt_film *film)
+{
+        return film->nx < 1 || film->ny < 1 || film->nx > 32768 || film->ny > 32768;
+}
+
+// the primary frame: vrt_render_tiles_device with rank i of n
+RankWork primary_work(vrt_multi *m, const vrt_camera *cam, const vrt_film *film)
+{
+        return [=](const std::vector<float *> &dst) -> int {
+                for (size_t i = 0; i < dst.size(); ++i)
+                        if (dst[i])
+                                if (int rc = vrt_render_tiles_device(m->sc[i], cam, film, (int)i, (int)dst.size(), 0, dst[i],
+                                                                     m->st[i]))
+                                        return rc;
+                return VRT_OK;
+        };
+}
+
+// Every rank's streams (the handle's and the scenes') are idle; the error of
+// the failed step stays the last error.
+int fail_synced(vrt_multi *m, int rc)
+{
+        const std::string err = vrt_last_error();
+        (void)sync_all(m);
+        for (vrt_scene *s : m->sc)
+                (void)scene_stream_sync(s);
+        return set_error(rc, "%s", err.c_str());
+}
+
+// Sharded light pass: every rank receives every other rank's keys and records
+// behind its own (other ranks in rank order; order within the list is
+// irrelevant), on the ranks' scene streams.  The source lists are complete:
+// their counts were read after a stream sync.  A rank's stream goes on (to the
+// sort, and later to the next march into the same lists) only when every other
+// rank has read its list.
+int exchange_lists(vrt_multi *m, const std::vector<LightList> &l)
+{
+        const int n = (int)l.size();
+        if (m->virt) {
+                HIPCHK(hipSetDevice(m->devs[0]));
+                for (int d = 0; d < n; ++d) {
+                        size_t off = l[d].n;
+                        for (int r = 0; r < n; ++r) {
+                                if (r == d || l[r].n == 0)
+                                        continue;
+                                HIPCHK(hipMemcpyAsync(l[d].keys + off, l[r].keys, (size_t)l[r].n * 8,
+                                                      hipMemcpyDeviceToDevice, l[d].stream));
+                                HIPCHK(hipMemcpyAsync(l[d].samp + 6 * off, l[r].samp, (size_t)l[r].n * 24,
+                                                      hipMemcpyDeviceToDevice, l[d].stream));
+                                off += l[r].n;
+                        }
+                        HIPCHK(hipEventRecord(m->ev_x[d], l[d].stream));
+                }
+                for (int r = 0; r < n; ++r)
+                        for (int d = 0; d < n; ++d)
+                                if (d != r)
+                                        HIPCHK(hipStreamWaitEvent(l[r].stream, m->ev_x[d], 0));
+                return VRT_OK;
+        }
+        // one broadcast of the keys and one of the records per root with hits
+        // (zero-length ones skipped on all ranks alike), in one group; the
+        // root's list stays in place
+        NCCLCHK(ncclGroupStart());
+        for (int r = 0; r < n; ++r) {
+                if (l[r].n == 0)
+                        continue;
+                for (int i = 0; i < n; ++i) {
+                        size_t off = 0;  // where root r's list lies on rank i
+                        if (i != r) {
+                                off = l[i].n;
+                                for (int q = 0; q < r; ++q)
+                                        if (q != i)
+                                                off += l[q].n;
+                        }
+                        ncclResult_t e = ncclBroadcast(l[i].keys + off, l[i].keys + off, l[r].n, ncclUint64, r, m->comm[i],
+                                                       l[i].stream);
+                        if (e == ncclSuccess)
+                                e = ncclBroadcast(l[i].samp + 6 * off, l[i].samp + 6 * off, (size_t)l[r].n * 6, ncclFloat32,
+                                                  r, m->comm[i], l[i].stream);
+                        if (e != ncclSuccess) {
+                                (void)ncclGroupEnd();
+                                return set_error(VRT_E_DEVICE, "ncclBroadcast (root %d, rank %d): %s", r, i,
+                                                 ncclGetErrorString(e));
+                        }
+                }
+        }
+        NCCLCHK(ncclGroupEnd());
+        return VRT_OK;
+}
+
+// The trace() frame's (or, with cam == nullptr or no tile, the light-map
+// build's) per-rank work in its three steps, each on every rank before the
+// next: the ranks' light passes run beside each other, not behind each
+// other's host sync.  a: the call's arguments; rank, buffer and stream are
+// filled in per rank.
+int trace_work(vrt_multi *m, FrameArgs a, const std::vector<float *> &dst, int64_t *hits)
+{
+        const int n = (int)m->devs.size();
+        const bool sharded = m->light_mode == VRT_MULTI_LIGHT_SHARDED && n > 1;
+        const vrt_camera *cam = a.cam;
+        std::vector<FrameJob *> job(n, nullptr);
+        std::vector<LightList> l(n);
+        auto bail = [&](int rc) {
+                const std::string err = vrt_last_error();
+                for (FrameJob *j : job)
+                        frame_abort(j);
+                (void)set_error(rc, "%s", err.c_str());
+                return fail_synced(m, rc);
+        };
+        for (int i = 0; i < n; ++i) {
+                a.cam = dst[i] ? cam : nullptr;
+                a.rank = i;
+                a.nranks = n;
+                a.image_layout = 0;
+                a.d_out = dst[i];
+                a.stream = m->st[i];
+                a.light_rank = sharded ? i : 0;
+                a.light_nranks = sharded ? n : 1;
+                if (int rc = frame_begin(m->sc[i], a, &job[i]))
+                        return bail(rc);
+        }
+        for (int i = 0; i < n; ++i) {
+                FrameJob *j = job[i];
+                job[i] = nullptr;  // a failed step has released it
+                if (int rc = frame_wait(j, &l[i]))
+                        return bail(rc);
+                job[i] = j;
+        }
+        uint64_t total = l[0].n;
+        for (int i = 1; i < n; ++i) {
+                if (sharded)
+                        total += l[i].n;
+                else if (l[i].n != l[0].n)
+                        return bail(set_error(VRT_E_DEVICE, "replicas diverged: rank %d counts %u light hits, rank 0 %u", i,
+                                              l[i].n, l[0].n));
+        }
+        if (total > l[0].cap)
+                return bail(set_error(VRT_E_DEVICE, "light pass: %llu hits of %llu samples", (unsigned long long)total,
+                                      (unsigned long long)l[0].cap));
+        if (sharded)
+                if (int rc = exchange_lists(m, l))
+                        return bail(rc);
+        for (int i = 0; i < n; ++i) {
+                FrameJob *j = job[i];
+                job[i] = nullptr;
+                if (int rc = frame_finish(j, (unsigned int)total, sharded))
+                        return bail(rc);
+        }
+        if (hits)
+                *hits = (int64_t)total;
+        return VRT_OK;
+}
+
+FrameArgs frame_args(const char *what, const vrt_camera *light_cam, const vrt_film *light_film,
+                     const float *light_color, const vrt_camera *cam, const vrt_film *film, float min_voxel)
+{
+        FrameArgs a{};
+        a.what = what;
+        a.may_probe = true;
+        a.light_cam = light_cam;
+        a.light_film = light_film;
+        a.light_color = light_color;
+        a.light_nranks = 1;
+        a.cam = cam;
+        a.film = film;
+        a.min_voxel = min_voxel;
+        a.nranks = 1;
+        return a;
+}
+
+int trace_frame_multi(vrt_multi *m, const char *what, const vrt_camera *light_cam, const vrt_film *light_film,
+                      const float *light_color, const vrt_camera *cam, const vrt_film *film, float min_voxel,
+                      float *rgb, float *d_image, void *stream, int64_t *hits)
+{
+        if (!m || !light_cam || !light_film || !cam || !film || !(rgb || d_image))
+                return set_error(VRT_E_INVALID, "null argument");
+        const FrameArgs a = frame_args(what, light_cam, light_film, light_color, cam, film, min_voxel);
+        if (int rc = frame_check(m->sc[0], a))  // as every rank would, before anything is enqueued
+                return rc;
+        return frame_out(m, film, rgb, d_image, stream,
+                         [&](const std::vector<float *> &dst) { return trace_work(m, a, dst, hits); });
+}
+
+int render_trace_multi(vrt_multi *m, const char *what, const vrt_camera *cam, const vrt_film *film, float min_voxel,
+                       float *rgb, float *d_image, void *stream)
+{
+        if (!m || !cam || !film || !(rgb || d_image))
+                return set_error(VRT_E_INVALID, "null argument");
+        if (int rc = frame_check(m->sc[0], frame_args(what, nullptr, nullptr, nullptr, cam, film, min_voxel)))
+                return rc;
+        for (size_t i = 0; i < m->sc.size(); ++i)
+                if (!scene_has_lightmap(m->sc[i]))
+                        return set_error(VRT_E_INVALID, "no light map on rank %d: call vrt_lightmap_build_multi first",
+                                         (int)i);
+        return frame_out(m, film, rgb, d_image, stream, [&](const std::vector<float *> &dst) -> int {
+                for (size_t i = 0; i < dst.size(); ++i)
+                        if (dst[i])
+                                if (int rc = vrt_render_trace_probes_device(m->sc[i], cam, film, min_voxel, (int)i,
+                                                                            (int)dst.size(), 0, dst[i], m->st[i]))
+                                        return fail_synced(m, rc);
+                return VRT_OK;
+        });
 }
 
 }  // namespace
@@ -201,6 +442,8 @@ extern "C" void vrt_multi_destroy(vrt_multi *m)
         for (size_t i = 0; i < m->st.size(); ++i) {
                 (void)hipSetDevice(m->devs[i]);
                 m->ev[i].reset();
+                if (i < m->ev_x.size())
+                        m->ev_x[i].reset();
                 m->st[i].reset();
         }
         for (vrt_scene *s : m->sc)
@@ -210,8 +453,10 @@ extern "C" void vrt_multi_destroy(vrt_multi *m)
         delete m;
 }
 
-extern "C" int vrt_scene_create_multi(const vrt_scene_desc *desc, int max_depth, uint32_t device_mask, int flags,
-                                      vrt_multi **out)
+// probes == nullptr: vrt_scene_create_multi (no probe flag); else a probe
+// scene with vrt_scene_create_probes' flags
+static int create_multi(const vrt_scene_desc *desc, const vrt_probe *probes, int32_t nprobe, int max_depth,
+                        uint32_t device_mask, int flags, vrt_multi **out)
 {
         if (!out)
                 return set_error(VRT_E_INVALID, "null out");
@@ -241,11 +486,16 @@ extern "C" int vrt_scene_create_multi(const vrt_scene_desc *desc, int max_depth,
         m->st.resize(n);
         m->ev.resize(n);
         m->send.resize(n);
-        // no probes in a multi-device scene: VRT_BUILD_DEVICE_PROBES is refused too
-        if (flags & ~VRT_BUILD_DEVICE)
+        m->ev_x.resize(n);
+        // without probes VRT_BUILD_DEVICE_PROBES is refused too
+        if (!probes && (flags & ~VRT_BUILD_DEVICE))
                 return set_error(VRT_E_INVALID, "vrt_scene_create_multi: unknown flags %#x", flags);
+        if (probes && flags != 0 && flags != (VRT_BUILD_DEVICE | VRT_BUILD_DEVICE_PROBES))
+                return set_error(VRT_E_INVALID, "vrt_scene_create_multi_probes: flags %#x (0, or VRT_BUILD_DEVICE | "
+                                                "VRT_BUILD_DEVICE_PROBES)", flags);
         // build once (host, or rank 0's device with VRT_BUILD_DEVICE) ...
-        if (int rc = vrt_scene_create_ex(desc, max_depth, devs[0], flags, &m->sc[0]))
+        if (int rc = probes ? vrt_scene_create_probes(desc, probes, nprobe, max_depth, devs[0], flags, &m->sc[0])
+                            : vrt_scene_create_ex(desc, max_depth, devs[0], flags, &m->sc[0]))
                 return rc;
         // ... and upload the same build to every other device, in parallel
         std::vector<int> rcs(n, VRT_OK);
@@ -268,6 +518,7 @@ extern "C" int vrt_scene_create_multi(const vrt_scene_desc *desc, int max_depth,
                 HIPCHK(hipSetDevice(devs[i]));
                 HIPCHK(m->st[i].create());
                 HIPCHK(m->ev[i].create(hipEventDisableTiming));
+                HIPCHK(m->ev_x[i].create(hipEventDisableTiming));
         }
         HIPCHK(hipSetDevice(devs[0]));
         HIPCHK(m->ev_in.create(hipEventDisableTiming));
@@ -278,6 +529,20 @@ extern "C" int vrt_scene_create_multi(const vrt_scene_desc *desc, int max_depth,
         }
         *out = m.release();
         return VRT_OK;
+}
+
+extern "C" int vrt_scene_create_multi(const vrt_scene_desc *desc, int max_depth, uint32_t device_mask, int flags,
+                                      vrt_multi **out)
+{
+        return create_multi(desc, nullptr, 0, max_depth, device_mask, flags, out);
+}
+
+extern "C" int vrt_scene_create_multi_probes(const vrt_scene_desc *desc, const vrt_probe *probes, int32_t nprobe,
+                                             int max_depth, uint32_t device_mask, int flags, vrt_multi **out)
+{
+        if (nprobe == 0 || !probes)
+                return create_multi(desc, nullptr, 0, max_depth, device_mask, flags, out);
+        return create_multi(desc, probes, nprobe, max_depth, device_mask, flags, out);
 }
 
 extern "C" int vrt_multi_devices(const vrt_multi *m, int *n, int32_t *devices)
@@ -304,37 +569,87 @@ extern "C" int vrt_render_multi_device(vrt_multi *m, const vrt_camera *cam, cons
 {
         if (!m || !cam || !film || !d_image)
                 return set_error(VRT_E_INVALID, "null argument");
-        if (film->nx < 1 || film->ny < 1 || film->nx > 32768 || film->ny > 32768)
+        if (film_bad(film))
                 return set_error(VRT_E_INVALID, "bad film");
-        std::lock_guard<std::mutex> lk(m->mu);
-        DeviceGuard g;
-        if (int rc = render_multi(m, cam, film, d_image, static_cast<hipStream_t>(stream)))
-                return rc;
-        if (!stream)  // no caller stream: the image is complete on return
-                return sync_all(m);
-        return VRT_OK;
+        return frame_out(m, film, nullptr, d_image, stream, primary_work(m, cam, film));
 }
 
 extern "C" int vrt_render_multi(vrt_multi *m, const vrt_camera *cam, const vrt_film *film, float *rgb)
 {
         if (!m || !cam || !film || !rgb)
                 return set_error(VRT_E_INVALID, "null argument");
-        if (film->nx < 1 || film->ny < 1 || film->nx > 32768 || film->ny > 32768)
+        if (film_bad(film))
+                return set_error(VRT_E_INVALID, "bad film");
+        return frame_out(m, film, rgb, nullptr, nullptr, primary_work(m, cam, film));
+}
+
+extern "C" int vrt_multi_set_light_mode(vrt_multi *m, int mode)
+{
+        if (!m)
+                return set_error(VRT_E_INVALID, "null argument");
+        if (mode != VRT_MULTI_LIGHT_REPLICATED && mode != VRT_MULTI_LIGHT_SHARDED)
+                return set_error(VRT_E_INVALID, "unknown light mode %d", mode);
+        std::lock_guard<std::mutex> lk(m->mu);
+        m->light_mode = mode;
+        return VRT_OK;
+}
+
+extern "C" int vrt_multi_set_probe_sgs(vrt_multi *m, const vrt_sg *sgs)
+{
+        if (!m || !sgs)
+                return set_error(VRT_E_INVALID, "null argument");
+        std::lock_guard<std::mutex> lk(m->mu);
+        DeviceGuard g;
+        for (vrt_scene *s : m->sc)
+                if (int rc = vrt_scene_set_probe_sgs(s, sgs))
+                        return rc;
+        return VRT_OK;
+}
+
+extern "C" int vrt_lightmap_build_multi(vrt_multi *m, const vrt_camera *light_cam, const vrt_film *light_film,
+                                        int64_t *hits)
+{
+        if (!m || !light_cam || !light_film)
+                return set_error(VRT_E_INVALID, "null argument");
+        if (film_bad(light_film))
                 return set_error(VRT_E_INVALID, "bad film");
         std::lock_guard<std::mutex> lk(m->mu);
         DeviceGuard g;
-        const size_t bytes = (size_t)film->nx * film->ny * 12;
-        HIPCHK(hipSetDevice(m->devs[0]));
-        HIPCHK(m->img.grow(bytes, m->st[0]));
-        // the unpack writes every pixel (zero outside the tile grid)
-        if (int rc = render_multi(m, cam, film, m->img.d.as<float>(), nullptr))
+        const FrameArgs a = frame_args("vrt_lightmap_build_multi", light_cam, light_film, nullptr, nullptr, nullptr, 0.f);
+        if (int rc = trace_work(m, a, std::vector<float *>(m->sc.size(), nullptr), hits))
                 return rc;
-        HIPCHK(hipSetDevice(m->devs[0]));
-        HIPCHK(hipMemcpyAsync(m->img.h, m->img.d, bytes, hipMemcpyDeviceToHost, m->st[0]));
-        if (int rc = sync_all(m))
-                return rc;
-        par_memcpy(rgb, m->img.h, bytes);
+        for (vrt_scene *s : m->sc)  // every rank's map is built on return
+                if (int rc = scene_stream_sync(s))
+                        return rc;
         return VRT_OK;
+}
+
+extern "C" int vrt_render_trace_multi(vrt_multi *m, const vrt_camera *cam, const vrt_film *film, float min_voxel,
+                                      float *rgb)
+{
+        return render_trace_multi(m, "vrt_render_trace_multi", cam, film, min_voxel, rgb, nullptr, nullptr);
+}
+
+extern "C" int vrt_render_trace_multi_device(vrt_multi *m, const vrt_camera *cam, const vrt_film *film,
+                                             float min_voxel, float *d_image, void *stream)
+{
+        return render_trace_multi(m, "vrt_render_trace_multi_device", cam, film, min_voxel, nullptr, d_image, stream);
+}
+
+extern "C" int vrt_trace_frame_multi(vrt_multi *m, const vrt_camera *light_cam, const vrt_film *light_film,
+                                     const float *light_color, const vrt_camera *cam, const vrt_film *film,
+                                     float min_voxel, float *rgb, int64_t *hits)
+{
+        return trace_frame_multi(m, "vrt_trace_frame_multi", light_cam, light_film, light_color, cam, film, min_voxel, rgb,
+                                 nullptr, nullptr, hits);
+}
+
+extern "C" int vrt_trace_frame_multi_device(vrt_multi *m, const vrt_camera *light_cam, const vrt_film *light_film,
+                                            const float *light_color, const vrt_camera *cam, const vrt_film *film,
+                                            float min_voxel, float *d_image, void *stream, int64_t *hits)
+{
+        return trace_frame_multi(m, "vrt_trace_frame_multi_device", light_cam, light_film, light_color, cam, film,
+                                 min_voxel, nullptr, d_image, stream, hits);
 }
 
 extern "C" int vrt_multi_tile_map(const vrt_film *film, uint32_t device_mask, int32_t *device_of_tile,
