@@ -249,6 +249,19 @@ int vrt_render_secondary_device(vrt_scene *s, const vrt_camera *cam,
                                 const vrt_film *film, int spp, int rank,
                                 int nranks, float *d_prim, float *d_vis,
                                 void *stream);
+/* One rank's config-5 share, packed for the gather: the share-sized primary
+ * pass over this rank's tiles of the deal, the secondary walk of
+ * vrt_render_secondary_device, then this rank's tiles of d_vis packed
+ * tile-major into d_packed (vrt_pack_tiles_c_device with comps = 1:
+ * tiles_per_rank * 64 floats).  d_prim: scratch, 8*(nx/8)*8*(ny/8)*8 floats;
+ * records of tiles not dealt to this rank are neither written nor read.
+ * d_vis: scratch, nx*ny floats, need not be zeroed; only this rank's pixels
+ * are written.  d_prim_hits (may be NULL): set to the number of this rank's
+ * pixels whose primary ray hit.  nranks == 1 is allowed (raster deal).
+ * Enqueued on `stream`, no host synchronisation. */
+int vrt_render_secondary_tiles_device(vrt_scene *s, const vrt_camera *cam, const vrt_film *film, int spp,
+                                      int rank, int nranks, float *d_prim, float *d_vis, float *d_packed,
+                                      uint64_t *d_prim_hits, void *stream);
 
 /* Batched gi::ray_march (VRT/voxel_octree.cc:131-188) on host arrays. */
 int vrt_ray_march_batch(vrt_scene *s, const vrt_ray *rays, int64_t n,
@@ -763,6 +776,22 @@ int vrt_trace_frame_multi(vrt_multi *m, const vrt_camera *light_cam, const vrt_f
 int vrt_trace_frame_multi_device(vrt_multi *m, const vrt_camera *light_cam, const vrt_film *light_film,
                                  const float *light_color, const vrt_camera *cam, const vrt_film *film,
                                  float min_voxel, float *d_image, void *stream, int64_t *hits);
+
+/* Config 5 over the handle's ranks: rank i renders its share
+ * (vrt_render_secondary_tiles_device) on its stream into scratch the handle
+ * owns, one gather of tiles_per_rank * 64 floats per rank to rank 0,
+ * vrt_unpack_tiles_c_device (comps = 1) there.  vis (nx*ny floats, index
+ * y*nx+x, zero outside the tile grid) is vrt_render_secondary's, bit for bit,
+ * for any rank count; *rays (may be NULL) = 8*(nx/8)*8*(ny/8) + spp * (sum of
+ * the ranks' primary hits) = vrt_render_secondary's *rays.  spp outside 1..64,
+ * a bad film or a NULL argument: VRT_E_INVALID before anything is enqueued;
+ * after a failure on any rank nothing collective is enqueued and every rank's
+ * streams are synchronised.  A probe handle skips the probes. */
+int vrt_render_secondary_multi(vrt_multi *m, const vrt_camera *cam, const vrt_film *film, int spp,
+                               float *vis, int64_t *rays);
+/* d_vis on rank 0's device, stream ordering as vrt_render_multi_device. */
+int vrt_render_secondary_multi_device(vrt_multi *m, const vrt_camera *cam, const vrt_film *film, int spp,
+                                      float *d_vis, void *stream);
 
 /* ---- output (VRT/stb_image_write.h:178,723-757) ------------------------- */
 /* Byte-identical to stbi_write_hdr: returns 1 on success, 0 on failure. */

@@ -142,6 +142,8 @@ SIGNATURES = {
                                        i32p, u32p, i64p]),
     "vrt_render_secondary_device": (C.c_int, [_P, C.POINTER(Camera), C.POINTER(Film), C.c_int, C.c_int,
                                               C.c_int, _P, _P, _P]),
+    "vrt_render_secondary_tiles_device": (C.c_int, [_P, C.POINTER(Camera), C.POINTER(Film), C.c_int, C.c_int,
+                                                    C.c_int, _P, _P, _P, _P, _P]),
     "vrt_ray_march_batch": (C.c_int, [_P, C.POINTER(Ray), C.c_int64, C.POINTER(Hit)]),
     "vrt_ray_march_batch_device": (C.c_int, [_P, _P, C.c_int64, _P, _P]),
     "vrt_trace_batch": (C.c_int, [_P, C.POINTER(Ray), C.c_int64, C.c_float, f32p, C.POINTER(TraceParts)]),
@@ -240,6 +242,8 @@ SIGNATURES = {
                                         C.POINTER(Film), C.c_float, f32p, i64p]),
     "vrt_trace_frame_multi_device": (C.c_int, [_P, C.POINTER(Camera), C.POINTER(Film), f32p, C.POINTER(Camera),
                                                C.POINTER(Film), C.c_float, _P, _P, i64p]),
+    "vrt_render_secondary_multi": (C.c_int, [_P, C.POINTER(Camera), C.POINTER(Film), C.c_int, f32p, i64p]),
+    "vrt_render_secondary_multi_device": (C.c_int, [_P, C.POINTER(Camera), C.POINTER(Film), C.c_int, _P, _P]),
     "vrt_status_string": (C.c_char_p, [C.c_int]),
     "vrt_last_error": (C.c_char_p, []),
 }

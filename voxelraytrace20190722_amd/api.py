@@ -512,6 +512,20 @@ class VoxelOctree:
                                                 C.c_void_p(stream_ptr) if stream_ptr else None),
               "vrt_render_secondary_device")
 
+    def render_secondary_tiles_device(self, cam, film, spp, rank, nranks, d_prim_ptr, d_vis_ptr, d_packed_ptr,
+                                      d_prim_hits_ptr=None, stream_ptr=None):
+        """One rank's config-5 share, packed for the gather
+        (vrt_render_secondary_tiles_device): the primary pass marches only the
+        rank's own tiles; d_packed receives its tiles of the visibility image
+        in deal order (64 floats each), d_prim_hits (a device uint64, or
+        None) the number of its pixels whose primary ray hit."""
+        check(lib().vrt_render_secondary_tiles_device(self.h, C.byref(cam.c), C.byref(film.c), int(spp), int(rank),
+                                                      int(nranks), C.c_void_p(d_prim_ptr), C.c_void_p(d_vis_ptr),
+                                                      C.c_void_p(d_packed_ptr),
+                                                      C.c_void_p(d_prim_hits_ptr) if d_prim_hits_ptr else None,
+                                                      C.c_void_p(stream_ptr) if stream_ptr else None),
+              "vrt_render_secondary_tiles_device")
+
     def render_tiles_device(self, cam, film, rank, nranks, image_layout, d_out_ptr, stream_ptr=None):
         check(lib().vrt_render_tiles_device(self.h, C.byref(cam.c), C.byref(film.c), int(rank),
                                             int(nranks), int(image_layout), C.c_void_p(d_out_ptr),
@@ -828,6 +842,23 @@ class MultiOctree:
                                             C.c_void_p(stream_ptr) if stream_ptr else None),
               "vrt_render_multi_device")
 
+    def render_secondary(self, cam, film, spp=64):
+        """Config 5 over the handle's ranks (vrt_render_secondary_multi) ->
+        ((ny, nx) float32 visibility image, rays traced): VoxelOctree's
+        render_secondary, bit for bit, for any rank count."""
+        vis = np.zeros((film.ny, film.nx), np.float32)
+        rays = C.c_int64()
+        check(lib().vrt_render_secondary_multi(self.h, C.byref(cam.c), C.byref(film.c), int(spp),
+                                               ptr(vis, _ffi.f32p), C.byref(rays)), "vrt_render_secondary_multi")
+        return vis, rays.value
+
+    def render_secondary_device(self, cam, film, spp, d_vis_ptr, stream_ptr=None):
+        """render_secondary into a device image (nx*ny floats) on the first
+        device, ordered on stream_ptr as render_device is."""
+        check(lib().vrt_render_secondary_multi_device(self.h, C.byref(cam.c), C.byref(film.c), int(spp),
+                                                      C.c_void_p(d_vis_ptr),
+                                                      C.c_void_p(stream_ptr) if stream_ptr else None),
+              "vrt_render_secondary_multi_device")
 
     # ---- trace() frames (light pass + filter + cone-traced view) ----
     LIGHT_MODES = {"replicated": _ffi.VRT_MULTI_LIGHT_REPLICATED, "sharded": _ffi.VRT_MULTI_LIGHT_SHARDED}

@@ -1712,9 +1712,11 @@ static int spill_done(vrt_scene *s, int k, const SpillQueues &sq, hipStream_t st
 }
 
 // One config-5 launch (k_primary1 + secondary rays) on stream st (caller
-// holds s->mu).
+// holds s->mu).  share: the share-sized primary pass (PrimShare) instead of
+// the whole-film one.
 static int secondary_launch(vrt_scene *s, const RenderParams &p, int spp, int rank, int nranks, float *d_prim,
-                            float *d_vis, int32_t *s_hit, int32_t *s_tri, uint32_t *s_vox, hipStream_t st)
+                            float *d_vis, int32_t *s_hit, int32_t *s_tri, uint32_t *s_vox, hipStream_t st,
+                            const PrimShare *share = nullptr)
 {
         int slot = -1;
         WorkQueue q;
@@ -1739,7 +1741,7 @@ static int secondary_launch(vrt_scene *s, const RenderParams &p, int spp, int ra
                 side = { s->spill_side[set].st, s->spill_side[set].fork, s->spill_side[set].join };
         const hipError_t e = launch_secondary(p, spp, rank, nranks, scene_res(s), d_prim, d_vis, s_hit, s_tri,
                                               s_vox, slot >= 0 ? &q : nullptr, st, &waves, units, &sq,
-                                              side.st ? &side : nullptr);
+                                              side.st ? &side : nullptr, share);
         if (set >= 0)
                 if (int rc = spill_done(s, set, sq, st))
                         return rc;
@@ -2173,6 +2175,26 @@ static float scene_res(const vrt_scene *s)
         return res;
 }
 
+// One rank's config-5 share on st (arguments checked; takes s->mu).  share:
+// nullptr = the primary pass covers every pixel, else it covers the rank's
+// tiles (PrimShare).
+static int secondary_share(vrt_scene *s, const vrt_camera *cam, const vrt_film *film, int spp, int rank, int nranks,
+                           float *d_prim, float *d_vis, const PrimShare *share, hipStream_t st)
+{
+        std::lock_guard<std::mutex> lk(s->mu);
+        HIPCHK(hipSetDevice(s->device));
+        RenderParams p;
+        fill_render_params(s, cam, film, 0, 1, &p);
+        // the secondary rays' share
+        p.tile_xy = deal_map(s, p.ntx, p.nty, nranks, rank, st);
+        HIPCHK(hipEventRecord(s->ev0, st));
+        if (int rc = secondary_launch(s, p, spp, rank, nranks, d_prim, d_vis, nullptr, nullptr, nullptr, st, share))
+                return rc;
+        HIPCHK(hipEventRecord(s->ev1, st));
+        s->timed = true;
+        return VRT_OK;
+}
+
 extern "C" int vrt_render_secondary_device(vrt_scene *s, const vrt_camera *cam,
                                            const vrt_film *film, int spp,
                                            int rank, int nranks, float *d_prim,
@@ -2186,18 +2208,34 @@ extern "C" int vrt_render_secondary_device(vrt_scene *s, const vrt_camera *cam,
                 return rc;
         if (nranks < 1 || rank < 0 || rank >= nranks)
                 return fail(VRT_E_INVALID, "rank %d of %d", rank, nranks);
-        std::lock_guard<std::mutex> lk(s->mu);
-        HIPCHK(hipSetDevice(s->device));
-        RenderParams p;
-        fill_render_params(s, cam, film, 0, 1, &p);
-        hipStream_t st = static_cast<hipStream_t>(stream);
-        // the secondary rays' share (the primary pass covers every pixel)
-        p.tile_xy = deal_map(s, p.ntx, p.nty, nranks, rank, st);
-        HIPCHK(hipEventRecord(s->ev0, st));
-        if (int rc = secondary_launch(s, p, spp, rank, nranks, d_prim, d_vis, nullptr, nullptr, nullptr, st))
+        // (the primary pass covers every pixel)
+        return secondary_share(s, cam, film, spp, rank, nranks, d_prim, d_vis, nullptr, static_cast<hipStream_t>(stream));
+}
+
+extern "C" int vrt_render_secondary_tiles_device(vrt_scene *s, const vrt_camera *cam, const vrt_film *film, int spp,
+                                                 int rank, int nranks, float *d_prim, float *d_vis, float *d_packed,
+                                                 uint64_t *d_prim_hits, void *stream)
+{
+        if (s && need_device(s))
+                return VRT_E_NODEVICE;
+        if (!s || !cam || !d_prim || !d_vis || !d_packed || spp < 1 || spp > 64)
+                return fail(VRT_E_INVALID, "bad argument (spp must be 1..64)");
+        if (int rc = film_ok(film))
                 return rc;
-        HIPCHK(hipEventRecord(s->ev1, st));
-        s->timed = true;
+        if (nranks < 1 || rank < 0 || rank >= nranks)
+                return fail(VRT_E_INVALID, "rank %d of %d", rank, nranks);
+        hipStream_t st = static_cast<hipStream_t>(stream);
+        if (d_prim_hits) {
+                std::lock_guard<std::mutex> lk(s->mu);
+                HIPCHK(hipSetDevice(s->device));
+                HIPCHK(hipMemsetAsync(d_prim_hits, 0, sizeof(uint64_t), st));
+        }
+        if (deal_count(tile_deal(film->nx / 8, film->ny / 8, nranks), rank) == 0)  // no tile: nothing to render or pack
+                return VRT_OK;
+        const PrimShare share{ reinterpret_cast<unsigned long long *>(d_prim_hits) };
+        if (int rc = secondary_share(s, cam, film, spp, rank, nranks, d_prim, d_vis, &share, st))
+                return rc;
+        HIPCHK(launch_pack_c(film->nx, film->ny, rank, nranks, 1, d_vis, d_packed, st));
         return VRT_OK;
 }
 

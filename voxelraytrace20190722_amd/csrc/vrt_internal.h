@@ -798,13 +798,22 @@ struct SideLaunch {
         hipStream_t st;
         hipEvent_t fork, join;
 };
+// The share-sized primary pass of a config-5 launch (k_primary1_share: only
+// the records of the rank's own tiles are written) instead of the whole-film
+// one.  hits: nullptr, or a zeroed device counter that receives the number of
+// the rank's pixels whose primary ray hit.
+struct PrimShare {
+        unsigned long long *hits;
+};
 // q: the launch's work queue (persistent kernel) or nullptr (one wave per
-// pixel); side: nullptr = every kernel on st
+// pixel); side: nullptr = every kernel on st; share: nullptr = the whole-film
+// primary pass
 hipError_t launch_secondary(const RenderParams &rp, int spp, int rank,
                             int nranks, float res, float *prim, float *vis,
                             int32_t *s_hit, int32_t *s_tri, uint32_t *s_vox,
                             const WorkQueue *q, hipStream_t st, int *q_waves, int slice_units[8],
-                            const SpillQueues *sq = nullptr, const SideLaunch *side = nullptr);
+                            const SpillQueues *sq = nullptr, const SideLaunch *side = nullptr,
+                            const PrimShare *share = nullptr);
 // the compaction settings of this build (VRT_SEC_SPILL*), cap left 0
 SpillQueues spill_defaults();
 // a path-selecting compile-time switch of the kernel build by name (false:

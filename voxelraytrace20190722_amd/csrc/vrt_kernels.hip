@@ -2772,6 +2772,63 @@ __global__ __launch_bounds__(kBlock) void k_primary1(RenderParams p, float *__re
         o[6] = nrm.z;
 }
 
+// Pass 1 over one rank's share of the deal: wave t takes the rank's t-th tile
+// in deal order (rank_tile: the tabled deal p.tile_xy by a scalar load, or
+// deal_tile when there is no table; lane = 8 * row + column) and writes
+// k_primary1's record of each of its pixels at k_primary1's address -- the same
+// ray, march and normal, so the same bits.  Records of tiles dealt to other
+// ranks are neither written nor read; waves past the rank's ntiles tiles
+// return before touching memory.  hits (may be nullptr): += the wave's lanes
+// whose ray hit, one atomic add per wave.
+template <bool kR64>
+__global__ __launch_bounds__(kBlock) void k_primary1_share(RenderParams p, int rank, int nranks, int ntiles,
+                                                           unsigned long long *__restrict__ hits,
+                                                           float *__restrict__ prim)
+{
+        __shared__ uint2 stk[kStack * kBlock];
+        const int tid = threadIdx.x;
+        const int W8 = 8 * p.ntx;
+        // the tile is wave-uniform: its index and coordinates stay in SGPRs
+        const int t = __builtin_amdgcn_readfirstlane((int)blockIdx.x * (kBlock / 64) + (tid >> 6));
+        if (t >= ntiles)
+                return;
+        int tx, ty;
+        rank_tile(p.ntx, p.nty, nranks, rank, p.ntx_magic, p.tile_xy, t, tx, ty);
+        tx = __builtin_amdgcn_readfirstlane(tx);
+        ty = __builtin_amdgcn_readfirstlane(ty);
+        const int px = tx * 8 + (tid & 7), py = ty * 8 + ((tid >> 3) & 7);
+        const int64_t i = (int64_t)py * W8 + px;
+        const CamParams &c = p.cam;
+        const f3 dn = camera_dir(c.s, c.u, c.nf, c.e, c.z, c.nx, c.ny, px, py, 0.5f, 0.5f);
+        const RayK r = make_rayk(mk3(c.origin[0], c.origin[1], c.origin[2]), dn, c.tmin, c.tmax);
+        MarchResult m;
+        ray_march_dispatch<false, kBlock, true, kR64>(p.sc, r, stk + tid, nullptr, nullptr, m);
+        if (hits) {  // uniform: a kernel argument
+                const unsigned long long b = __ballot(m.hit);
+                if ((tid & 63) == 0 && b)
+                        atomicAdd(hits, (unsigned long long)__popcll(b));
+        }
+        float *o = prim + 8 * i;
+        if (!m.hit) {
+                o[0] = 0.f;
+                return;
+        }
+        const TriAttr *ta = p.sc.tri_attr + m.tri;
+        const f3 n0 = mk3(ta->n[0], ta->n[1], ta->n[2]);
+        const f3 n1 = mk3(ta->n[3], ta->n[4], ta->n[5]);
+        const f3 n2 = mk3(ta->n[6], ta->n[7], ta->n[8]);
+        // tri_normal, written out as in k_primary1
+        const float w = clampf(1.0f - m.u - m.v, 0, 1);
+        const f3 nrm = normalize((n0 * w + n1 * m.u) + n2 * m.v);
+        o[0] = 1.f;
+        o[1] = m.hp.x;
+        o[2] = m.hp.y;
+        o[3] = m.hp.z;
+        o[4] = nrm.x;
+        o[5] = nrm.y;
+        o[6] = nrm.z;
+}
+
 // Pass 2: one wave per pixel, lane s = secondary ray s.  The reference
 // draws points sequentially (rejection sampling, 3 draws per attempt); here
 // lane l evaluates attempt l (+64 per round) from a jump-ahead PCG state and
@@ -3473,7 +3530,7 @@ SpillQueues spill_defaults()
 hipError_t launch_secondary(const RenderParams &rp, int spp, int rank, int nranks, float res,
                             float *prim, float *vis, int32_t *s_hit, int32_t *s_tri,
                             uint32_t *s_vox, const WorkQueue *q, hipStream_t st, int *q_waves, int slice_units[8],
-                            const SpillQueues *sq, const SideLaunch *side)
+                            const SpillQueues *sq, const SideLaunch *side, const PrimShare *share)
 {
         *q_waves = 0;
         for (int x = 0; x < 8; ++x)
@@ -3481,8 +3538,17 @@ hipError_t launch_secondary(const RenderParams &rp, int spp, int rank, int nrank
         const int64_t npix = (int64_t)rp.ntx * 8 * rp.nty * 8;
         if (npix <= 0)
                 return hipSuccess;
-        hipLaunchKernelGGL(rp.sc.wide_leaves ? k_primary1<true> : k_primary1<false>, dim3((unsigned)((npix + kBlock - 1) / kBlock)), dim3(kBlock), 0, st,
-                           rp, prim);
+        if (share) {
+                // the share-sized pass: a wave per tile of this rank (none: no launch)
+                const int nt = deal_count(tile_deal(rp.ntx, rp.nty, nranks), rank);
+                if (nt > 0)
+                        hipLaunchKernelGGL(rp.sc.wide_leaves ? k_primary1_share<true> : k_primary1_share<false>,
+                                           dim3((unsigned)((nt + kBlock / 64 - 1) / (kBlock / 64))), dim3(kBlock), 0, st, rp,
+                                           rank, nranks, nt, share->hits, prim);
+        } else {
+                hipLaunchKernelGGL(rp.sc.wide_leaves ? k_primary1<true> : k_primary1<false>, dim3((unsigned)((npix + kBlock - 1) / kBlock)), dim3(kBlock), 0, st,
+                                   rp, prim);
+        }
         if (hipError_t e = hipGetLastError())
                 return e;
         SecondaryParams sp;

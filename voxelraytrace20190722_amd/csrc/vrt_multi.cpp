@@ -15,6 +15,7 @@
 
 #include <rccl/rccl.h>
 
+#include <algorithm>
 #include <cstring>
 #include <functional>
 #include <memory>
@@ -35,6 +36,10 @@ struct vrt_multi {
         std::vector<DevMem> send;       // ranks >= 1: packed tile buffer (tpr * 192 floats)
         DevMem gath;                    // rank 0: n * tpr * 192 floats (its own share in place)
         size_t tpr_cap = 0;             // tiles per rank the buffers hold
+        // config 5 (vrt_render_secondary_multi*): rank i's primary records, visibility
+        // image and primary-hit counter (8 B) on its device, used on st[i]
+        std::vector<DevMem> prim, vis, hits;
+        size_t prim_cap = 0, vis_cap = 0;  // bytes every rank's prim / vis holds
         Staging img;                    // vrt_render_multi: image on rank 0's device, its pinned copy; on st[0]
         Event ev_in;                    // caller's stream -> rank 0's stream
         int light_mode = VRT_MULTI_LIGHT_REPLICATED;  // vrt_multi_set_light_mode
@@ -92,6 +97,19 @@ void free_buffers(vrt_multi *m)
         m->tpr_cap = 0;
 }
 
+// config 5's per-rank scratch, each with its device current
+void free_secondary(vrt_multi *m)
+{
+        for (size_t i = 0; i < m->prim.size(); ++i)
+                if (m->prim[i] || m->vis[i] || m->hits[i]) {
+                        (void)hipSetDevice(m->devs[i]);
+                        m->prim[i].reset();
+                        m->vis[i].reset();
+                        m->hits[i].reset();
+                }
+        m->prim_cap = m->vis_cap = 0;
+}
+
 int sync_all(vrt_multi *m)
 {
         for (size_t i = 0; i < m->st.size(); ++i)
@@ -142,28 +160,31 @@ int gather(vrt_multi *m, size_t count)
 }
 
 // What every rank enqueues for one frame: dst[i] is rank i's packed tile
-// buffer (tpr * 192 floats, written on m->st[i]), or null when the film has no
-// tile.  It enqueues nothing collective, and after a failure it has
+// buffer (tpr * 64 * comps floats, written on m->st[i]), or null when the film
+// has no tile.  It enqueues nothing collective, and after a failure it has
 // synchronised whatever it started.
 using RankWork = std::function<int(const std::vector<float *> &dst)>;
 
-// One frame into d_image on rank 0's device (caller holds m->mu): the ranks'
-// work, the gather, the unpack.
-int frame_multi(vrt_multi *m, const vrt_film *film, float *d_image, hipStream_t caller, const RankWork &work)
+// One frame of `comps` floats per pixel (3: RGB, 1: config 5's visibility)
+// into d_image on rank 0's device (caller holds m->mu): the ranks' work, the
+// gather, the unpack.
+int frame_multi(vrt_multi *m, const vrt_film *film, int comps, float *d_image, hipStream_t caller,
+                const RankWork &work)
 {
         const int n = (int)m->devs.size();
         const int tpr = vrt_tiles_per_rank(film, n);
-        const size_t count = (size_t)tpr * 192;  // floats per rank buffer (8x8 pixels x RGB per tile)
+        const size_t count = (size_t)tpr * 64 * comps;  // floats per rank buffer (8x8 pixels x comps per tile)
         if (tpr > 0 && (size_t)tpr > m->tpr_cap) {
                 if (int rc = sync_all(m))
                         return rc;
                 free_buffers(m);
+                const size_t cap = (size_t)tpr * 192;  // room for either kind of frame
                 for (int i = 1; i < n; ++i) {
                         HIPCHK(hipSetDevice(m->devs[i]));
-                        HIPCHK(m->send[i].alloc(count * sizeof(float)));
+                        HIPCHK(m->send[i].alloc(cap * sizeof(float)));
                 }
                 HIPCHK(hipSetDevice(m->devs[0]));
-                HIPCHK(m->gath.alloc((size_t)n * count * sizeof(float)));
+                HIPCHK(m->gath.alloc((size_t)n * cap * sizeof(float)));
                 m->tpr_cap = (size_t)tpr;
         }
         HIPCHK(hipSetDevice(m->devs[0]));
@@ -183,10 +204,12 @@ int frame_multi(vrt_multi *m, const vrt_film *film, float *d_image, hipStream_t 
                         return rc;
         HIPCHK(hipSetDevice(m->devs[0]));
         if (tpr > 0) {
-                if (int rc = vrt_unpack_tiles_device(film, n, m->gath.as<float>(), d_image, m->st[0]))
+                if (int rc = comps == 3 ? vrt_unpack_tiles_device(film, n, m->gath.as<float>(), d_image, m->st[0])
+                                        : vrt_unpack_tiles_c_device(film, n, comps, m->gath.as<float>(), d_image,
+                                                                    m->st[0]))
                         return rc;
         } else {
-                HIPCHK(hipMemsetAsync(d_image, 0, (size_t)film->nx * film->ny * 12, m->st[0]));
+                HIPCHK(hipMemsetAsync(d_image, 0, (size_t)film->nx * film->ny * comps * sizeof(float), m->st[0]));
         }
         if (caller) {
                 HIPCHK(hipEventRecord(m->ev[0], m->st[0]));
@@ -195,31 +218,33 @@ int frame_multi(vrt_multi *m, const vrt_film *film, float *d_image, hipStream_t 
         return VRT_OK;
 }
 
-// A frame call's two outputs: the host array rgb (through m->img), or d_image
-// ordered on `stream` (null: complete on return).
-int frame_out(vrt_multi *m, const vrt_film *film, float *rgb, float *d_image, void *stream, const RankWork &work)
+// A frame call's two outputs (comps floats per pixel): the host array rgb
+// (through m->img), or d_image ordered on `stream` (null: complete on return).
+// done (host output only): called under m->mu once every rank's stream is idle.
+int frame_out(vrt_multi *m, const vrt_film *film, int comps, float *rgb, float *d_image, void *stream,
+              const RankWork &work, const std::function<int()> &done = nullptr)
 {
         std::lock_guard<std::mutex> lk(m->mu);
         DeviceGuard g;
         if (!rgb) {
-                if (int rc = frame_multi(m, film, d_image, static_cast<hipStream_t>(stream), work))
+                if (int rc = frame_multi(m, film, comps, d_image, static_cast<hipStream_t>(stream), work))
                         return rc;
                 if (!stream)  // no caller stream: the image is complete on return
                         return sync_all(m);
                 return VRT_OK;
         }
-        const size_t bytes = (size_t)film->nx * film->ny * 12;
+        const size_t bytes = (size_t)film->nx * film->ny * comps * sizeof(float);
         HIPCHK(hipSetDevice(m->devs[0]));
         HIPCHK(m->img.grow(bytes, m->st[0]));
         // the unpack writes every pixel (zero outside the tile grid)
-        if (int rc = frame_multi(m, film, m->img.d.as<float>(), nullptr, work))
+        if (int rc = frame_multi(m, film, comps, m->img.d.as<float>(), nullptr, work))
                 return rc;
         HIPCHK(hipSetDevice(m->devs[0]));
         HIPCHK(hipMemcpyAsync(m->img.h, m->img.d, bytes, hipMemcpyDeviceToHost, m->st[0]));
         if (int rc = sync_all(m))
                 return rc;
         par_memcpy(rgb, m->img.h, bytes);
-        return VRT_OK;
+        return done ? done() : VRT_OK;
 }
 
 bool film_bad(const vrt_film *film)
@@ -249,6 +274,59 @@ int fail_synced(vrt_multi *m, int rc)
         for (vrt_scene *s : m->sc)
                 (void)scene_stream_sync(s);
         return set_error(rc, "%s", err.c_str());
+}
+
+// Config 5's scratch for this film on every rank (caller holds m->mu): the
+// primary records, the visibility image and the hit counter.  Grown on
+// demand, once every rank's stream is idle, as the tile buffers are.
+int secondary_scratch(vrt_multi *m, const vrt_film *film)
+{
+        const size_t narea = (size_t)(8 * (film->nx / 8)) * (8 * (film->ny / 8));
+        const size_t pb = narea * 8 * sizeof(float), vb = (size_t)film->nx * film->ny * sizeof(float);
+        if (pb <= m->prim_cap && vb <= m->vis_cap && m->hits[0])
+                return VRT_OK;
+        if (int rc = sync_all(m))
+                return rc;
+        const size_t pcap = std::max(pb, m->prim_cap), vcap = std::max(vb, m->vis_cap);
+        free_secondary(m);
+        for (size_t i = 0; i < m->devs.size(); ++i) {
+                HIPCHK(hipSetDevice(m->devs[i]));
+                HIPCHK(m->prim[i].alloc(pcap));
+                HIPCHK(m->vis[i].alloc(vcap));
+                HIPCHK(m->hits[i].alloc(sizeof(uint64_t)));
+        }
+        m->prim_cap = pcap;
+        m->vis_cap = vcap;
+        return VRT_OK;
+}
+
+// the config-5 frame: vrt_render_secondary_tiles_device with rank i of n,
+// into the handle's scratch and the rank's packed buffer
+RankWork secondary_work(vrt_multi *m, const vrt_camera *cam, const vrt_film *film, int spp)
+{
+        return [=](const std::vector<float *> &dst) -> int {
+                if (!dst[0])  // no tile: nothing to render
+                        return VRT_OK;
+                if (int rc = secondary_scratch(m, film))
+                        return rc;
+                for (size_t i = 0; i < dst.size(); ++i)
+                        if (int rc = vrt_render_secondary_tiles_device(m->sc[i], cam, film, spp, (int)i, (int)dst.size(),
+                                                                       m->prim[i].as<float>(), m->vis[i].as<float>(),
+                                                                       dst[i], m->hits[i].as<uint64_t>(), m->st[i]))
+                                return fail_synced(m, rc);
+                return VRT_OK;
+        };
+}
+
+int secondary_check(vrt_multi *m, const vrt_camera *cam, const vrt_film *film, int spp, const void *out)
+{
+        if (!m || !cam || !film || !out)
+                return set_error(VRT_E_INVALID, "null argument");
+        if (spp < 1 || spp > 64)
+                return set_error(VRT_E_INVALID, "bad argument (spp must be 1..64)");
+        if (film_bad(film))
+                return set_error(VRT_E_INVALID, "bad film");
+        return VRT_OK;
 }
 
 // Sharded light pass: every rank receives every other rank's keys and records
@@ -401,7 +479,7 @@ int trace_frame_multi(vrt_multi *m, const char *what, const vrt_camera *light_ca
         const FrameArgs a = frame_args(what, light_cam, light_film, light_color, cam, film, min_voxel);
         if (int rc = frame_check(m->sc[0], a))  // as every rank would, before anything is enqueued
                 return rc;
-        return frame_out(m, film, rgb, d_image, stream,
+        return frame_out(m, film, 3, rgb, d_image, stream,
                          [&](const std::vector<float *> &dst) { return trace_work(m, a, dst, hits); });
 }
 
@@ -416,7 +494,7 @@ int render_trace_multi(vrt_multi *m, const char *what, const vrt_camera *cam, co
                 if (!scene_has_lightmap(m->sc[i]))
                         return set_error(VRT_E_INVALID, "no light map on rank %d: call vrt_lightmap_build_multi first",
                                          (int)i);
-        return frame_out(m, film, rgb, d_image, stream, [&](const std::vector<float *> &dst) -> int {
+        return frame_out(m, film, 3, rgb, d_image, stream, [&](const std::vector<float *> &dst) -> int {
                 for (size_t i = 0; i < dst.size(); ++i)
                         if (dst[i])
                                 if (int rc = vrt_render_trace_probes_device(m->sc[i], cam, film, min_voxel, (int)i,
@@ -439,6 +517,7 @@ extern "C" void vrt_multi_destroy(vrt_multi *m)
                         (void)ncclCommDestroy(c);
         // each rank's resources go with its device current
         free_buffers(m);
+        free_secondary(m);
         for (size_t i = 0; i < m->st.size(); ++i) {
                 (void)hipSetDevice(m->devs[i]);
                 m->ev[i].reset();
@@ -487,6 +566,9 @@ static int create_multi(const vrt_scene_desc *desc, const vrt_probe *probes, int
         m->ev.resize(n);
         m->send.resize(n);
         m->ev_x.resize(n);
+        m->prim.resize(n);
+        m->vis.resize(n);
+        m->hits.resize(n);
         // without probes VRT_BUILD_DEVICE_PROBES is refused too
         if (!probes && (flags & ~VRT_BUILD_DEVICE))
                 return set_error(VRT_E_INVALID, "vrt_scene_create_multi: unknown flags %#x", flags);
@@ -571,7 +653,7 @@ extern "C" int vrt_render_multi_device(vrt_multi *m, const vrt_camera *cam, cons
                 return set_error(VRT_E_INVALID, "null argument");
         if (film_bad(film))
                 return set_error(VRT_E_INVALID, "bad film");
-        return frame_out(m, film, nullptr, d_image, stream, primary_work(m, cam, film));
+        return frame_out(m, film, 3, nullptr, d_image, stream, primary_work(m, cam, film));
 }
 
 extern "C" int vrt_render_multi(vrt_multi *m, const vrt_camera *cam, const vrt_film *film, float *rgb)
@@ -580,7 +662,38 @@ extern "C" int vrt_render_multi(vrt_multi *m, const vrt_camera *cam, const vrt_f
                 return set_error(VRT_E_INVALID, "null argument");
         if (film_bad(film))
                 return set_error(VRT_E_INVALID, "bad film");
-        return frame_out(m, film, rgb, nullptr, nullptr, primary_work(m, cam, film));
+        return frame_out(m, film, 3, rgb, nullptr, nullptr, primary_work(m, cam, film));
+}
+
+extern "C" int vrt_render_secondary_multi_device(vrt_multi *m, const vrt_camera *cam, const vrt_film *film, int spp,
+                                                 float *d_vis, void *stream)
+{
+        if (int rc = secondary_check(m, cam, film, spp, d_vis))
+                return rc;
+        return frame_out(m, film, 1, nullptr, d_vis, stream, secondary_work(m, cam, film, spp));
+}
+
+extern "C" int vrt_render_secondary_multi(vrt_multi *m, const vrt_camera *cam, const vrt_film *film, int spp,
+                                          float *vis, int64_t *rays)
+{
+        if (int rc = secondary_check(m, cam, film, spp, vis))
+                return rc;
+        return frame_out(m, film, 1, vis, nullptr, nullptr, secondary_work(m, cam, film, spp), [&]() -> int {
+                if (!rays)
+                        return VRT_OK;
+                // every rank's stream is idle: its counter is this frame's
+                const int64_t narea = (int64_t)(8 * (film->nx / 8)) * (8 * (film->ny / 8));
+                int64_t hits = 0;
+                if (narea)
+                        for (size_t i = 0; i < m->devs.size(); ++i) {
+                                uint64_t h = 0;
+                                HIPCHK(hipSetDevice(m->devs[i]));
+                                HIPCHK(hipMemcpy(&h, m->hits[i], sizeof h, hipMemcpyDeviceToHost));
+                                hits += (int64_t)h;
+                        }
+                *rays = narea + hits * spp;
+                return VRT_OK;
+        });
 }
 
 extern "C" int vrt_multi_set_light_mode(vrt_multi *m, int mode)
