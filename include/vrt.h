@@ -324,9 +324,24 @@ int vrt_device_selftest(int device, const double *mt_in, double *mt_out,
 /* VRT_TEST_SMALL_PROBE_CHUNK (the bit after it, unused before) makes
  * vrt_probe_gather[_device] work in chunks of 2 probes. */
 #define VRT_TEST_SMALL_PROBE_CHUNK 0x20000
+/* VRT_TEST_SMALL_BEAM_ENTRY: the persistent primary render takes the beam
+ * entry for a one-rank frame of any size; without it only
+ * frames of at least 65,536 units (4x4-pixel quadrants) do, because the
+ * pre-pass costs a small frame more than it saves. */
+#define VRT_TEST_SMALL_BEAM_ENTRY 0x40000
 int vrt_set_test_flags(int flags);
 /* The current vrt_set_test_flags value (so a caller can restore it). */
 int vrt_test_flags(void);
+
+/* Diagnostic: the beam-entry records of the scene's last persistent primary
+ * render (builds with VRT_BEAM_ENTRY), one per 4x4-pixel unit
+ * of the rank's share in unit order (4 * tile + quadrant), 16 words each:
+ * word 0 = 0xFFFFFFFF ("no entry"), else the number of stack entries | 0x100
+ * when the unit's rays take the chain order; words 2 + 2i, 3 + 2i = entry i
+ * (first child's node index, order | count << 24).  Waits for that launch;
+ * *units = its unit count (0: there was none), at most max_units records are
+ * copied to out. */
+int vrt_debug_beam_entries(vrt_scene *s, uint32_t *out, int64_t max_units, int64_t *units);
 
 /* Diagnostic: the records appended to each compaction queue (phase A, then
  * resume rounds 1..3; with the one streaming resume round only queue 0 is

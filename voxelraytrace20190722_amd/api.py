@@ -537,6 +537,19 @@ class VoxelOctree:
         in flight on different streams -> half-chip persistent grids."""
         check(lib().vrt_scene_set_frames_in_flight(self.h, int(n)), "vrt_scene_set_frames_in_flight")
 
+    def beam_entries(self):
+        """The beam-entry records of the last persistent primary render
+        (vrt_debug_beam_entries): uint32 [units, 16], or None when there was
+        none."""
+        n = C.c_int64()
+        check(lib().vrt_debug_beam_entries(self.h, None, 0, C.byref(n)), "vrt_debug_beam_entries")
+        if n.value <= 0:
+            return None
+        out = np.zeros((n.value, 16), np.uint32)
+        check(lib().vrt_debug_beam_entries(self.h, out.ctypes.data_as(_ffi.u32p), n.value, C.byref(n)),
+              "vrt_debug_beam_entries")
+        return out
+
     def secondary_spill_counts(self):
         """Records appended to each config-5 compaction queue (phase A, resume
         rounds 1..3) by the last secondary launch (vrt_secondary_spill_counts)."""
@@ -1345,6 +1358,7 @@ TEST_PRIM_TAIL = 64  # include/vrt.h VRT_TEST_PRIM_TAIL
 TEST_SEC_DEFER = 128  # include/vrt.h VRT_TEST_SEC_DEFER
 TEST_SMALL_BATCH_CHUNK = 0x10000  # include/vrt.h VRT_TEST_SMALL_BATCH_CHUNK
 TEST_SMALL_PROBE_CHUNK = 0x20000  # include/vrt.h VRT_TEST_SMALL_PROBE_CHUNK
+TEST_SMALL_BEAM_ENTRY = 0x40000  # include/vrt.h VRT_TEST_SMALL_BEAM_ENTRY
 
 
 def set_test_flags(flags):

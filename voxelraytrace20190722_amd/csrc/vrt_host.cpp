@@ -447,6 +447,13 @@ struct vrt_scene {
         uint32_t q_base[kQueueSlots][8] = {};
         LastUse q_use[kQueueSlots];
         int q_next = 0;
+        // beam-entry records (VRT_BEAM_ENTRY, vrt_internal.h): one buffer per
+        // ring slot, grown to the largest share rendered on it and protected
+        // by the slot's q_use like its counters; entry_slot / entry_units:
+        // the last persistent fast-only launch's (vrt_debug_beam_entries)
+        DevMem d_entry[kQueueSlots];
+        int entry_slot = -1;
+        int64_t entry_units = 0;
         Event lm_ev;  // vrt_trace_frame_device: the light map is filtered
         // vrt_render's host-output path (render_to_host): a device image kept
         // between calls, its pinned host staging copy, a second render stream
@@ -1560,7 +1567,33 @@ static int render_launch(vrt_scene *s, RenderParams &p, bool instrumented, hipSt
                         return rc;
         }
         int waves = 0, units[8];
-        const hipError_t e = launch_render(p, instrumented, st, &waves, units, s->ord_wmin);
+        uint32_t *entry = nullptr;
+        hipError_t e = hipSuccess;
+        if (slot >= 0)
+                s->entry_slot = -1;
+        // one-rank frames of at least kEntryMinUnits units only: a smaller
+        // frame, and a rank's share of a multi-rank frame, keep the waves' own
+        // prologue (both measured slower with the pre-pass)
+        if (VRT_BEAM_ENTRY && slot >= 0 && render_kind(p, instrumented) == kRenderPersistFast &&
+            p.tiles_this_rank > 0 && p.nranks == 1 &&
+            ((int64_t)p.tiles_this_rank * 4 >= kEntryMinUnits || (p.test_flags & VRT_TEST_SMALL_BEAM_ENTRY))) {
+                // the slot's record buffer, sized for this rank's units; one
+                // that must grow has no work in flight left after the host's
+                // wait for the slot's last launch
+                const int64_t nu = (int64_t)p.tiles_this_rank * 4;
+                const size_t need = (size_t)nu * kEntryWords * sizeof(uint32_t);
+                DevMem &d = s->d_entry[slot];
+                if (d.size() < need) {
+                        e = s->q_use[slot].sync();
+                        if (e == hipSuccess)
+                                e = d.alloc(need);
+                }
+                entry = d.as<uint32_t>();
+                s->entry_slot = e == hipSuccess ? slot : -1;
+                s->entry_units = nu;
+        }
+        if (e == hipSuccess)
+                e = launch_render(p, instrumented, st, &waves, units, s->ord_wmin, entry);
         if (e != hipSuccess) {
                 if (slot >= 0)
                         queue_reset(s, slot, st);
@@ -2251,6 +2284,8 @@ extern "C" int vrt_scene_scratch_bytes(vrt_scene *s, int64_t *bytes, int64_t *sp
         int64_t t = sp + (int64_t)s->d_light.size() + (int64_t)s->ho.img.cap + (int64_t)s->tb.cap;
         for (const TraceSet &ts : s->ts)
                 t += (int64_t)(ts.lm.size() + ts.rec.size());
+        for (const DevMem &e : s->d_entry)  // the beam-entry records of the ring slots used so far
+                t += (int64_t)e.size();
         for (const auto &m : s->dmaps)  // the tabled multi-rank deals
                 t += (int64_t)deal_count(tile_deal(m.ntx, m.nty, m.nranks), m.rank) * (int64_t)sizeof(uint32_t);
         *bytes = t;
@@ -2276,6 +2311,26 @@ extern "C" int vrt_secondary_spill_counts(vrt_scene *s, int64_t counts[4])
         HIPCHK(hipMemcpy(c.data(), s->d_spill[s->spill_last], c.size() * 4, hipMemcpyDeviceToHost));
         for (int r = 0; r < 4 && r < kSpillMaxRounds; ++r)
                 counts[r] = c[(size_t)r * kSpillCtrStride + 2];  // records (spill_close)
+        return VRT_OK;
+}
+
+extern "C" int vrt_debug_beam_entries(vrt_scene *s, uint32_t *out, int64_t max_units, int64_t *units)
+{
+        if (s && need_device(s))
+                return VRT_E_NODEVICE;
+        if (!s || !units || (max_units > 0 && !out) || max_units < 0)
+                return fail(VRT_E_INVALID, "null argument");
+        std::lock_guard<std::mutex> lk(s->mu);
+        *units = 0;
+        if (s->entry_slot < 0 || !s->d_entry[s->entry_slot])
+                return VRT_OK;
+        HIPCHK(hipSetDevice(s->device));
+        HIPCHK(s->q_use[s->entry_slot].sync());  // the slot's last launch
+        *units = s->entry_units;
+        const int64_t n = std::min(max_units, s->entry_units);
+        if (n > 0)
+                HIPCHK(hipMemcpy(out, s->d_entry[s->entry_slot], (size_t)n * kEntryWords * sizeof(uint32_t),
+                                 hipMemcpyDeviceToHost));
         return VRT_OK;
 }
 

@@ -195,6 +195,33 @@ struct WorkQueue {
         uint32_t *defer;
         uint32_t base[8];
 };
+// Beam entry of the persistent fast-only render (VRT_BEAM_ENTRY, DESIGN
+// §4.2): before k_render_p<true>, k_unit_entry walks the octree once per unit
+// (a unit's 64 rays share the origin) while every decision is certain for all
+// 64 rays, and records the walk's loop-top state where it stops; the unit's
+// wave starts there.  One record per unit, 64 B, one buffer per WorkQueue
+// ring slot (vrt_scene::d_entry):
+//   word 0: kEntryNone ("no entry": the wave runs its own prologue), else
+//           the number of stack entries (0: no ray of the unit can hit) |
+//           kEntryChainBit when every ray passes chain_criterion
+//   words 2 + 2i, 3 + 2i: stack entry i < kEntryMax in ray_march's format
+//           (base, order | cnt << 24), cnt > 0; the level being walked is the
+//           top entry
+#ifndef VRT_BEAM_ENTRY
+#define VRT_BEAM_ENTRY 1
+#endif
+constexpr int kEntryWords = 16;
+constexpr int kEntryMax = 7;
+constexpr uint32_t kEntryNone = 0xFFFFFFFFu;
+constexpr uint32_t kEntryCountMask = 0xFFu;
+constexpr uint32_t kEntryChainBit = 0x100u;
+// Smallest one-rank frame that takes the entry.  The pre-pass is one long
+// dependent chain per lane (64 rays, then ~10 visits): 0.07-0.11 ms alone at
+// 1080p (kernel trace), whatever the size, against a quarter of the render's
+// time saved.  Measured with 3 frames in flight: 8,160 units 0.180 -> 0.216
+// ms per frame, 32,640 units 0.310 -> 0.312, 129,600 units 0.86 -> 0.72
+// (DESIGN §4.1).  VRT_TEST_SMALL_BEAM_ENTRY lifts the limit.
+constexpr int64_t kEntryMinUnits = 65536;
 // units of slice x: a contiguous range [lo, hi) of the unit order
 __host__ __device__ inline void queue_range(int units, int x, int &lo, int &hi)
 {
@@ -774,8 +801,12 @@ int64_t camera_defer_bound(const CamParams &c);
 // no work queue was used), for the queue bases
 // ord_wmin: the scene's child-centre spacings of the chain order (3 floats,
 // vrt_scene::ord_wmin; nullptr or zeros = sort every expansion)
+// entry: the launch's beam-entry records (kEntryWords words per unit of the
+// rank's share; the persistent fast-only kind fills and reads them), or
+// nullptr
 hipError_t launch_render(const RenderParams &p, bool instrumented,
-                         hipStream_t st, int *q_waves, int slice_units[8], const float *ord_wmin = nullptr);
+                         hipStream_t st, int *q_waves, int slice_units[8], const float *ord_wmin = nullptr,
+                         uint32_t *entry = nullptr);
 // resident blocks of the persistent render / secondary kernels on the
 // current device
 hipError_t persistent_blocks(int *render_blocks, int *sec_blocks);

@@ -1063,12 +1063,13 @@ struct ChainW {
         float wmin[3];  // vrt_scene's ord_wmin; 0 = off
 };
 template <bool kCount, bool kFast, int kS, int kStd, int kUni, bool kR64, int kBudget = 0, bool kCullAsk = false,
-          bool kChainAsk = false>
+          bool kChainAsk = false, bool kEntry = false>
 __device__ __forceinline__ void ray_march(const DevScene &sc, const RayK &r,
                                           uint2 *stk,
                                           uint32_t *stk_aux,
                                           uint32_t *path_rem,
-                                          MarchResult &m, float cw0 = 0.0f, float cw1 = 0.0f, float cw2 = 0.0f)
+                                          MarchResult &m, float cw0 = 0.0f, float cw1 = 0.0f, float cw2 = 0.0f,
+                                          const uint32_t *entry = nullptr)
 {
         m.hit = false;
         m.deferred = false;
@@ -1084,17 +1085,39 @@ __device__ __forceinline__ void ray_march(const DevScene &sc, const RayK &r,
         constexpr bool kChain = VRT_CHAIN_ORDER && kChainAsk && kLB;
         const NodeRec *__restrict__ nodes = sc.nodes;  // kNB: xnodes instead
         const bool lbok = kLB && __all(leaf_box_ok(sc, r));  // wave-uniform: held in SGPRs
-        load_node(sc.nodes, 0, bmin, bmax, a, b);
+        // kEntry: the unit's beam-entry record (k_unit_entry; `entry` is
+        // wave-uniform, every lane reads the same 64 B).  Unless it says "no
+        // entry" (have), the walk starts from the recorded loop-top state: the
+        // entries go into this lane's stack column, the current level on top,
+        // and the loop's first iteration pops it (count 0: no ray of the unit
+        // can hit -- the loop ends at once).
+        static_assert(!kEntry || (kLB && VRT_BEAM_ENTRY), "the beam entry is the finite-slab walk's");
+        uint32_t ehdr = kEntryNone;
+        uint4 eq[4];
+        if (kEntry && entry) {
+                const uint4 *eqp = reinterpret_cast<const uint4 *>(entry);
+#pragma unroll
+                for (int i = 0; i < 4; ++i)
+                        eq[i] = eqp[i];
+                ehdr = __builtin_amdgcn_readfirstlane(eq[0].x);
+        }
+        const bool have = kEntry && ehdr != kEntryNone;
+        if (!have)
+                load_node(sc.nodes, 0, bmin, bmax, a, b);
         // wave-uniform for the whole walk (bmin / bmax: the root box), voted
         // by every lane that entered, before any leaves
         bool chain_on = false;
         if (kChain) {
-                const float wmin[3] = { cw0, cw1, cw2 };
-                chain_on = __all(chain_criterion(bmin, bmax, r, wmin));
+                if (!have) {
+                        const float wmin[3] = { cw0, cw1, cw2 };
+                        chain_on = __all(chain_criterion(bmin, bmax, r, wmin));
+                } else {
+                        chain_on = (ehdr & kEntryChainBit) != 0u;
+                }
         }
-        if (!aabb_isect(bmin, bmax, r.o, r.dinv, r.tmin, r.tmax))
+        if (!have && !aabb_isect(bmin, bmax, r.o, r.dinv, r.tmin, r.tmax))
                 return;
-        if (a & kLeafBit) {
+        if (!have && (a & kLeafBit)) {
                 if (kCount)
                         m.L++;
                 if (leaf_isect<kCount, kUni, kR64>(sc, b, a & ~kLeafBit, r, m)) {
@@ -1106,11 +1129,29 @@ __device__ __forceinline__ void ray_march(const DevScene &sc, const RayK &r,
         int cnt;
         uint32_t fpos;
         const uint32_t cs = 0u;  // remade per expansion (expand_v2's kRecs)
-        uint32_t order = expand<kCount, kFast, kStd, kChain>(bmin, bmax, r, cnt, fpos, kCount ? 0xFFu : b, chain_on, cs);
-        uint32_t base = a;
+        uint32_t order, base;
+        int sp = 0;
+        if (!have) {
+                order = expand<kCount, kFast, kStd, kChain>(bmin, bmax, r, cnt, fpos, kCount ? 0xFFu : b, chain_on, cs);
+                base = a;
+        } else {
+                sp = (int)(ehdr & kEntryCountMask);
+                stk[0 * kS] = make_uint2(eq[0].z, eq[0].w);
+                stk[1 * kS] = make_uint2(eq[1].x, eq[1].y);
+                stk[2 * kS] = make_uint2(eq[1].z, eq[1].w);
+                if (sp > 3) {
+                        stk[3 * kS] = make_uint2(eq[2].x, eq[2].y);
+                        stk[4 * kS] = make_uint2(eq[2].z, eq[2].w);
+                        stk[5 * kS] = make_uint2(eq[3].x, eq[3].y);
+                        stk[6 * kS] = make_uint2(eq[3].z, eq[3].w);
+                }
+                cnt = 0;
+                order = 0u;
+                base = 0u;
+                fpos = 0u;
+        }
         uint32_t depth = 1;  // depth of the node whose children we walk
         uint32_t nexp = 1;
-        int sp = 0;
         // while-while: every lane first advances (pop / expand) to its next
         // non-empty leaf in DFS order, then the lanes test their leaves
         // together -- expand and leaf code no longer interleave per lane.
@@ -1355,16 +1396,20 @@ __device__ __forceinline__ bool fin_ok(const RayK &r)
                fabsf(r.dinv.z) <= 0x1p64f;
 }
 
-template <bool kCount, int kS, int kUni, bool kR64, int kBudget = 0, bool kCullAsk = false, bool kChainAsk = false>
+// kEntry: `entry` is the unit's beam-entry record or nullptr; a record other
+// than "no entry" exists only for a unit whose 64 rays all pass fast_ok and
+// fin_ok, i.e. one that takes the finite-slab walk here.
+template <bool kCount, int kS, int kUni, bool kR64, int kBudget = 0, bool kCullAsk = false, bool kChainAsk = false,
+          bool kEntry = false>
 __device__ __forceinline__ void ray_march_dispatch(const DevScene &sc, const RayK &r,
                                                    uint2 *sb, uint32_t *sa, uint32_t *pr,
                                                    MarchResult &m, float cw0 = 0.0f, float cw1 = 0.0f,
-                                                   float cw2 = 0.0f)
+                                                   float cw2 = 0.0f, const uint32_t *entry = nullptr)
 {
         if (__all(sc.fast_ok && fast_ok(r))) {
                 if (!kCount && __all(fin_ok(r)))
-                        ray_march<kCount, true, kS, 2, kUni, kR64, kBudget, kCullAsk, kChainAsk>(sc, r, sb, sa, pr, m,
-                                                                                                 cw0, cw1, cw2);
+                        ray_march<kCount, true, kS, 2, kUni, kR64, kBudget, kCullAsk, kChainAsk, kEntry>(
+                                sc, r, sb, sa, pr, m, cw0, cw1, cw2, entry);
                 else
                         ray_march<kCount, true, kS, 0, kUni, kR64, kBudget>(sc, r, sb, sa, pr, m);
         } else
@@ -2063,10 +2108,13 @@ constexpr int kRenderBlock = 64;
 // standard-range instantiation is compiled in (fewer live registers); a wave
 // whose rays need another path returns false before writing anything and the
 // caller defers the unit to k_render_defer.
-template <bool kCount, bool kR64, int kS, bool kSamples = true, bool kFastOnly = false>
+// kWalkAsk (the deferred pass): the general dispatch's finite-slab walk culls
+// leaf records, takes the chain order and starts from the unit's beam entry
+// like the fast-only kernel's.
+template <bool kCount, bool kR64, int kS, bool kSamples = true, bool kFastOnly = false, bool kWalkAsk = false>
 __device__ __forceinline__ bool render_unit(const RenderParams &p, int k, int wave, int lane, uint2 *stk,
                                             uint32_t *stk_aux, uint32_t *path_rem, float cw0 = 0.0f, float cw1 = 0.0f,
-                                            float cw2 = 0.0f)
+                                            float cw2 = 0.0f, const uint32_t *entry = nullptr)
 {
         // the lane id is re-read per unit (volatile asm: not hoisted out of
         // a persistent loop), so its derived per-lane constants are
@@ -2126,6 +2174,8 @@ __device__ __forceinline__ bool render_unit(const RenderParams &p, int k, int wa
 #if VRT_PHASE_STAMPS
         unsigned long long d_m1 = 0;
 #endif
+        // this unit's beam-entry record (unit = 4 * k + wave, wave-uniform)
+        const uint32_t *er = VRT_BEAM_ENTRY && entry ? entry + (size_t)(k * 4 + wave) * kEntryWords : nullptr;
         if (kFastOnly) {
                 if (!wave_fast_std(p.sc, r) || (p.test_flags & VRT_TEST_FORCE_DEFER))
                         return false;
@@ -2134,15 +2184,16 @@ __device__ __forceinline__ bool render_unit(const RenderParams &p, int k, int wa
                 if (lane_now() == 0)
                         atomicAdd(&g_phase[21], d_m0 - d_r0);
 #endif
-                ray_march<false, true, kS, kFastStd, true, kR64, 0, true, true>(p.sc, r, stk, nullptr, nullptr, m, cw0, cw1,
-                                                                                cw2);
+                ray_march<false, true, kS, kFastStd, true, kR64, 0, true, true, VRT_BEAM_ENTRY != 0>(
+                        p.sc, r, stk, nullptr, nullptr, m, cw0, cw1, cw2, er);
 #if VRT_PHASE_STAMPS
                 d_m1 = __builtin_amdgcn_s_memtime();
                 if (lane_now() == 0)
                         atomicAdd(&g_phase[22], d_m1 - d_m0);
 #endif
         } else {
-                ray_march_dispatch<kCount, kS, true, kR64>(p.sc, r, stk, stk_aux, path_rem, m);
+                ray_march_dispatch<kCount, kS, true, kR64, 0, kWalkAsk, kWalkAsk, kWalkAsk>(p.sc, r, stk, stk_aux, path_rem,
+                                                                                            m, cw0, cw1, cw2, er);
         }
 #if VRT_UNIT_DIAG && VRT_LIGHT_DIAG
         if (kFastOnly) {
@@ -2295,7 +2346,8 @@ constexpr int kPersistHelp = 2;
 #define VRT_PERSIST_WAVES_PER_EU 6
 #endif
 template <bool kFastOnly>
-__global__ __launch_bounds__(kPersistBlock, VRT_PERSIST_WAVES_PER_EU) void k_render_p(RenderParams p, ChainW cw)
+__global__ __launch_bounds__(kPersistBlock, VRT_PERSIST_WAVES_PER_EU) void k_render_p(RenderParams p, ChainW cw,
+                                                                                      const uint32_t *entry)
 {
         __shared__ uint2 stk[kStack * kPersistBlock];
         const int tid = threadIdx.x, lane = tid & 63;
@@ -2324,7 +2376,8 @@ __global__ __launch_bounds__(kPersistBlock, VRT_PERSIST_WAVES_PER_EU) void k_ren
                         const uint32_t dg_u0 = (uint32_t)__builtin_amdgcn_s_memrealtime();
 #endif
                         const bool done = render_unit<false, false, kPersistBlock, false, kFastOnly>(
-                                p, kq >> 2, kq & 3, lane, stk + tid, nullptr, nullptr, cw.wmin[0], cw.wmin[1], cw.wmin[2]);
+                                p, kq >> 2, kq & 3, lane, stk + tid, nullptr, nullptr, cw.wmin[0], cw.wmin[1], cw.wmin[2],
+                                kFastOnly ? entry : nullptr);
 #if VRT_UNIT_DIAG
                         {
                                 const uint32_t dg_u1 = (uint32_t)__builtin_amdgcn_s_memrealtime();
@@ -2358,11 +2411,242 @@ __global__ __launch_bounds__(kPersistBlock, VRT_PERSIST_WAVES_PER_EU) void k_ren
         }
 }
 
+// ---------------------------------------------------------------------------
+// Beam entry (VRT_BEAM_ENTRY; record format in vrt_internal.h): one lane per
+// unit of the rank's share.  The lane makes the unit's 64 rays with
+// render_unit's own operations and keeps, per axis, the smallest and largest
+// dinv; then it runs ray_march's loop for the finite-slab walk (pop, visit,
+// triangle-box test, leaf / internal dispatch, push, expand, order) and
+// commits an iteration only when every decision in it is the same for all 64
+// rays.  Every slab distance of the walk is fl(c * dinv_k) with c = fl(plane -
+// o_k) the same for all rays of the unit; a rounded product is monotone in
+// dinv_k, and so are fminf, fmaxf and the tmin fold, so each ray's t0 / t1
+// lie between the values the same operations give at the extreme dinv_k: no
+// epsilon.  hit for certain: T0hi <= T1lo; missed for certain: T0lo > T1hi.
+// ---------------------------------------------------------------------------
+struct BeamIv {
+        float lo, hi;
+};
+// fl((plane - o) * dinv) over dinv in [dlo, dhi]
+__device__ __forceinline__ BeamIv beam_mul(float plane, float o, float dlo, float dhi)
+{
+        const float c = plane - o;
+        const float a = c * dlo, b = c * dhi;
+        return BeamIv{ fminf(a, b), fmaxf(a, b) };
+}
+// 0: missed for certain, 1: hit for certain, 2: uncertain
+__device__ __forceinline__ int beam_verdict(float t0lo, float t0hi, float t1lo, float t1hi)
+{
+        if (t0hi <= t1lo)
+                return 1;
+        if (t0lo > t1hi)
+                return 0;
+        return 2;
+}
+// line_meets_box (fold = false) / aabb_isect in the standard range (fold =
+// true: max(t0, +0) <= t1) over the beam
+__device__ __forceinline__ int beam_box(const float bmin[3], const float bmax[3], const float o[3], const float dlo[3],
+                                        const float dhi[3], bool fold)
+{
+        float t0lo = 0.f, t0hi = 0.f, t1lo = 0.f, t1hi = 0.f;
+#pragma unroll
+        for (int k = 0; k < 3; ++k) {
+                const BeamIv a = beam_mul(bmin[k], o[k], dlo[k], dhi[k]);
+                const BeamIv b = beam_mul(bmax[k], o[k], dlo[k], dhi[k]);
+                const float nlo = fminf(a.lo, b.lo), nhi = fminf(a.hi, b.hi);
+                const float flo = fmaxf(a.lo, b.lo), fhi = fmaxf(a.hi, b.hi);
+                t0lo = k ? fmaxf(t0lo, nlo) : nlo;
+                t0hi = k ? fmaxf(t0hi, nhi) : nhi;
+                t1lo = k ? fminf(t1lo, flo) : flo;
+                t1hi = k ? fminf(t1hi, fhi) : fhi;
+        }
+        if (fold) {
+                t0lo = fmaxf(t0lo, 0.0f);
+                t0hi = fmaxf(t0hi, 0.0f);
+        }
+        return beam_verdict(t0lo, t0hi, t1lo, t1hi);
+}
+// expand_v2<2>'s slab tests over the beam: the children hit for certain in
+// `hm`; false when some content child is uncertain
+__device__ __forceinline__ bool beam_expand(const float bmin[3], const float bmax[3], const float o[3],
+                                            const float dlo[3], const float dhi[3], uint32_t content, uint32_t &hm)
+{
+        BeamIv nr[3][2], fr[3][2];
+#pragma unroll
+        for (int k = 0; k < 3; ++k) {
+                const float h = (bmax[k] - bmin[k]) / 2.0f;
+                const float a0 = bmin[k];
+                const float b = bmin[k] + h;
+                const float c = b + h;
+                const BeamIv ta = beam_mul(a0, o[k], dlo[k], dhi[k]);
+                const BeamIv tb = beam_mul(b, o[k], dlo[k], dhi[k]);
+                const BeamIv tc = beam_mul(c, o[k], dlo[k], dhi[k]);
+                nr[k][0] = BeamIv{ fminf(ta.lo, tb.lo), fminf(ta.hi, tb.hi) };
+                fr[k][0] = BeamIv{ fmaxf(ta.lo, tb.lo), fmaxf(ta.hi, tb.hi) };
+                nr[k][1] = BeamIv{ fminf(tb.lo, tc.lo), fminf(tb.hi, tc.hi) };
+                fr[k][1] = BeamIv{ fmaxf(tb.lo, tc.lo), fmaxf(tb.hi, tc.hi) };
+        }
+#pragma unroll
+        for (int j = 0; j < 2; ++j) {  // the tmin fold (tmin = +0)
+                nr[2][j].lo = fmaxf(nr[2][j].lo, 0.0f);
+                nr[2][j].hi = fmaxf(nr[2][j].hi, 0.0f);
+        }
+        hm = 0u;
+        bool sure = true;
+#pragma unroll
+        for (int i = 0; i < 8; ++i) {
+                const int mx = (i >> 2) & 1, my = (i >> 1) & 1, mz = i & 1;
+                const float t0lo = fmaxf(fmaxf(nr[0][mx].lo, nr[1][my].lo), nr[2][mz].lo);
+                const float t0hi = fmaxf(fmaxf(nr[0][mx].hi, nr[1][my].hi), nr[2][mz].hi);
+                const float t1lo = fminf(fminf(fr[0][mx].lo, fr[1][my].lo), fr[2][mz].lo);
+                const float t1hi = fminf(fminf(fr[0][mx].hi, fr[1][my].hi), fr[2][mz].hi);
+                const int v = beam_verdict(t0lo, t0hi, t1lo, t1hi);
+                if ((content >> i) & 1u) {
+                        sure = sure && v != 2;
+                        hm |= (uint32_t)(v == 1) << i;
+                }
+        }
+        return sure;
+}
+
+constexpr int kBeamIterCap = 4096;  // far above any walk's length: the loop ends without it
+__global__ __launch_bounds__(64) void k_unit_entry(RenderParams p, ChainW cw, uint32_t *__restrict__ entry)
+{
+        const int u = blockIdx.x * 64 + threadIdx.x;
+        if (u >= p.tiles_this_rank * 4)
+                return;
+        uint32_t *rec = entry + (size_t)u * kEntryWords;
+        uint2 *stk = reinterpret_cast<uint2 *>(rec + 2);
+        rec[1] = 0u;
+        const CamParams &c = p.cam;
+        const int k = u >> 2, wave = u & 3;
+        int tx, ty;
+        // render_unit's own tile (k varies per lane here: rank_tile's tabled
+        // case becomes a vector load)
+        rank_tile(p.ntx, p.nty, p.nranks, p.rank, p.ntx_magic, p.tile_xy, k, tx, ty);
+        ty += p.ty0;
+        float rmin[3], rmax[3];
+        uint32_t a, b;
+        load_node(p.sc.nodes, 0, rmin, rmax, a, b);
+        const float o[3] = { c.origin[0], c.origin[1], c.origin[2] };
+        float dlo[3] = { 0.f, 0.f, 0.f }, dhi[3] = { 0.f, 0.f, 0.f };
+        uint32_t s_or = 0u, s_and = 7u;
+        bool ok = p.sc.fast_ok != 0, chain = true;
+#pragma unroll 1
+        for (int l = 0; l < 64; ++l) {
+                const int s = l & 3, pix = l >> 2;
+                const int px = tx * 8 + (wave & 1) * 4 + (pix & 3);
+                const int py = ty * 8 + (wave >> 1) * 4 + (pix >> 2);
+                const f3 dn = camera_dir(c.s, c.u, c.nf, c.e, c.z, c.nx, c.ny, px, py, sample_x(s), sample_y(s));
+                const RayK r = make_rayk(mk3(o[0], o[1], o[2]), dn, c.tmin, c.tmax);
+                ok = ok && fast_ok(r) && __float_as_uint(r.tmin) == 0u && r.tmax == kFltMax && fin_ok(r);
+                chain = chain && chain_criterion(rmin, rmax, r, cw.wmin);
+                const uint32_t cs = chain_signs(r);
+                s_or |= cs;
+                s_and &= cs;
+                const float di[3] = { r.dinv.x, r.dinv.y, r.dinv.z };
+#pragma unroll
+                for (int q = 0; q < 3; ++q) {
+                        dlo[q] = l ? fminf(dlo[q], di[q]) : di[q];
+                        dhi[q] = l ? fmaxf(dhi[q], di[q]) : di[q];
+                }
+        }
+        if (!ok || s_or != s_and || (a & kLeafBit) ||
+            beam_box(rmin, rmax, o, dlo, dhi, true) != 1) {
+                rec[0] = kEntryNone;
+                return;
+        }
+        const RayK ro = make_rayk(mk3(o[0], o[1], o[2]), mk3(0.f, 0.f, 0.f), 0.f, 0.f);
+        const bool lbok = leaf_box_ok(p.sc, ro);  // the origin alone decides
+        const uint32_t cs = s_or;
+        // the root's expansion, then ray_march's loop; (sp, base, order, cnt)
+        // is the loop-top state, stack entries 0 .. sp - 1 lie in the record
+        int sp = 0, cnt = 0;
+        uint32_t base = a, order = 0u;
+        // an expansion's order for the whole beam; false: not certain
+        auto beam_order = [&](uint32_t hm, uint32_t &ord) {
+                const int n = __popc(hm);
+                if (n <= 1) {
+                        ord = (uint32_t)__builtin_ctz(hm | 0x100u) & 7u;
+                        return true;
+                }
+                bool valid;
+                ord = n <= 2 ? chain_order2(hm, cs, valid) : chain_order4(hm, cs, valid);
+                ord &= (1u << (3 * (n > 4 ? 4 : n))) - 1u;
+                return chain && valid;
+        };
+        {
+                uint32_t hm;
+                if (!beam_expand(rmin, rmax, o, dlo, dhi, b, hm) || !beam_order(hm, order)) {
+                        rec[0] = kEntryNone;  // nothing committed: the wave's own prologue
+                        return;
+                }
+                cnt = __popc(hm);
+        }
+#pragma unroll 1
+        for (int it = 0; it < kBeamIterCap; ++it) {
+                // loop top; an iteration either commits (the state advances)
+                // or breaks with the state untouched
+                int sp1 = sp, cnt1 = cnt;
+                uint32_t base1 = base, order1 = order;
+                if (cnt1 == 0) {
+                        if (sp1 == 0)
+                                break;  // the walk ends: no ray of the unit hits
+                        --sp1;
+                        const uint2 e = stk[sp1];
+                        base1 = e.x;
+                        order1 = e.y & 0xFFFFFFu;
+                        cnt1 = (int)(e.y >> 24);
+                }
+                const uint32_t ci = order1 & 7u;
+                order1 >>= 3;
+                --cnt1;
+                const uint32_t node = base1 + ci;
+                float bmin[3], bmax[3], tmn[3], tmx[3];
+                uint32_t na, nb;
+                load_xnode(p.sc.xnodes, node, bmin, bmax, na, nb, tmn, tmx);
+                const int tb = lbok ? beam_box(tmn, tmx, o, dlo, dhi, false) : 1;
+                if (tb == 2)
+                        break;
+                if (tb == 1) {
+                        if (na & kLeafBit) {
+                                if ((na & ~kLeafBit) != 0u)
+                                        break;  // a leaf's triangles: the wave's work
+                        } else {
+                                uint32_t hm, ord;
+                                if (!beam_expand(bmin, bmax, o, dlo, dhi, nb, hm) || !beam_order(hm, ord))
+                                        break;
+                                if (cnt1) {
+                                        // the record holds sp entries and the current level
+                                        if (sp1 + 2 > kEntryMax)
+                                                break;
+                                        stk[sp1] = make_uint2(base1, order1 | ((uint32_t)cnt1 << 24));
+                                        ++sp1;
+                                }
+                                order1 = ord;
+                                cnt1 = __popc(hm);
+                                base1 = na;
+                        }
+                }
+                sp = sp1, cnt = cnt1, base = base1, order = order1;
+        }
+        if (cnt > 0) {
+                stk[sp] = make_uint2(base, order | ((uint32_t)cnt << 24));
+                ++sp;
+        }
+        rec[0] = (uint32_t)sp | (chain ? kEntryChainBit : 0u);
+}
+
 // The units k_render_p<true> deferred (normally none), rendered with the
-// general march (ray_march_dispatch) by half as many workgroups as the
-// persistent launch (so even a frame whose every unit was deferred runs on
-// half the resident slots; a latency-bound march loses far less than half
-// its rate).  No deferred unit: every wave returns after 8 scalar loads.
+// general march (ray_march_dispatch) by at most as many workgroups as the
+// persistent launch (a frame whose every unit was deferred runs on the
+// whole chip; half the grid kept such a frame under twice a normal one only
+// until the beam entry made the normal frame faster; for the same reason its
+// finite-slab walk now culls leaf records, takes the chain order and starts
+// from the beam entries, as the fast-only kernel's does -- a unit deferred
+// for its rays has a "no entry" record, one deferred by VRT_TEST_FORCE_DEFER
+// or re-rendered with its whole slice has its usual record).  No deferred unit: every wave returns after 8
+// scalar loads.
 // Otherwise each wave walks the XCD slices like k_render_p (its own first),
 // taking a slice's list entries -- or, past kDeferSliceCap, every unit of
 // the slice (the render is deterministic, so units already written are
@@ -2370,7 +2654,8 @@ __global__ __launch_bounds__(kPersistBlock, VRT_PERSIST_WAVES_PER_EU) void k_ren
 // whole-wave atomics; the last wave to finish zeroes the counts and
 // counters for the queue slot's next launch (every other wave has finished
 // reading them: its done-add follows its last, returned, take).
-__global__ __launch_bounds__(kPersistBlock, VRT_PERSIST_WAVES_PER_EU) void k_render_defer(RenderParams p)
+__global__ __launch_bounds__(kPersistBlock, VRT_PERSIST_WAVES_PER_EU) void k_render_defer(RenderParams p, ChainW cw,
+                                                                                          const uint32_t *entry)
 {
         __shared__ uint2 stk[kStack * kPersistBlock];
         const int tid = threadIdx.x, lane = tid & 63;
@@ -2396,8 +2681,9 @@ __global__ __launch_bounds__(kPersistBlock, VRT_PERSIST_WAVES_PER_EU) void k_ren
                         const uint32_t unit = all ? (uint32_t)slice_unit(units, x, (int)i, VRT_SLICE_CHUNK)
                                                   : __builtin_amdgcn_readfirstlane(
                                                             p.q.defer[kDeferList + x * kDeferSliceCap + i]);
-                        render_unit<false, false, kPersistBlock, false, false>(
-                                p, (int)(unit >> 2), (int)(unit & 3), lane, stk + tid, nullptr, nullptr);
+                        render_unit<false, false, kPersistBlock, false, false, VRT_BEAM_ENTRY != 0>(
+                                p, (int)(unit >> 2), (int)(unit & 3), lane, stk + tid, nullptr, nullptr, cw.wmin[0],
+                                cw.wmin[1], cw.wmin[2], entry);
                 }
         }
         const uint32_t fin = take_unit(p.q.defer + kDeferDoneWord);
@@ -4096,7 +4382,7 @@ static ChainW chain_w(const float *ord_wmin)
 }
 
 hipError_t launch_render(const RenderParams &p, bool instrumented,
-                         hipStream_t st, int *q_waves, int slice_units[8], const float *ord_wmin)
+                         hipStream_t st, int *q_waves, int slice_units[8], const float *ord_wmin, uint32_t *entry)
 {
         const ChainW cw = chain_w(ord_wmin);
         *q_waves = 0;
@@ -4117,7 +4403,16 @@ hipError_t launch_render(const RenderParams &p, bool instrumented,
                 const int cap = std::max(8, p.nranks > 1 ? full - kCollectiveReserve : full);
                 const int g = std::min(cap, need);
                 if (kind == kRenderPersistFast) {
-                        hipLaunchKernelGGL(k_render_p<true>, dim3(g), dim3(kPersistBlock), 0, st, p, cw);
+                        if (VRT_BEAM_ENTRY && entry) {
+                                // every frame's own pre-pass (camera poses do not repeat), on
+                                // the frame's stream directly before the render
+                                const int units = p.tiles_this_rank * 4;
+                                hipLaunchKernelGGL(k_unit_entry, dim3((units + 63) / 64), dim3(64), 0, st, p, cw, entry);
+                                if (hipError_t e = hipGetLastError())
+                                        return e;
+                        }
+                        hipLaunchKernelGGL(k_render_p<true>, dim3(g), dim3(kPersistBlock), 0, st, p, cw,
+                                           VRT_BEAM_ENTRY ? (const uint32_t *)entry : nullptr);
                         if (hipError_t e = hipGetLastError())
                                 return e;
 #if VRT_UNIT_DIAG
@@ -4148,19 +4443,21 @@ hipError_t launch_render(const RenderParams &p, bool instrumented,
                         if (p.test_flags & VRT_TEST_FAIL_LAUNCH)  // test hook: fail between the two launches
                                 return hipErrorLaunchFailure;
                         // the deferred pass only when some ray of the frame may
-                        // defer, on half the persistent grid, or fewer blocks when
-                        // the host's bound says only a few units can be deferred
-                        // (each of the grid's waves then takes at most one)
+                        // defer, on a grid as large as the persistent launch's, or
+                        // fewer blocks when the host's bound says only a few units
+                        // can be deferred (each of the grid's waves then takes at
+                        // most one)
                         const int64_t nd = (p.test_flags & VRT_TEST_FORCE_DEFER) ? INT64_MAX
                                                                                   : camera_defer_bound(p.cam);
                         if (nd > 0) {
-                                const int half = std::max(8, (g / 2) & ~7);
                                 const int64_t want = ((nd + 3) / 4 + 7) & ~int64_t(7);
-                                const int gd = (int)std::min<int64_t>(half, std::max<int64_t>(8, want));
-                                hipLaunchKernelGGL(k_render_defer, dim3(gd), dim3(kPersistBlock), 0, st, p);
+                                const int gd = (int)std::min<int64_t>(g, std::max<int64_t>(8, want));
+                                hipLaunchKernelGGL(k_render_defer, dim3(gd), dim3(kPersistBlock), 0, st, p, cw,
+                                                   VRT_BEAM_ENTRY ? (const uint32_t *)entry : nullptr);
                         }
                 } else {
-                        hipLaunchKernelGGL(k_render_p<false>, dim3(g), dim3(kPersistBlock), 0, st, p, cw);
+                        hipLaunchKernelGGL(k_render_p<false>, dim3(g), dim3(kPersistBlock), 0, st, p, cw,
+                                           (const uint32_t *)nullptr);
                 }
                 // failing adds per slice counter: one from every wave of the
                 // kPersistHelp XCDs that visit it (g/8 blocks per XCD)
@@ -5929,6 +6226,7 @@ bool build_flag(const char *name, int64_t *value)
                 { "VRT_LIGHT_BUDGET", VRT_LIGHT_BUDGET },
                 { "VRT_PRIM_BUDGET", VRT_PRIM_BUDGET },
                 { "VRT_CHAIN_ORDER", VRT_CHAIN_ORDER },
+                { "VRT_BEAM_ENTRY", VRT_BEAM_ENTRY },
                 { "VRT_LEAF_CULL", VRT_LEAF_CULL },
                 { "VRT_LEAF_CULL_BOX", VRT_LEAF_CULL_BOX },
                 { "VRT_LEAF_CULL_GROUP", VRT_LEAF_CULL_GROUP },
