@@ -329,6 +329,11 @@ int vrt_device_selftest(int device, const double *mt_in, double *mt_out,
  * frames of at least 65,536 units (4x4-pixel quadrants) do, because the
  * pre-pass costs a small frame more than it saves. */
 #define VRT_TEST_SMALL_BEAM_ENTRY 0x40000
+/* VRT_TEST_UPDATE_TOO_LARGE makes vrt_scene_update[_device]'s device build
+ * report its size limit ("octree too large") after the frontier has been
+ * expanded: the refusal a huge scene would meet, which must leave the scene
+ * on its previous geometry.  A host-side error return. */
+#define VRT_TEST_UPDATE_TOO_LARGE 0x80000
 int vrt_set_test_flags(int flags);
 /* The current vrt_set_test_flags value (so a caller can restore it). */
 int vrt_test_flags(void);
@@ -397,6 +402,42 @@ int vrt_device_selftest_chain(int device, const float *cases, int64_t n,
 /* The scene's chain-order constant: per axis the smallest spacing of the two
  * child centres over its internal nodes; zeros = the chain order is off. */
 int vrt_scene_chain_spacing(const vrt_scene *s, float out[3]);
+
+/* ---- moving geometry -------------------------------------------------------
+ * Replace the scene's vertex positions (ntri*9 floats, the layout of
+ * vrt_scene_desc::pos) and, unless nrm is NULL, its vertex normals (ntri*9,
+ * normalised as at creation); rebuild octree, leaf records, march records and
+ * shading tables.  ntri, uv, materials, textures, max_depth, device unchanged.
+ * Afterwards the scene equals, bit for bit, one created with
+ * vrt_scene_create_ex(VRT_BUILD_DEVICE) from the same description with these
+ * arrays: every query, render and device array; the light map and every other
+ * derived state are a fresh scene's (build the light map again), while
+ * vrt_scene_set_frames_in_flight, streams, queues and scratch stay.  The call
+ * waits for all work the scene has in flight first, on whatever stream it was
+ * launched: it synchronises the scene's device.  (Calls on the scene from
+ * other threads during an update are the caller's to exclude.)  A device scene
+ * rebuilds on the GPU; a host-only scene (device < 0) runs the host build.  A
+ * refused update (VRT_E_INVALID: null arguments, a scene with light probes, a
+ * rank scene of a vrt_multi handle, a size limit of the build; no memory)
+ * leaves the scene on its previous geometry, fully usable.  Only VRT_E_DEVICE
+ * (a failed launch or copy) can leave it half rebuilt: destroy it then. */
+int vrt_scene_update(vrt_scene *s, const float *pos, const float *nrm);
+/* The same from device memory on the scene's device.  The arrays are read in
+ * `stream` order (NULL = the null stream).  On return the scene is ready and
+ * the caller may overwrite the arrays. */
+int vrt_scene_update_device(vrt_scene *s, const float *d_pos, const float *d_nrm, void *stream);
+/* Wall-clock split of the last update: {total, GPU (events), copy back, host}. */
+int vrt_scene_update_stats(const vrt_scene *s, double ms[4]);
+/* The device memory an updated scene keeps for its next update (the build's
+ * frontier, sort and flatten arrays and the finish kernels' scratch), which
+ * neither vrt_scene_info's device_bytes nor vrt_scene_scratch_bytes counts:
+ * *bytes as held on entry; 0 on a scene never updated.  release != 0 frees it
+ * (and the spare host mirrors); the next update allocates it again. */
+int vrt_scene_update_scratch(vrt_scene *s, int release, int64_t *bytes);
+/* Test access: copy one derived device array of the scene to the host.
+ * kind: 0 leaf records (48 or 64 B each), 1 per-record boxes (device order, pad excluded),
+ * 2 xnodes, 3 TriPos, 4 TriAttr.  out == NULL returns only *bytes. */
+int vrt_scene_device_array(vrt_scene *s, int kind, void *out, int64_t cap, int64_t *bytes);
 
 /* ---- multi-device frame (render_mt, VRT/camera.h:42-68,
  * over the GPUs of one node) --------------------------------------------------

@@ -1,0 +1,134 @@
+#!/usr/bin/env python3
+"""Moving geometry: vrt_scene_update against destroy + create.
+
+On the sponza-proxy (detail 1.0 by default) at depths 6, 8, 9 and 10, in one
+process, alternating, best of three each:
+  (a) destroy the scene, vrt_scene_create_ex(VRT_BUILD_DEVICE) on the moved
+      positions -- what a caller had to do before vrt_scene_update;
+  (b) vrt_scene_update from host arrays and vrt_scene_update_device from
+      device arrays, on a second handle that lives through the whole run, to
+      the positions (a) has just built from, with vrt_scene_update_stats'
+      split.  That handle's first update, which allocates what later ones
+      keep, is reported apart, and two more updates of each kind pass before
+      the first one that counts.
+The positions alternate between two rigid placements from round to round (the
+moved one, the original, the moved one), and the updated handle always holds
+the other placement, so every step rebuilds a different tree than the one it
+starts from; "moved" is the best of the rounds on the moved placement for all
+three, like against like.  One device build runs first at every depth and is
+not counted (the first one in a process loads the code object).
+
+  --lib PATH     load this libvrt.so instead of the package's
+  --create-only  (a) only: for a library from before vrt_scene_update, to show
+                 that the create path did not move
+Prints and, with --out, writes one JSON document."""
+import argparse
+import json
+import os
+import sys
+import time
+
+import numpy as np
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--detail", type=float, default=1.0)
+    ap.add_argument("--depths", default="6,8,9,10")
+    ap.add_argument("--reps", type=int, default=3)
+    ap.add_argument("--lib")
+    ap.add_argument("--create-only", action="store_true")
+    ap.add_argument("--out")
+    a = ap.parse_args()
+
+    import torch  # first: one HIP runtime per process
+    from voxelraytrace20190722_amd import _ffi
+    if a.lib:
+        _ffi.LIB_PATH = os.path.abspath(a.lib)
+        if a.create_only:  # an older library lacks the new symbols
+            for name in [n for n in _ffi.SIGNATURES if n.startswith(("vrt_scene_update", "vrt_scene_device_array"))]:
+                del _ffi.SIGNATURES[name]
+    import voxelraytrace20190722_amd as vrt
+
+    sd = vrt.SceneData.proxy(a.detail, 1)
+    p3 = sd.pos.reshape(-1, 3)
+    c, s = np.float32(np.cos(0.3)), np.float32(np.sin(0.3))
+    R = np.array(((c, 0, s), (0, 1, 0), (-s, 0, c)), np.float32)
+    places = [sd.pos,
+              np.ascontiguousarray((p3 @ R.T + np.array((0.5, 0.25, -0.5), np.float32)).astype(np.float32)
+                                   .reshape(-1, 9))]
+    scenes = [vrt.SceneData(p, sd.nrm, sd.uv, sd.mat, sd.mat_tex, sd.mat_kd, sd.tex_dims, sd.tex_off, sd.tex_data)
+              for p in places]
+    d_places = [torch.from_numpy(p).cuda() for p in places]
+    torch.cuda.synchronize()
+    doc = {"scene": "sponza-proxy", "detail": a.detail, "triangles": int(sd.ntri), "reps": a.reps,
+           "library": vrt.build_id(), "device": torch.cuda.get_device_name(0), "depths": {}}
+    def timed_update(live, kind, k):
+        t0 = time.perf_counter()
+        if kind == "host":
+            live.update(places[k])
+        else:
+            live.update_device(d_places[k].data_ptr())
+        return dict(live.update_stats(), wall=(time.perf_counter() - t0) * 1e3, placement=k)
+
+    for depth in [int(x) for x in a.depths.split(",")]:
+        tree = vrt.VoxelOctree(scenes[0], depth, build_on_device=True)  # warm-up, not counted
+        create, upd, upd_dev = [], [], []
+        live = first = None
+        if not a.create_only:
+            # the handle that is updated lives through the depth's whole run.
+            # Its first update allocates the build's scratch and the host
+            # mirrors' second halves and is reported apart; one update of each
+            # kind after it is not counted, the rest are the steady state.
+            live = vrt.VoxelOctree(scenes[0], depth, build_on_device=True)
+            first = timed_update(live, "host", 1)
+            timed_update(live, "device", 0)
+            timed_update(live, "host", 1)
+            timed_update(live, "device", 0)
+        k = 0
+        for _ in range(a.reps):
+            k ^= 1  # this round's positions: 1, 0, 1, ... for (a) and (b) alike
+            t0 = time.perf_counter()
+            tree.close()
+            tree = vrt.VoxelOctree(scenes[k], depth, build_on_device=True)
+            create.append({"total": (time.perf_counter() - t0) * 1e3, "build_ms": tree.info.build_ms,
+                           "upload_ms": tree.info.upload_ms, "gpu": tree.info.build_device_ms, "placement": k})
+            if a.create_only:
+                continue
+            # live holds the other placement: each update rebuilds the tree
+            # (a) has just built, from a different one; between the two it is
+            # moved back, not counted
+            upd.append(timed_update(live, "host", k))
+            timed_update(live, "host", k ^ 1)
+            upd_dev.append(timed_update(live, "device", k))
+            assert int(live.info.nodes) == int(tree.info.nodes) and int(live.info.tri_refs) == int(tree.info.tri_refs)
+        row = {"nodes": int(tree.info.nodes), "tri_refs": int(tree.info.tri_refs),
+               "create": min(create, key=lambda r: r["total"])}
+        if not a.create_only:
+            row["update_first"] = first
+            row["update"] = min(upd, key=lambda r: r["wall"])
+            row["update_device"] = min(upd_dev, key=lambda r: r["wall"])
+            # like against like: the best of the rounds on the moved positions
+            row["moved"] = {"create": min(r["total"] for r in create if r["placement"] == 1),
+                            "update": min(r["wall"] for r in upd if r["placement"] == 1),
+                            "update_device": min(r["wall"] for r in upd_dev if r["placement"] == 1)}
+            row["update_scratch_bytes"] = int(live.update_scratch())
+            row["device_bytes"] = int(live.info.device_bytes)
+            row["rounds"] = {"create": create, "update": upd, "update_device": upd_dev}
+            live.close()
+        doc["depths"][str(depth)] = row
+        tree.close()
+        print(f"depth {depth}: " + json.dumps(row), flush=True)
+    text = json.dumps(doc, indent=1)
+    if a.out:
+        os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
+        with open(a.out, "w") as f:
+            f.write(text + "\n")
+    print(json.dumps(doc))
+
+
+if __name__ == "__main__":
+    main()

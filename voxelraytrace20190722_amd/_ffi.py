@@ -105,6 +105,7 @@ VRT_OBJ_PARSE_ONLY = 1
 VRT_BUILD_DEVICE = 1
 VRT_BUILD_DEVICE_PROBES = 4
 VRT_MARCH_EVEN_INVISIBLE = 1
+VRT_TEST_UPDATE_TOO_LARGE = 0x80000
 VRT_MULTI_LIGHT_REPLICATED = 0
 VRT_MULTI_LIGHT_SHARDED = 1
 
@@ -195,6 +196,11 @@ SIGNATURES = {
                                             C.c_int32, i32p]),
     "vrt_device_selftest_chain": (C.c_int, [C.c_int, f32p, C.c_int64, u32p]),
     "vrt_scene_chain_spacing": (C.c_int, [_P, f32p]),
+    "vrt_scene_update": (C.c_int, [_P, f32p, f32p]),
+    "vrt_scene_update_device": (C.c_int, [_P, _P, _P, _P]),
+    "vrt_scene_update_stats": (C.c_int, [_P, f64p]),
+    "vrt_scene_update_scratch": (C.c_int, [_P, C.c_int, i64p]),
+    "vrt_scene_device_array": (C.c_int, [_P, C.c_int, _P, C.c_int64, i64p]),
     "vrt_write_hdr_mem": (C.c_int64, [C.c_int, C.c_int, C.c_int, f32p, u8p, C.c_int64]),
     "vrt_rgbe_device": (C.c_int, [_P, C.c_int, C.c_int, C.c_int, _P, _P]),
     "vrt_write_hdr_rgbe": (C.c_int, [C.c_char_p, C.c_int, C.c_int, u8p]),

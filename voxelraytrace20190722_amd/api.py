@@ -351,6 +351,55 @@ class VoxelOctree:
               "vrt_scene_nodes")
         return box, a, b
 
+    def update(self, pos, nrm=None):
+        """Rebuild the scene in place from new vertex positions (ntri*9 floats)
+        and, unless nrm is None, new vertex normals (vrt_scene_update).
+        Afterwards the tree equals one freshly built from these arrays; a
+        refused update raises and leaves the previous geometry in place."""
+        pos = np.ascontiguousarray(pos, np.float32).reshape(-1)
+        n9 = 9 * self.scene.ntri
+        if pos.size != n9:
+            raise ValueError(f"pos has {pos.size} floats, the scene needs {n9}")
+        if nrm is not None:
+            nrm = np.ascontiguousarray(nrm, np.float32).reshape(-1)
+            if nrm.size != n9:
+                raise ValueError(f"nrm has {nrm.size} floats, the scene needs {n9}")
+        check(lib().vrt_scene_update(self.h, ptr(pos, _ffi.f32p), ptr(nrm, _ffi.f32p)), "vrt_scene_update")
+        check(lib().vrt_scene_info(self.h, C.byref(self.info)), "vrt_scene_info")
+
+    def update_device(self, d_pos_ptr, d_nrm_ptr=None, stream_ptr=None):
+        """update() from device arrays on the scene's device, read in the order
+        of stream_ptr (vrt_scene_update_device); ready on return."""
+        check(lib().vrt_scene_update_device(self.h, C.c_void_p(d_pos_ptr),
+                                            C.c_void_p(d_nrm_ptr) if d_nrm_ptr else None,
+                                            C.c_void_p(stream_ptr) if stream_ptr else None),
+              "vrt_scene_update_device")
+        check(lib().vrt_scene_info(self.h, C.byref(self.info)), "vrt_scene_info")
+
+    def update_stats(self):
+        """The last update's wall-clock split in ms (vrt_scene_update_stats)."""
+        ms = np.zeros(4, np.float64)
+        check(lib().vrt_scene_update_stats(self.h, ptr(ms, _ffi.f64p)), "vrt_scene_update_stats")
+        return dict(total=ms[0], gpu=ms[1], copy_back=ms[2], host=ms[3])
+
+    def update_scratch(self, release=False):
+        """Bytes of device memory the scene keeps for its next update, counted
+        by neither info.device_bytes nor scratch_bytes(); release=True frees
+        them (vrt_scene_update_scratch)."""
+        nb = C.c_int64()
+        check(lib().vrt_scene_update_scratch(self.h, int(bool(release)), C.byref(nb)), "vrt_scene_update_scratch")
+        return nb.value
+
+    def device_array(self, kind):
+        """One derived device array as bytes (vrt_scene_device_array): 0 leaf
+        records, 1 per-record boxes, 2 march records, 3 TriPos, 4 TriAttr."""
+        nb = C.c_int64()
+        check(lib().vrt_scene_device_array(self.h, int(kind), None, 0, C.byref(nb)), "vrt_scene_device_array")
+        out = np.zeros(nb.value, np.uint8)
+        check(lib().vrt_scene_device_array(self.h, int(kind), out.ctypes.data_as(C.c_void_p), nb.value,
+                                           C.byref(nb)), "vrt_scene_device_array")
+        return out
+
     def leaves(self):
         """(voxel ids, counts, concatenated triangle lists) of the non-empty leaves."""
         nl, nr = self.info.nonempty_leaves, self.info.tri_refs
@@ -1359,6 +1408,7 @@ TEST_SEC_DEFER = 128  # include/vrt.h VRT_TEST_SEC_DEFER
 TEST_SMALL_BATCH_CHUNK = 0x10000  # include/vrt.h VRT_TEST_SMALL_BATCH_CHUNK
 TEST_SMALL_PROBE_CHUNK = 0x20000  # include/vrt.h VRT_TEST_SMALL_PROBE_CHUNK
 TEST_SMALL_BEAM_ENTRY = 0x40000  # include/vrt.h VRT_TEST_SMALL_BEAM_ENTRY
+TEST_UPDATE_TOO_LARGE = 0x80000  # include/vrt.h VRT_TEST_UPDATE_TOO_LARGE
 
 
 def set_test_flags(flags):

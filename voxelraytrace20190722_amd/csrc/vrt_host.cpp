@@ -431,9 +431,27 @@ struct vrt_scene {
         uint32_t spill_want = 0;           // queue-0 chunks the next launch sizes for (0: first estimate)
         int spill_next = 0;
         int spill_last = -1;  // the set the last config-5 launch compacted with (vrt_secondary_spill_counts)
-        // device
+        // device: d_mem holds what no update touches or resizes (TriPos,
+        // TriAttr, materials, textures, the work queues); the arrays whose size
+        // follows the geometry have an owner each, with its capacity, so that
+        // vrt_scene_update reallocates only the ones that must grow
         DevMem d_mem;
+        DevMem g_nodes, g_vox, g_refs, g_xnodes;  // g_refs: [pad | per-record boxes | records]
+        bool rboxes = false;  // the per-record boxes are there (has_ref_boxes at the last build)
         DevScene dev{};
+        // vrt_scene_update: the build's scratch (kept between updates, not part
+        // of vrt_scene_scratch_bytes), the caller's stream joined in, the
+        // events of the GPU part and the last update's {total, GPU, copy back,
+        // host} ms; owned: a rank scene of a vrt_multi handle (no update)
+        BuildScratch bscratch;
+        // the host mirrors' other halves: an update fills these and swaps, so a
+        // steady animation neither allocates nor frees (nor zero-fills) them
+        std::vector<NodeRec> up_nodes;
+        std::vector<uint32_t> up_vox, up_ref_tri;
+        Event up_in, up_e0, up_e1;
+        double up_ms[4] = {};
+        bool updated = false;
+        bool owned = false;
         // chain order: per axis the smallest spacing of the
         // two child centres over the internal nodes, 0 = off (chain_spacing)
         float ord_wmin[3] = {};
@@ -1012,22 +1030,32 @@ static int upload(vrt_scene *s, const vrt_scene_desc *d)
         const size_t sz_texs = std::max<size_t>(1, s->texs.size()) * sizeof(TexRec);
         const size_t sz_tex = (size_t)std::max<int64_t>(16, s->tex_bytes);
         size_t off[11];
-        size_t tot = 0;
+        size_t tot = 0, fixed = 0;
         const size_t sz_xnodes = s->nodes.size() * sizeof(XNodeRec);
         const size_t sizes[10] = { sz_nodes, sz_vox, sz_refs, sz_pos, sz_attr, sz_mats, sz_texs, sz_tex,
                                    kQueueSlots * kQueueBytes, sz_xnodes };
+        // regions 0, 1, 2 and 9 follow the geometry (their own owners); the
+        // rest share d_mem.  device_bytes counts all ten as it always has.
         for (int i = 0; i < 10; ++i) {
-                off[i] = tot;
+                const bool geo = i <= 2 || i == 9;
+                off[i] = geo ? 0 : fixed;
                 tot += align_up(sizes[i]);
+                if (!geo)
+                        fixed += align_up(sizes[i]);
         }
         off[10] = tot;
-        HIPCHK(s->d_mem.alloc(tot));
+        HIPCHK(s->d_mem.alloc(fixed));
+        HIPCHK(s->g_nodes.alloc(align_up(sz_nodes)));
+        HIPCHK(s->g_vox.alloc(align_up(sz_vox)));
+        HIPCHK(s->g_refs.alloc(align_up(sz_refs)));
+        HIPCHK(s->g_xnodes.alloc(align_up(sz_xnodes)));
+        s->rboxes = rboxes;
         char *base = s->d_mem.as<char>();
         HIPCHK(hipMemset(base + off[8], 0, kQueueSlots * kQueueBytes));
-        HIPCHK(hipMemcpy(base + off[0], s->nodes.data(), sz_nodes, hipMemcpyHostToDevice));
-        HIPCHK(hipMemcpy(base + off[1], s->node_vox.data(), sz_vox, hipMemcpyHostToDevice));
+        HIPCHK(hipMemcpy(s->g_nodes, s->nodes.data(), sz_nodes, hipMemcpyHostToDevice));
+        HIPCHK(hipMemcpy(s->g_vox, s->node_vox.data(), sz_vox, hipMemcpyHostToDevice));
         if (refs_bytes)
-                HIPCHK(hipMemcpy(base + off[2] + sz_rbox, refs_host, refs_bytes, hipMemcpyHostToDevice));
+                HIPCHK(hipMemcpy(s->g_refs.as<char>() + sz_rbox, refs_host, refs_bytes, hipMemcpyHostToDevice));
         if (!s->tri_pos.empty())
                 HIPCHK(hipMemcpy(base + off[3], s->tri_pos.data(), s->tri_pos.size() * sizeof(TriPos), hipMemcpyHostToDevice));
         if (!s->tri_attr.empty())
@@ -1037,9 +1065,9 @@ static int upload(vrt_scene *s, const vrt_scene_desc *d)
                 HIPCHK(hipMemcpy(base + off[6], s->texs.data(), s->texs.size() * sizeof(TexRec), hipMemcpyHostToDevice));
         if (s->tex_bytes > 0)
                 HIPCHK(hipMemcpy(base + off[7], d->tex_data, (size_t)s->tex_bytes, hipMemcpyHostToDevice));
-        s->dev.nodes = reinterpret_cast<const NodeRec *>(base + off[0]);
-        s->dev.node_vox = reinterpret_cast<const uint32_t *>(base + off[1]);
-        s->dev.refs = base + off[2] + sz_rbox;
+        s->dev.nodes = s->g_nodes.as<NodeRec>();
+        s->dev.node_vox = s->g_vox.as<uint32_t>();
+        s->dev.refs = s->g_refs.as<char>() + sz_rbox;
         s->dev.tri_pos = reinterpret_cast<const TriPos *>(base + off[3]);
         s->dev.tri_attr = reinterpret_cast<const TriAttr *>(base + off[4]);
         s->dev.mats = reinterpret_cast<const MatRec *>(base + off[5]);
@@ -1051,14 +1079,14 @@ static int upload(vrt_scene *s, const vrt_scene_desc *d)
                 std::vector<XNodeRec> xn;
                 march_nodes(s, d, xn);
                 if (sz_xnodes)
-                        HIPCHK(hipMemcpy(base + off[9], xn.data(), sz_xnodes, hipMemcpyHostToDevice));
-                s->dev.xnodes = reinterpret_cast<const XNodeRec *>(base + off[9]);
+                        HIPCHK(hipMemcpy(s->g_xnodes, xn.data(), sz_xnodes, hipMemcpyHostToDevice));
+                s->dev.xnodes = s->g_xnodes.as<XNodeRec>();
         }
         if (rboxes && !s->ref_tri.empty()) {
                 std::vector<RefBox> rb;
                 ref_boxes(s, d, rb);
                 const size_t nb = rb.size() * sizeof(RefBox);
-                HIPCHK(hipMemcpy(base + off[2] + sz_rbox - nb, rb.data(), nb, hipMemcpyHostToDevice));
+                HIPCHK(hipMemcpy(s->g_refs.as<char>() + sz_rbox - nb, rb.data(), nb, hipMemcpyHostToDevice));
         }
         HIPCHK(persistent_blocks(&s->dev.persist_blocks, &s->dev.sec_blocks));
         s->dev.grid_div = 1;
@@ -1338,6 +1366,8 @@ extern "C" void vrt_scene_destroy(vrt_scene *s)
         }
         delete s;
 }
+
+void vrt::scene_mark_owned(vrt_scene *s) { s->owned = true; }
 
 extern "C" int vrt_scene_info(const vrt_scene *s, vrt_scene_info_t *info)
 {
@@ -4283,5 +4313,430 @@ extern "C" int vrt_device_selftest_order(int device, const float *dist, const ui
                 HIPCHK(hipMemcpy(orders, dout, (size_t)n * 6 * sizeof(uint32_t), hipMemcpyDeviceToHost));
         if (m > 0)
                 HIPCHK(hipMemcpy(argmin, darg, (size_t)m * sizeof(int32_t), hipMemcpyDeviceToHost));
+        return VRT_OK;
+}
+
+// ---------------------------------------------------------------------------
+// scene update (vrt_scene_update, vrt_scene_update_device): new vertex
+// positions (and normals) on the live handle.  A device scene rebuilds on the
+// GPU -- root box, frontier build, then the finish kernels of vrt_build.hip
+// (leaf records, per-record boxes, march records, chain spacing, TriPos /
+// TriAttr) -- and copies back only what host code reads (nodes, node_vox,
+// ref_tri).  Everything that can refuse happens before the first write to an
+// array the scene is using, so a refused update leaves the scene as it was.
+// ---------------------------------------------------------------------------
+static int update_args_ok(vrt_scene *s, const float *pos, const char *what)
+{
+        if (!s || !pos)
+                return fail(VRT_E_INVALID, "%s: null argument", what);
+        if (int rc = no_probe_scene(s, what))
+                return rc;
+        if (s->owned)
+                return fail(VRT_E_INVALID, "%s: the scene is a rank of a vrt_multi handle, whose ranks must stay replicas",
+                            what);
+        if ((uint32_t)s->ntri > 0x55555555u)
+                return fail(VRT_E_INVALID, "%s: %d triangles, 3 x that must stay below 2^32", what, s->ntri);
+        return VRT_OK;
+}
+
+// The host-only scene: the host build and finish on the new arrays, made
+// beside the scene and swapped in.
+static int update_host(vrt_scene *s, const float *pos, const float *nrm)
+{
+        const double t0 = now_ms();
+        std::unique_ptr<vrt_scene> t(new (std::nothrow) vrt_scene);
+        if (!t)
+                return fail(VRT_E_NOMEM, "scene alloc");
+        t->device = -1;
+        t->max_depth = s->max_depth;
+        t->ntri = s->ntri;
+        vrt_scene_desc d{};
+        d.ntri = s->ntri;
+        d.pos = pos;
+        d.nrm = nrm;
+        try {
+                if (int rc = build_tree(t.get(), &d, false))
+                        return rc;
+                const int n = s->ntri;
+                t->tri_pos.resize((size_t)n);
+                t->tri_attr = s->tri_attr;  // uvs, materials and, without nrm, the normals stay
+                for (int i = 0; i < n; ++i) {
+                        TriPos &tp = t->tri_pos[i];
+                        std::memcpy(tp.p, pos + 9 * (size_t)i, sizeof tp.p);
+                        tp.pad[0] = tp.pad[1] = tp.pad[2] = 0.f;
+                        if (!nrm)
+                                continue;
+                        TriAttr &ta = t->tri_attr[i];
+                        for (int v = 0; v < 3; ++v) {
+                                const float *nn = nrm + 9 * (size_t)i + 3 * v;
+                                const f3 q = normalize(mk3(nn[0], nn[1], nn[2]));
+                                ta.n[3 * v + 0] = q.x;
+                                ta.n[3 * v + 1] = q.y;
+                                ta.n[3 * v + 2] = q.z;
+                        }
+                }
+        } catch (const std::bad_alloc &) {
+                return fail(VRT_E_NOMEM, "scene update: out of host memory");
+        }
+        s->nodes.swap(t->nodes);
+        s->node_vox.swap(t->node_vox);
+        s->refs48.swap(t->refs48);
+        s->refs64.swap(t->refs64);
+        s->wide_leaves = t->wide_leaves;
+        s->ref_tri.swap(t->ref_tri);
+        s->tri_pos.swap(t->tri_pos);
+        s->tri_attr.swap(t->tri_attr);
+        s->level_begin.swap(t->level_begin);
+        s->info.nodes = t->info.nodes;
+        s->info.internal = t->info.internal;
+        s->info.leaves = t->info.leaves;
+        s->info.nonempty_leaves = t->info.nonempty_leaves;
+        s->info.tri_refs = t->info.tri_refs;
+        for (int k = 0; k < 3; ++k) {
+                s->info.root_min[k] = t->info.root_min[k];
+                s->info.root_max[k] = t->info.root_max[k];
+        }
+        s->info.build_ms = now_ms() - t0;
+        s->info.build_device_ms = 0;
+        s->up_ms[0] = s->up_ms[3] = s->info.build_ms;
+        s->up_ms[1] = s->up_ms[2] = 0;
+        s->updated = true;
+        return VRT_OK;
+}
+
+// async copy to the host in the stream's order
+static hipError_t fetch(void *dst, const void *src, size_t bytes, hipStream_t st)
+{
+        return bytes ? hipMemcpyAsync(dst, src, bytes, hipMemcpyDeviceToHost, st) : hipSuccess;
+}
+
+// pos / nrm: host arrays (on_device false: copied to the scratch first) or
+// device arrays read in the order of the caller's stream cst
+static int update_device(vrt_scene *s, const float *pos, const float *nrm, bool on_device, hipStream_t cst)
+{
+        const double t0 = now_ms();
+        // Wait for all work the scene has in flight.  Not every launch leaves
+        // an event to wait for: a grid-kind render (every 64-B-record scene)
+        // and the device ray-march batches run on the caller's stream and
+        // record none.  So the whole device is waited for, which covers every
+        // stream a kernel that reads the scene's arrays can be on.
+        HIPCHK(hipSetDevice(s->device));
+        HIPCHK(hipDeviceSynchronize());
+        hipStream_t st = s->stream;
+        if (!s->up_e0) {
+                HIPCHK(s->up_in.create(hipEventDisableTiming));
+                HIPCHK(s->up_e0.create());
+                HIPCHK(s->up_e1.create());
+        }
+        BuildScratch &sc = s->bscratch;
+        const int n = s->ntri;
+        const float *d_pos = pos, *d_nrm = nrm;
+        if (on_device) {
+                HIPCHK(hipEventRecord(s->up_in, cst));
+                HIPCHK(hipStreamWaitEvent(st, s->up_in, 0));
+        } else {
+                HIPCHK(sc.pos.need((size_t)n * 36));
+                HIPCHK(hipMemcpyAsync(sc.pos, pos, (size_t)n * 36, hipMemcpyHostToDevice, st));
+                d_pos = sc.pos.as<float>();
+                if (nrm) {
+                        HIPCHK(sc.nrm.need((size_t)n * 36));
+                        HIPCHK(hipMemcpyAsync(sc.nrm, nrm, (size_t)n * 36, hipMemcpyHostToDevice, st));
+                        d_nrm = sc.nrm.as<float>();
+                }
+        }
+        HIPCHK(hipEventRecord(s->up_e0, st));
+        // root box: 6 keys, then the 6 floats the host needs for info
+        float root[6];
+        HIPCHK(sc.root.need(128));
+        HIPCHK(launch_root_box(d_pos, n, sc.root.as<uint64_t>(), sc.root.as<float>() + 12, st));
+        HIPCHK(fetch(root, sc.root.as<float>() + 12, sizeof root, st));
+        HIPCHK(hipStreamSynchronize(st));
+        DeviceTree tree;
+        try {
+                std::string err;
+                const bool fail_limit = (test_flags() & VRT_TEST_UPDATE_TOO_LARGE) != 0;
+                if (build_frontier_device(sc, d_pos, n, root, root + 3, s->max_depth, nullptr, 0, st, fail_limit, &tree,
+                                          &err) != hipSuccess) {
+                        (void)hipGetLastError();
+                        (void)hipStreamSynchronize(st);
+                        if (tree.too_large)
+                                return fail(VRT_E_INVALID, "%s", err.c_str());
+                        return fail(VRT_E_DEVICE, "device octree build: %s", err.c_str());
+                }
+        } catch (const std::bad_alloc &) {
+                // the build's host vectors; it has written only its own scratch
+                (void)hipStreamSynchronize(st);
+                return fail(VRT_E_NOMEM, "scene update: out of host memory");
+        }
+        const int64_t nn = tree.nnodes, nr = tree.nrefs;
+        unsigned int counts[2] = {};
+        HIPCHK(sc.counts.need(16));
+        HIPCHK(launch_leaf_counts(tree.nodes, nn, sc.counts.as<unsigned int>(), st));
+        HIPCHK(fetch(counts, sc.counts, sizeof counts, st));
+        HIPCHK(hipStreamSynchronize(st));
+        // the choices upload() makes, on the new geometry
+        const bool wide = (size_t)nr >= 8 * (size_t)std::max<int64_t>(1, (int64_t)counts[1]);
+        float ext = 0.f;
+        bool fast = true;
+        for (int k = 0; k < 3; ++k) {
+                ext = std::max(ext, root[3 + k] - root[k]);
+                fast = fast && std::fabs(root[k]) < 0x1p60f && std::fabs(root[3 + k]) < 0x1p60f;
+        }
+        const bool lb_on = ext > 0.f && std::isfinite(ext);
+        const bool rboxes = VRT_LEAF_CULL && !wide && lb_on;
+        const size_t refs_bytes = (size_t)nr * (wide ? sizeof(RefRec64) : sizeof(RefRec48));
+        const size_t sz_rbox = rboxes ? align_up(((size_t)nr + kRefBoxPad) * sizeof(RefBox)) : 0;
+        const size_t want[4] = { align_up((size_t)nn * sizeof(NodeRec)), align_up((size_t)nn * sizeof(uint32_t)),
+                                 align_up(sz_rbox + std::max<size_t>(64, refs_bytes)),
+                                 align_up((size_t)nn * sizeof(XNodeRec)) };
+        // larger arrays are made beside the ones in use and swapped in only
+        // when all of them exist
+        DevMem *const own[4] = { &s->g_nodes, &s->g_vox, &s->g_refs, &s->g_xnodes };
+        DevMem grown[4];
+        std::vector<NodeRec> &h_nodes = s->up_nodes;
+        std::vector<uint32_t> &h_vox = s->up_vox, &h_reftri = s->up_ref_tri;
+        for (int i = 0; i < 4; ++i)
+                if (own[i]->size() < want[i] && grown[i].alloc(want[i]) != hipSuccess) {
+                        (void)hipGetLastError();
+                        return fail(VRT_E_DEVICE, "scene update: no device memory for %zu bytes", want[i]);
+                }
+        if (sc.ref_tri.need((size_t)nr * 4) != hipSuccess || sc.lohi.need(lb_on ? (size_t)nn * 48 : 0) != hipSuccess ||
+            sc.chain.need(32) != hipSuccess) {
+                (void)hipGetLastError();
+                return fail(VRT_E_DEVICE, "scene update: no device memory for the finish scratch");
+        }
+        try {
+                h_nodes.resize((size_t)nn);
+                h_vox.resize((size_t)nn);
+                h_reftri.resize((size_t)nr);
+        } catch (const std::bad_alloc &) {
+                return fail(VRT_E_NOMEM, "scene update: out of host memory");
+        }
+        // ---- nothing below refuses: the scene's arrays are written from here
+        // on.  The device pointers follow their owners at once, so that no
+        // later error return leaves one on released memory (after a
+        // VRT_E_DEVICE from here on the scene's contents are undefined).
+        const size_t old_nodes = s->nodes.size();
+        for (int i = 0; i < 4; ++i)
+                if (grown[i])
+                        *own[i] = std::move(grown[i]);
+        s->wide_leaves = wide;
+        s->rboxes = rboxes;
+        s->dev.nodes = s->g_nodes.as<NodeRec>();
+        s->dev.node_vox = s->g_vox.as<uint32_t>();
+        s->dev.refs = s->g_refs.as<char>() + sz_rbox;
+        s->dev.xnodes = s->g_xnodes.as<XNodeRec>();
+        s->dev.wide_leaves = wide ? 1 : 0;
+        HIPCHK(hipMemcpyAsync(s->g_nodes, tree.nodes, (size_t)nn * sizeof(NodeRec), hipMemcpyDeviceToDevice, st));
+        HIPCHK(hipMemcpyAsync(s->g_vox, tree.node_vox, (size_t)nn * sizeof(uint32_t), hipMemcpyDeviceToDevice, st));
+        FinishArgs fa{};
+        fa.tree = &tree;
+        fa.pos = d_pos;
+        fa.nrm = d_nrm;
+        fa.ntri = n;
+        fa.wide = wide ? 1 : 0;
+        fa.rboxes = rboxes ? 1 : 0;
+        fa.lb_on = lb_on ? 1 : 0;
+        fa.eps = std::ldexp((double)ext, -16);
+        fa.chain = fast ? 1 : 0;
+        fa.refs = s->g_refs.as<char>() + sz_rbox;
+        fa.ref_tri = sc.ref_tri.as<uint32_t>();
+        fa.xnodes = s->g_xnodes.as<XNodeRec>();
+        fa.lohi = sc.lohi.as<double>();
+        fa.chain_out = sc.chain.as<uint64_t>();
+        fa.tri_pos = const_cast<TriPos *>(s->dev.tri_pos);
+        fa.tri_attr = const_cast<TriAttr *>(s->dev.tri_attr);
+        HIPCHK(launch_finish(fa, st));
+        HIPCHK(hipEventRecord(s->up_e1, st));
+        HIPCHK(hipEventSynchronize(s->up_e1));
+        const double t1 = now_ms();
+        uint64_t chain[4] = { ~0ull, ~0ull, ~0ull, 1 };
+        HIPCHK(fetch(h_nodes.data(), tree.nodes, (size_t)nn * sizeof(NodeRec), st));
+        HIPCHK(fetch(h_vox.data(), tree.node_vox, (size_t)nn * sizeof(uint32_t), st));
+        HIPCHK(fetch(h_reftri.data(), fa.ref_tri, (size_t)nr * 4, st));
+        if (fast)
+                HIPCHK(fetch(chain, fa.chain_out, sizeof chain, st));
+        HIPCHK(hipStreamSynchronize(st));
+        const double t2 = now_ms();
+        // ---- host mirrors and the scene's constants
+        s->nodes.swap(h_nodes);
+        s->node_vox.swap(h_vox);
+        s->ref_tri.swap(h_reftri);
+        s->level_begin.swap(tree.level_begin);
+        // no reader after upload() on a scene that cannot be replicated
+        std::vector<RefRec48>().swap(s->refs48);
+        std::vector<RefRec64>().swap(s->refs64);
+        std::vector<TriPos>().swap(s->tri_pos);
+        std::vector<TriAttr>().swap(s->tri_attr);
+        s->info.nodes = nn;
+        s->info.internal = tree.ninternal;
+        s->info.leaves = counts[0];
+        s->info.nonempty_leaves = counts[1];
+        s->info.tri_refs = nr;
+        for (int k = 0; k < 3; ++k) {
+                s->info.root_min[k] = root[k];
+                s->info.root_max[k] = root[3 + k];
+                s->dev.lb_center[k] = 0.5f * (root[k] + root[3 + k]);
+        }
+        s->dev.lb_reach = lb_on ? 16.f * ext : -1.f;
+        s->dev.fast_ok = fast ? 1 : 0;
+        // chain_spacing's tail on the reduced minima
+        for (int k = 0; k < 3; ++k)
+                s->ord_wmin[k] = 0.f;
+        if (fast) {
+                bool ok = chain[3] == 0;
+                const bool any = tree.ninternal > 0;
+                float f[3];
+                for (int k = 0; k < 3; ++k) {
+                        const double w = chain[k] == ~0ull ? HUGE_VAL : chain_key_value(chain[k]);
+                        ok = ok && any && std::isfinite(w) && w > 0.0;
+                        f[k] = (float)w;
+                        if (ok && (double)f[k] > w)
+                                f[k] = std::nextafter(f[k], 0.f);
+                        ok = ok && f[k] > 0.f;
+                }
+                if (ok)
+                        for (int k = 0; k < 3; ++k)
+                                s->ord_wmin[k] = f[k];
+        }
+        int64_t bytes = (int64_t)(s->d_mem.size() + s->d_probe.size());
+        for (int i = 0; i < 4; ++i)
+                bytes += (int64_t)own[i]->size();
+        s->info.device_bytes = bytes;
+        // ---- derived state back to a fresh scene's; the allocations stay
+        // where their size still fits
+        for (TraceSet &t : s->ts) {
+                t.steps_key[0] = t.steps_key[1] = -1.f;
+                if (!t.lm)
+                        continue;
+                if (s->nodes.size() != old_nodes) {
+                        t.lm.reset();  // sized by the node count: made again on first use
+                        continue;
+                }
+                std::vector<float4> cells;
+                try {
+                        cells = cone_cells(s->nodes);
+                } catch (const std::bad_alloc &) {
+                        t.lm.reset();  // no host memory for the cells now: made again on first use
+                        continue;
+                }
+                HIPCHK(hipMemcpy(t.lm.as<char>() + (size_t)nn * (sizeof(LMRec) + sizeof(float4)) + 256, cells.data(),
+                                 cells.size() * sizeof(float4), hipMemcpyHostToDevice));
+        }
+        s->ts_next = 0;
+        s->lm_cur = -1;
+        for (int64_t &v : s->lm_stats)
+                v = 0;
+        s->timed = false;
+        s->entry_slot = -1;
+        s->entry_units = 0;
+        s->spill_last = -1;
+        s->spill_want = 0;
+        s->spill_next = 0;
+        float gpu_ms = 0.f;
+        HIPCHK(hipEventElapsedTime(&gpu_ms, s->up_e0, s->up_e1));
+        const double t3 = now_ms();
+        s->up_ms[0] = t3 - t0;
+        s->up_ms[1] = gpu_ms;
+        s->up_ms[2] = t2 - t1;
+        s->up_ms[3] = std::max(0.0, s->up_ms[0] - s->up_ms[1] - s->up_ms[2]);
+        s->info.build_ms = s->up_ms[0];
+        s->info.build_device_ms = gpu_ms;
+        s->info.upload_ms = 0;
+        s->updated = true;
+        return VRT_OK;
+}
+
+extern "C" int vrt_scene_update(vrt_scene *s, const float *pos, const float *nrm)
+{
+        if (int rc = update_args_ok(s, pos, "vrt_scene_update"))
+                return rc;
+        std::lock_guard<std::mutex> lk(s->mu);
+        if (!s->d_mem)
+                return update_host(s, pos, nrm);
+        return update_device(s, pos, nrm, false, nullptr);
+}
+
+extern "C" int vrt_scene_update_device(vrt_scene *s, const float *d_pos, const float *d_nrm, void *stream)
+{
+        if (s && need_device(s))
+                return VRT_E_NODEVICE;
+        if (int rc = update_args_ok(s, d_pos, "vrt_scene_update_device"))
+                return rc;
+        std::lock_guard<std::mutex> lk(s->mu);
+        return update_device(s, d_pos, d_nrm, true, static_cast<hipStream_t>(stream));
+}
+
+extern "C" int vrt_scene_update_stats(const vrt_scene *s, double ms[4])
+{
+        if (!s || !ms)
+                return fail(VRT_E_INVALID, "null argument");
+        if (!s->updated)
+                return fail(VRT_E_INVALID, "the scene has not been updated");
+        for (int k = 0; k < 4; ++k)
+                ms[k] = s->up_ms[k];
+        return VRT_OK;
+}
+
+extern "C" int vrt_scene_update_scratch(vrt_scene *s, int release, int64_t *bytes)
+{
+        if (!s || !bytes)
+                return fail(VRT_E_INVALID, "null argument");
+        std::lock_guard<std::mutex> lk(s->mu);
+        *bytes = (int64_t)s->bscratch.bytes();
+        if (!release || !s->d_mem)
+                return VRT_OK;
+        // an update returns with its work done: nothing is using the scratch
+        HIPCHK(hipSetDevice(s->device));
+        s->bscratch = BuildScratch();
+        std::vector<NodeRec>().swap(s->up_nodes);
+        std::vector<uint32_t>().swap(s->up_vox);
+        std::vector<uint32_t>().swap(s->up_ref_tri);
+        return VRT_OK;
+}
+
+extern "C" int vrt_scene_device_array(vrt_scene *s, int kind, void *out, int64_t cap, int64_t *bytes)
+{
+        if (s && need_device(s))
+                return VRT_E_NODEVICE;
+        if (!s || !bytes)
+                return fail(VRT_E_INVALID, "null argument");
+        std::lock_guard<std::mutex> lk(s->mu);
+        const size_t nr = s->ref_tri.size();
+        const void *src = nullptr;
+        size_t n = 0;
+        switch (kind) {
+        case 0:
+                src = s->dev.refs;
+                n = nr * (s->wide_leaves ? sizeof(RefRec64) : sizeof(RefRec48));
+                break;
+        case 1:
+                n = s->rboxes ? nr * sizeof(RefBox) : 0;
+                src = static_cast<const char *>(s->dev.refs) - n;
+                break;
+        case 2:
+                src = s->dev.xnodes;
+                n = s->nodes.size() * sizeof(XNodeRec);
+                break;
+        case 3:
+                src = s->dev.tri_pos;
+                n = (size_t)s->ntri * sizeof(TriPos);
+                break;
+        case 4:
+                src = s->dev.tri_attr;
+                n = (size_t)s->ntri * sizeof(TriAttr);
+                break;
+        default:
+                return fail(VRT_E_INVALID, "vrt_scene_device_array: kind %d outside [0, 4]", kind);
+        }
+        *bytes = (int64_t)n;
+        if (!out)
+                return VRT_OK;
+        if (cap < (int64_t)n)
+                return fail(VRT_E_INVALID, "vrt_scene_device_array: %lld bytes do not fit %lld", (long long)n,
+                            (long long)cap);
+        HIPCHK(hipSetDevice(s->device));
+        if (n)
+                HIPCHK(hipMemcpy(out, src, n, hipMemcpyDeviceToHost));
         return VRT_OK;
 }

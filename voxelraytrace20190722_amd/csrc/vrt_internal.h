@@ -660,6 +660,8 @@ void frame_abort(FrameJob *j);
 bool scene_has_lightmap(vrt_scene *s);
 // the scene's own stream (light pass, filter, probe gather) is idle
 int scene_stream_sync(vrt_scene *s);
+// the scene belongs to a vrt_multi handle: vrt_scene_update refuses it
+void scene_mark_owned(vrt_scene *s);
 // memcpy of a large host range over up to 4 threads.
 void par_memcpy(void *dst, const void *src, size_t bytes);
 // the process-wide vrt_set_test_flags value
@@ -784,6 +786,93 @@ struct Staging {
                 return hipSuccess;
         }
 };
+
+// ---- scene update (vrt_scene_update[_device], vrt_build.hip) ---------------
+// Device memory with a capacity: need() keeps what it holds when that
+// suffices, so a steady animation allocates nothing per update.
+struct GrowMem : DevMem {
+        hipError_t need(size_t bytes)
+        {
+                if (get() && bytes <= size())
+                        return hipSuccess;
+                return alloc(bytes ? bytes : 16);
+        }
+};
+// The device build's frontier, sort and flatten arrays and the finish
+// kernels' scratch.  build_tree_device makes one per call; a scene that is
+// updated keeps one (vrt_scene::bscratch), released with the scene.
+struct BuildScratch {
+        // build_frontier_device: counters, the two frontiers, the level's codes
+        // (sorted, unique), hipcub's temporary, the internal codes, the leaf
+        // keys (sorted), and the flattened tree
+        GrowMem cnt, pa, pb, codes, codes_s, uniq, nuniq, temp, iall, keys, keys_s, inode, nodes, vox, has;
+        // ... and the probe frontier with its outputs
+        GrowMem qa, qb, pkeys, pkeys_s, pref, pnode, phas;
+        // the callers': positions and normals (build_tree_device: the probes in
+        // nrm), root-box keys (6 x 8 B) then the box (6 floats), and the
+        // finish kernels' ref_tri, per-node lo/hi, chain minima, leaf counts
+        GrowMem pos, nrm, root, ref_tri, lohi, chain, counts;
+
+        size_t bytes() const
+        {
+                size_t b = 0;
+                for (const GrowMem *g : { &cnt, &pa, &pb, &codes, &codes_s, &uniq, &nuniq, &temp, &iall, &keys,
+                                          &keys_s, &inode, &nodes, &vox, &has, &qa, &qb, &pkeys, &pkeys_s, &pref,
+                                          &pnode, &phas, &pos, &nrm, &root, &ref_tri, &lohi, &chain, &counts })
+                        b += g->size();
+                return b;
+        }
+};
+// The frontier build's result, left on the device in the scratch.
+struct DeviceTree {
+        const NodeRec *nodes = nullptr;
+        const uint32_t *node_vox = nullptr;
+        const uint64_t *refs = nullptr;    // sorted (leaf code << 32 | tri)
+        int64_t nnodes = 0, nrefs = 0, ninternal = 0;
+        std::vector<int64_t> level_begin;
+        // probe scenes (build_tree_device only)
+        const uint2 *pnode = nullptr;
+        const uint32_t *pref = nullptr;
+        int64_t nprefs = 0;
+        const unsigned int *probe_leaves = nullptr;
+        bool too_large = false;
+};
+// The level-synchronous build from device arrays on stream st (d_probes:
+// float4 {o, r} per probe or nullptr).  Host reads of the counters wait for
+// st.  fail_limit: report the size limit after the frontier has been expanded
+// (VRT_TEST_UPDATE_TOO_LARGE).
+hipError_t build_frontier_device(BuildScratch &sc, const float *d_pos, int ntri, const float root_mn[3],
+                                 const float root_mx[3], int max_depth, const float4 *d_probes, int nprobe,
+                                 hipStream_t st, bool fail_limit, DeviceTree *out, std::string *err);
+// Root box of ntri triangles as build_tree merges it: NaN ignored, the first
+// of equal extremes in (triangle, vertex) order wins.  keys: 6 uint64 of
+// device scratch; box: 6 floats on the device (min xyz, max xyz).
+hipError_t launch_root_box(const float *d_pos, int ntri, uint64_t *keys, float *box, hipStream_t st);
+// counts[0] = leaves, counts[1] = non-empty leaves of nodes[0, n) (zeroed here)
+hipError_t launch_leaf_counts(const NodeRec *nodes, int64_t n, unsigned int *counts, hipStream_t st);
+// The finish of a build on the device (finish_tree, ref_boxes, march_nodes,
+// chain_spacing of vrt_host.cpp restated).  All pointers are device memory.
+struct FinishArgs {
+        const DeviceTree *tree;
+        const float *pos;       // ntri * 9
+        const float *nrm;       // ntri * 9 or nullptr (the stored normals stay)
+        int ntri;
+        int wide;               // RefRec64 records
+        int rboxes;             // write the per-record boxes below refs
+        int lb_on;              // extent finite and positive: triangle union boxes in xnodes
+        double eps;             // ldexp(extent, -16)
+        int chain;              // fast_ok: reduce the chain spacing
+        void *refs;             // records (boxes below)
+        uint32_t *ref_tri;
+        XNodeRec *xnodes;
+        double *lohi;           // 6 doubles per node (lb_on)
+        uint64_t *chain_out;    // 3 ordered keys of the minima, then a "bad" word (chain)
+        TriPos *tri_pos;
+        TriAttr *tri_attr;
+};
+hipError_t launch_finish(const FinishArgs &a, hipStream_t st);
+// the ordered key of launch_finish's chain minima back to the double
+double chain_key_value(uint64_t key);
 
 // Kernel launchers (vrt_kernels.hip)
 // Which primary-render kernel launch_render runs: the one-wave grid

@@ -597,6 +597,7 @@ static int create_multi(const vrt_scene_desc *desc, const vrt_probe *probes, int
                 if (rcs[i])
                         return set_error(rcs[i], "replica on device %d: %s", devs[i], errs[i].c_str());
         for (int i = 0; i < n; ++i) {
+                scene_mark_owned(m->sc[i]);  // the ranks stay replicas: no vrt_scene_update
                 HIPCHK(hipSetDevice(devs[i]));
                 HIPCHK(m->st[i].create());
                 HIPCHK(m->ev[i].create(hipEventDisableTiming));
