@@ -329,7 +329,8 @@ int vrt_device_selftest(int device, const double *mt_in, double *mt_out,
  * frames of at least 65,536 units (4x4-pixel quadrants) do, because the
  * pre-pass costs a small frame more than it saves. */
 #define VRT_TEST_SMALL_BEAM_ENTRY 0x40000
-/* VRT_TEST_UPDATE_TOO_LARGE makes vrt_scene_update[_device]'s device build
+/* VRT_TEST_UPDATE_TOO_LARGE makes the device build of vrt_scene_update[_device]
+ * and vrt_scene_update_probes[_device]
  * report its size limit ("octree too large") after the frontier has been
  * expanded: the refusal a huge scene would meet, which must leave the scene
  * on its previous geometry.  A host-side error return. */
@@ -417,7 +418,8 @@ int vrt_scene_chain_spacing(const vrt_scene *s, float out[3]);
  * launched: it synchronises the scene's device.  (Calls on the scene from
  * other threads during an update are the caller's to exclude.)  A device scene
  * rebuilds on the GPU; a host-only scene (device < 0) runs the host build.  A
- * refused update (VRT_E_INVALID: null arguments, a scene with light probes, a
+ * refused update (VRT_E_INVALID: null arguments, a scene with light probes --
+ * which vrt_scene_update_probes below moves --, a
  * rank scene of a vrt_multi handle, a size limit of the build; no memory)
  * leaves the scene on its previous geometry, fully usable.  Only VRT_E_DEVICE
  * (a failed launch or copy) can leave it half rebuilt: destroy it then. */
@@ -426,7 +428,8 @@ int vrt_scene_update(vrt_scene *s, const float *pos, const float *nrm);
  * `stream` order (NULL = the null stream).  On return the scene is ready and
  * the caller may overwrite the arrays. */
 int vrt_scene_update_device(vrt_scene *s, const float *d_pos, const float *d_nrm, void *stream);
-/* Wall-clock split of the last update: {total, GPU (events), copy back, host}. */
+/* Wall-clock split of the last update of either kind: {total, GPU (events),
+ * copy back, host}. */
 int vrt_scene_update_stats(const vrt_scene *s, double ms[4]);
 /* The device memory an updated scene keeps for its next update (the build's
  * frontier, sort and flatten arrays and the finish kernels' scratch), which
@@ -436,7 +439,9 @@ int vrt_scene_update_stats(const vrt_scene *s, double ms[4]);
 int vrt_scene_update_scratch(vrt_scene *s, int release, int64_t *bytes);
 /* Test access: copy one derived device array of the scene to the host.
  * kind: 0 leaf records (48 or 64 B each), 1 per-record boxes (device order, pad excluded),
- * 2 xnodes, 3 TriPos, 4 TriAttr.  out == NULL returns only *bytes. */
+ * 2 xnodes, 3 TriPos, 4 TriAttr; on a probe scene only (VRT_E_INVALID on any
+ * other): 5 pnode (8 B per node), 6 pref (4 B per probe reference), 7 the
+ * probes (16 B each).  out == NULL returns only *bytes. */
 int vrt_scene_device_array(vrt_scene *s, int kind, void *out, int64_t cap, int64_t *bytes);
 
 /* ---- multi-device frame (render_mt, VRT/camera.h:42-68,
@@ -670,6 +675,38 @@ int vrt_scene_probe_sgs(const vrt_scene *s, vrt_sg *sgs);
  * reference's 100 points (vrt_probe_gather on the scene's own probes) into
  * the stored SGs.  Needs a light map. */
 int vrt_scene_probes_gather(vrt_scene *s, float min_voxel, const float light_color[3]);
+
+/* The update of a probe scene (vrt_scene_create_probes with nprobe >= 1): new
+ * positions (required, ntri*9), new normals (NULL: the stored normals stay)
+ * and new probe centres and radii (nprobe records; NULL: the probes stay where
+ * they are).  ntri, nprobe, uv, materials, textures, max_depth, device
+ * unchanged.  Afterwards the scene equals, bit for bit, one created with
+ * vrt_scene_create_probes(VRT_BUILD_DEVICE | VRT_BUILD_DEVICE_PROBES) from
+ * these arrays -- every query, march, render and device array, the host copy
+ * of the probes included -- with the two differences vrt_scene_update
+ * documents: derived state is a fresh scene's (no light map:
+ * vrt_scene_probes_gather and the trace calls refuse until one is built), and
+ * frames in flight, streams, queues, scratch and test flags stay.  The stored
+ * SGs (14 per probe) are caller data of unchanged size and stay:
+ * vrt_scene_probe_sgs returns the same bytes before and after, whichever copy
+ * was the newer one.  Waiting, thread rules and the host-only scene are
+ * vrt_scene_update's.  A probe is checked as at creation (centre finite,
+ * radius finite and >= 0): a bad one is VRT_E_INVALID with its index.  On a
+ * scene without probes: VRT_E_INVALID (use vrt_scene_update).  A refused
+ * update (VRT_E_INVALID: null s or pos, a scene without probes, a rank scene
+ * of a vrt_multi handle, a bad probe, a size limit of the build -- 3 * ntri +
+ * nprobe above 2^32 among them; no memory) leaves the scene on its previous
+ * geometry and probes, fully usable; only VRT_E_DEVICE can leave it half
+ * rebuilt. */
+int vrt_scene_update_probes(vrt_scene *s, const float *pos, const float *nrm, const vrt_probe *probes);
+/* The same from device memory on the scene's device; all three arrays are
+ * read in `stream` order and are the caller's again on return.  The probes
+ * are checked by a kernel, whose flag comes back with the root box: no
+ * synchronisation is added for it.  d_probes needs only a float's alignment
+ * (a slice of a larger array will do); one that is not 16-byte aligned costs a
+ * device-to-device copy of the probes.  A host-only scene: VRT_E_NODEVICE. */
+int vrt_scene_update_probes_device(vrt_scene *s, const float *d_pos, const float *d_nrm,
+                                   const vrt_probe *d_probes, void *stream);
 
 /* LightProbe::is_overlap(AABB3D{box}) on the host (box = min xyz, max xyz):
  * 1 / 0, negative on a NULL argument.  The float32 squared-distance test,

@@ -18,9 +18,14 @@ starts from; "moved" is the best of the rounds on the moved placement for all
 three, like against like.  One device build runs first at every depth and is
 not counted (the first one in a process loads the code object).
 
-  --lib PATH     load this libvrt.so instead of the package's
-  --create-only  (a) only: for a library from before vrt_scene_update, to show
+  --lib PATH     load this libvrt.so instead of the package's (calls it lacks
+                 are left out of the bindings)
+  --create-only  (a) only: for a library from before the update call, to show
                  that the create path did not move
+  --probes G     a probe scene: G x G x G light probes on a grid in the
+                 triangles' box, moved with the placement, radius 0.1 x the
+                 grid spacing.  (a) is vrt_scene_create_probes(VRT_BUILD_DEVICE |
+                 VRT_BUILD_DEVICE_PROBES), (b) vrt_scene_update_probes[_device]
 Prints and, with --out, writes one JSON document."""
 import argparse
 import json
@@ -41,16 +46,18 @@ def main():
     ap.add_argument("--reps", type=int, default=3)
     ap.add_argument("--lib")
     ap.add_argument("--create-only", action="store_true")
+    ap.add_argument("--probes", type=int, default=0)
     ap.add_argument("--out")
     a = ap.parse_args()
 
     import torch  # first: one HIP runtime per process
     from voxelraytrace20190722_amd import _ffi
     if a.lib:
+        import ctypes
         _ffi.LIB_PATH = os.path.abspath(a.lib)
-        if a.create_only:  # an older library lacks the new symbols
-            for name in [n for n in _ffi.SIGNATURES if n.startswith(("vrt_scene_update", "vrt_scene_device_array"))]:
-                del _ffi.SIGNATURES[name]
+        older = ctypes.CDLL(_ffi.LIB_PATH)  # an older library lacks the newer symbols
+        for name in [n for n in _ffi.SIGNATURES if not hasattr(older, n)]:
+            del _ffi.SIGNATURES[name]
     import voxelraytrace20190722_amd as vrt
 
     sd = vrt.SceneData.proxy(a.detail, 1)
@@ -63,19 +70,41 @@ def main():
     scenes = [vrt.SceneData(p, sd.nrm, sd.uv, sd.mat, sd.mat_tex, sd.mat_kd, sd.tex_dims, sd.tex_off, sd.tex_data)
               for p in places]
     d_places = [torch.from_numpy(p).cuda() for p in places]
+    probes = d_probes = None
+    if a.probes:
+        g = a.probes
+        mn, mx = p3.min(axis=0), p3.max(axis=0)
+        cell = (mx - mn) / np.float32(g)
+        ijk = np.stack(np.meshgrid(*[np.arange(g)] * 3, indexing="ij"), axis=-1).reshape(-1, 3).astype(np.float32)
+        o = (mn + (ijk + np.float32(0.5)) * cell).astype(np.float32)
+        r = np.full((len(o), 1), np.float32(0.1) * cell.min(), np.float32)
+        probes = [np.ascontiguousarray(np.concatenate([o, r], axis=1)),
+                  np.ascontiguousarray(np.concatenate(
+                      [(o @ R.T + np.array((0.5, 0.25, -0.5), np.float32)).astype(np.float32), r], axis=1))]
+        d_probes = [torch.from_numpy(p).cuda() for p in probes]
     torch.cuda.synchronize()
     doc = {"scene": "sponza-proxy", "detail": a.detail, "triangles": int(sd.ntri), "reps": a.reps,
+           "probes": 0 if probes is None else int(len(probes[0])),
            "library": vrt.build_id(), "device": torch.cuda.get_device_name(0), "depths": {}}
+
+    def make(k, depth):
+        return vrt.VoxelOctree(scenes[k], depth, build_on_device=True, probes=None if probes is None else probes[k])
+
     def timed_update(live, kind, k):
         t0 = time.perf_counter()
-        if kind == "host":
+        if probes is not None:
+            if kind == "host":
+                live.update_probes(places[k], None, probes[k])
+            else:
+                live.update_probes_device(d_places[k].data_ptr(), None, d_probes[k].data_ptr())
+        elif kind == "host":
             live.update(places[k])
         else:
             live.update_device(d_places[k].data_ptr())
         return dict(live.update_stats(), wall=(time.perf_counter() - t0) * 1e3, placement=k)
 
     for depth in [int(x) for x in a.depths.split(",")]:
-        tree = vrt.VoxelOctree(scenes[0], depth, build_on_device=True)  # warm-up, not counted
+        tree = make(0, depth)  # warm-up, not counted
         create, upd, upd_dev = [], [], []
         live = first = None
         if not a.create_only:
@@ -83,7 +112,7 @@ def main():
             # Its first update allocates the build's scratch and the host
             # mirrors' second halves and is reported apart; one update of each
             # kind after it is not counted, the rest are the steady state.
-            live = vrt.VoxelOctree(scenes[0], depth, build_on_device=True)
+            live = make(0, depth)
             first = timed_update(live, "host", 1)
             timed_update(live, "device", 0)
             timed_update(live, "host", 1)
@@ -93,7 +122,7 @@ def main():
             k ^= 1  # this round's positions: 1, 0, 1, ... for (a) and (b) alike
             t0 = time.perf_counter()
             tree.close()
-            tree = vrt.VoxelOctree(scenes[k], depth, build_on_device=True)
+            tree = make(k, depth)
             create.append({"total": (time.perf_counter() - t0) * 1e3, "build_ms": tree.info.build_ms,
                            "upload_ms": tree.info.upload_ms, "gpu": tree.info.build_device_ms, "placement": k})
             if a.create_only:
@@ -105,7 +134,9 @@ def main():
             timed_update(live, "host", k ^ 1)
             upd_dev.append(timed_update(live, "device", k))
             assert int(live.info.nodes) == int(tree.info.nodes) and int(live.info.tri_refs) == int(tree.info.tri_refs)
+            assert live.probe_info() == tree.probe_info()
         row = {"nodes": int(tree.info.nodes), "tri_refs": int(tree.info.tri_refs),
+               "probe_leaves": int(tree.probe_info()[1]), "probe_refs": int(tree.probe_info()[2]),
                "create": min(create, key=lambda r: r["total"])}
         if not a.create_only:
             row["update_first"] = first

@@ -198,6 +198,8 @@ SIGNATURES = {
     "vrt_scene_chain_spacing": (C.c_int, [_P, f32p]),
     "vrt_scene_update": (C.c_int, [_P, f32p, f32p]),
     "vrt_scene_update_device": (C.c_int, [_P, _P, _P, _P]),
+    "vrt_scene_update_probes": (C.c_int, [_P, f32p, f32p, C.POINTER(Probe)]),
+    "vrt_scene_update_probes_device": (C.c_int, [_P, _P, _P, _P, _P]),
     "vrt_scene_update_stats": (C.c_int, [_P, f64p]),
     "vrt_scene_update_scratch": (C.c_int, [_P, C.c_int, i64p]),
     "vrt_scene_device_array": (C.c_int, [_P, C.c_int, _P, C.c_int64, i64p]),

@@ -309,6 +309,24 @@ class VoxelOctree:
         self.info = _ffi.SceneInfo()
         check(lib().vrt_scene_info(self.h, C.byref(self.info)), "vrt_scene_info")
 
+    _probes = None
+    _probes_moved = False
+
+    @property
+    def probes(self):
+        """The scene's probes as (n, 4) {o, r}, or None.  After an
+        update_probes_device that moved them they are fetched from the scene's
+        device copy, once, when first asked for."""
+        if self._probes_moved:
+            self._probes = np.ascontiguousarray(self.device_array(7).view(np.float32).reshape(-1, 4))
+            self._probes_moved = False
+        return self._probes
+
+    @probes.setter
+    def probes(self, value):
+        self._probes = value
+        self._probes_moved = False
+
     def close(self):
         if self.h:
             lib().vrt_scene_destroy(self.h)
@@ -376,6 +394,47 @@ class VoxelOctree:
               "vrt_scene_update_device")
         check(lib().vrt_scene_info(self.h, C.byref(self.info)), "vrt_scene_info")
 
+    def update_probes(self, pos, nrm=None, probes=None):
+        """update() for a scene with light probes (vrt_scene_update_probes):
+        new positions, unless nrm is None new normals, and unless probes is
+        None new probe centres and radii ((nprobe, 4) {o, r} or LightProbe
+        objects).  Afterwards the scene equals one freshly built from these
+        arrays, except that the stored SGs stay."""
+        pos = np.ascontiguousarray(pos, np.float32).reshape(-1)
+        n9 = 9 * self.scene.ntri
+        if pos.size != n9:
+            raise ValueError(f"pos has {pos.size} floats, the scene needs {n9}")
+        if nrm is not None:
+            nrm = np.ascontiguousarray(nrm, np.float32).reshape(-1)
+            if nrm.size != n9:
+                raise ValueError(f"nrm has {nrm.size} floats, the scene needs {n9}")
+        pp = None
+        if probes is not None:
+            probes = _probes_arg(probes)
+            have = 0 if self.probes is None else len(self.probes)
+            if probes is None or len(probes) != have:
+                raise ValueError(f"probes has {0 if probes is None else len(probes)} records, the scene has {have}")
+            pp = probes.ctypes.data_as(C.POINTER(_ffi.Probe))
+        check(lib().vrt_scene_update_probes(self.h, ptr(pos, _ffi.f32p), ptr(nrm, _ffi.f32p), pp),
+              "vrt_scene_update_probes")
+        if probes is not None:
+            self.probes = probes
+        check(lib().vrt_scene_info(self.h, C.byref(self.info)), "vrt_scene_info")
+
+    def update_probes_device(self, d_pos_ptr, d_nrm_ptr=None, d_probes_ptr=None, stream_ptr=None):
+        """update_probes() from device arrays on the scene's device, read in
+        the order of stream_ptr (vrt_scene_update_probes_device); ready on
+        return.  self.probes is fetched again from the scene's device copy
+        when it is next asked for, not here."""
+        check(lib().vrt_scene_update_probes_device(self.h, C.c_void_p(d_pos_ptr),
+                                                   C.c_void_p(d_nrm_ptr) if d_nrm_ptr else None,
+                                                   C.c_void_p(d_probes_ptr) if d_probes_ptr else None,
+                                                   C.c_void_p(stream_ptr) if stream_ptr else None),
+              "vrt_scene_update_probes_device")
+        if d_probes_ptr:
+            self._probes_moved = True
+        check(lib().vrt_scene_info(self.h, C.byref(self.info)), "vrt_scene_info")
+
     def update_stats(self):
         """The last update's wall-clock split in ms (vrt_scene_update_stats)."""
         ms = np.zeros(4, np.float64)
@@ -392,7 +451,8 @@ class VoxelOctree:
 
     def device_array(self, kind):
         """One derived device array as bytes (vrt_scene_device_array): 0 leaf
-        records, 1 per-record boxes, 2 march records, 3 TriPos, 4 TriAttr."""
+        records, 1 per-record boxes, 2 march records, 3 TriPos, 4 TriAttr; on a
+        scene with probes also 5 pnode, 6 pref, 7 the probes."""
         nb = C.c_int64()
         check(lib().vrt_scene_device_array(self.h, int(kind), None, 0, C.byref(nb)), "vrt_scene_device_array")
         out = np.zeros(nb.value, np.uint8)

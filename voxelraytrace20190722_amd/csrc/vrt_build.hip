@@ -463,9 +463,51 @@ __global__ __launch_bounds__(256) void k_root_keys(int n, const float *__restric
         }
 }
 
-// the float at each winning index (its own sign of zero)
-__global__ void k_root_box(const float *__restrict__ pos, const unsigned long long *__restrict__ keys,
-                           float *__restrict__ box)
+// The probes' faces behind the vertices (build_tree merges every probe's
+// {o - r, o + r}, one float operation each, after the triangles and in probe
+// order): probe i has sequence number seq0 + i, seq0 = 3 * ntri, so a vertex
+// beats a probe face of the same value and probe i beats probe i + 1.  The
+// probes are checked here as vrt_scene_create_probes checks them: *bad = the
+// lowest index of a probe with a centre that is not finite or a radius that
+// is not finite or negative (starts as all ones).
+__global__ __launch_bounds__(256) void k_root_keys_probes(int n, const float4 *__restrict__ probes, uint32_t seq0,
+                                                          unsigned long long *__restrict__ keys, unsigned int *bad)
+{
+        const int i = blockIdx.x * blockDim.x + threadIdx.x;
+        uint64_t mn[3] = { ~0ull, ~0ull, ~0ull }, mx[3] = { ~0ull, ~0ull, ~0ull };
+        if (i < n) {
+                const float4 pb = probes[i];
+                const float o[3] = { pb.x, pb.y, pb.z };
+                const float inf = __builtin_huge_valf();
+                const bool finite = fabsf(o[0]) < inf && fabsf(o[1]) < inf && fabsf(o[2]) < inf && fabsf(pb.w) < inf;
+                if (!finite || pb.w < 0.f)
+                        atomicMin(bad, (unsigned int)i);
+                const uint32_t seq = seq0 + (uint32_t)i;
+#pragma unroll
+                for (int k = 0; k < 3; ++k) {
+                        const float lo = o[k] - pb.w, hi = o[k] + pb.w;
+                        if (lo < kFltMax)
+                                mn[k] = ((uint64_t)ord_f32(lo) << 32) | seq;
+                        if (hi > -kFltMax)
+                                mx[k] = ((uint64_t)(~ord_f32(hi)) << 32) | seq;
+                }
+        }
+#pragma unroll
+        for (int k = 0; k < 3; ++k) {
+                const uint64_t a = wave_min_u64(mn[k]), b = wave_min_u64(mx[k]);
+                if ((threadIdx.x & 63) == 0) {
+                        if (a != ~0ull)
+                                atomicMin(&keys[k], (unsigned long long)a);
+                        if (b != ~0ull)
+                                atomicMin(&keys[3 + k], (unsigned long long)b);
+                }
+        }
+}
+
+// the float at each winning index (its own sign of zero); a sequence number
+// from nvert = 3 * ntri on is a probe's face, computed again
+__global__ void k_root_box(const float *__restrict__ pos, const float4 *__restrict__ probes, uint32_t nvert,
+                           const unsigned long long *__restrict__ keys, float *__restrict__ box)
 {
         const int j = threadIdx.x;
         if (j >= 6)
@@ -477,7 +519,13 @@ __global__ void k_root_box(const float *__restrict__ pos, const unsigned long lo
                 return;
         }
         const uint32_t seq = (uint32_t)(key & 0xFFFFFFFFu);
-        box[j] = pos[9 * (int64_t)(seq / 3u) + 3 * (seq % 3u) + k];
+        if (seq < nvert || !probes) {
+                box[j] = pos[9 * (int64_t)(seq / 3u) + 3 * (seq % 3u) + k];
+                return;
+        }
+        const float4 pb = probes[seq - nvert];
+        const float o = k == 0 ? pb.x : k == 1 ? pb.y : pb.z;
+        box[j] = j < 3 ? o - pb.w : o + pb.w;
 }
 
 __global__ __launch_bounds__(256) void k_leaf_counts(int64_t n, const NodeRec *__restrict__ nodes,
@@ -1048,15 +1096,23 @@ hipError_t build_tree_device(int device, const float *pos, int ntri, const float
         return hipSuccess;
 }
 
-hipError_t launch_root_box(const float *d_pos, int ntri, uint64_t *keys, float *box, hipStream_t st)
+hipError_t launch_root_box(const float *d_pos, int ntri, const float4 *d_probes, int nprobe, uint64_t *keys,
+                           float *box, hipStream_t st)
 {
         if (hipError_t e = hipMemsetAsync(keys, 0xFF, 6 * sizeof(uint64_t), st))
                 return e;
         if (ntri > 0)
                 hipLaunchKernelGGL(k_root_keys, dim3(grid_of(ntri)), dim3(256), 0, st, ntri, d_pos,
                                    reinterpret_cast<unsigned long long *>(keys));
-        hipLaunchKernelGGL(k_root_box, dim3(1), dim3(64), 0, st, d_pos,
-                           reinterpret_cast<const unsigned long long *>(keys), box);
+        if (nprobe > 0) {
+                unsigned int *const bad = reinterpret_cast<unsigned int *>(box + 6);
+                if (hipError_t e = hipMemsetAsync(bad, 0xFF, sizeof *bad, st))
+                        return e;
+                hipLaunchKernelGGL(k_root_keys_probes, dim3(grid_of(nprobe)), dim3(256), 0, st, nprobe, d_probes,
+                                   3u * (uint32_t)ntri, reinterpret_cast<unsigned long long *>(keys), bad);
+        }
+        hipLaunchKernelGGL(k_root_box, dim3(1), dim3(64), 0, st, d_pos, nprobe > 0 ? d_probes : nullptr,
+                           3u * (uint32_t)ntri, reinterpret_cast<const unsigned long long *>(keys), box);
         return hipGetLastError();
 }
 

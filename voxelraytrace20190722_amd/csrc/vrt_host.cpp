@@ -379,14 +379,17 @@ struct vrt_scene {
         std::vector<int64_t> level_begin;  // BFS level l (1-based) = [lb[l-1], lb[l])
         // light probes as voxels (vrt_scene_create_probes; empty otherwise):
         // the probes, per node its probe list or child mask (ProbeDev::pnode),
-        // the concatenated leaf lists, the stored SGs (14 per probe), and the
-        // device copy of the first three (one allocation, d_probe)
+        // the concatenated leaf lists, the stored SGs (14 per probe), and their
+        // device copies: the probes and the SGs, whose sizes never change, in
+        // d_probe; pnode (one per node) and pref (one per probe reference)
+        // follow the geometry and have an owner each, with its capacity, as
+        // g_nodes ... g_xnodes have (vrt_scene_update_probes)
         std::vector<vrt_probe> probes;
         std::vector<uint2> pnode;
         std::vector<uint32_t> pref;
         std::vector<vrt_sg> probe_sgs;
         int64_t probe_leaves = 0;
-        DevMem d_probe;
+        DevMem d_probe, g_pnode, g_pref;
         ProbeDev pdev{};
         // the stored SGs' device copy (in d_probe), read by the kernels that
         // shade a probe hit.  The host copy probe_sgs is what the host
@@ -448,6 +451,9 @@ struct vrt_scene {
         // steady animation neither allocates nor frees (nor zero-fills) them
         std::vector<NodeRec> up_nodes;
         std::vector<uint32_t> up_vox, up_ref_tri;
+        std::vector<uint2> up_pnode;  // ... and a probe scene's (vrt_scene_update_probes)
+        std::vector<uint32_t> up_pref;
+        std::vector<vrt_probe> up_probes;
         Event up_in, up_e0, up_e1;
         double up_ms[4] = {};
         bool updated = false;
@@ -1111,19 +1117,20 @@ static int upload(vrt_scene *s, const vrt_scene_desc *d)
                 const size_t sz_pr = align_up(std::max<size_t>(1, s->pref.size()) * sizeof(uint32_t));
                 const size_t sz_pb = align_up(s->probes.size() * sizeof(vrt_probe));
                 const size_t sz_sg = align_up(s->probe_sgs.size() * sizeof(vrt_sg));
-                HIPCHK(s->d_probe.alloc(sz_pn + sz_pr + sz_pb + sz_sg));
+                HIPCHK(s->g_pnode.alloc(sz_pn));
+                HIPCHK(s->g_pref.alloc(sz_pr));
+                HIPCHK(s->d_probe.alloc(sz_pb + sz_sg));
                 char *pb = s->d_probe.as<char>();
-                HIPCHK(hipMemcpy(pb, s->pnode.data(), s->pnode.size() * sizeof(uint2), hipMemcpyHostToDevice));
+                HIPCHK(hipMemcpy(s->g_pnode, s->pnode.data(), s->pnode.size() * sizeof(uint2), hipMemcpyHostToDevice));
                 if (!s->pref.empty())
-                        HIPCHK(hipMemcpy(pb + sz_pn, s->pref.data(), s->pref.size() * sizeof(uint32_t),
+                        HIPCHK(hipMemcpy(s->g_pref, s->pref.data(), s->pref.size() * sizeof(uint32_t),
                                          hipMemcpyHostToDevice));
-                HIPCHK(hipMemcpy(pb + sz_pn + sz_pr, s->probes.data(), s->probes.size() * sizeof(vrt_probe),
-                                 hipMemcpyHostToDevice));
-                s->pdev.pnode = reinterpret_cast<const uint2 *>(pb);
-                s->pdev.pref = reinterpret_cast<const uint32_t *>(pb + sz_pn);
-                s->pdev.probes = reinterpret_cast<const float4 *>(pb + sz_pn + sz_pr);
+                HIPCHK(hipMemcpy(pb, s->probes.data(), s->probes.size() * sizeof(vrt_probe), hipMemcpyHostToDevice));
+                s->pdev.pnode = s->g_pnode.as<uint2>();
+                s->pdev.pref = s->g_pref.as<uint32_t>();
+                s->pdev.probes = reinterpret_cast<const float4 *>(pb);
                 s->pdev.ntri = s->ntri;
-                s->d_sgs = reinterpret_cast<float *>(pb + sz_pn + sz_pr + sz_pb);
+                s->d_sgs = reinterpret_cast<float *>(pb + sz_pb);
                 HIPCHK(hipMemcpy(s->d_sgs, s->probe_sgs.data(), s->probe_sgs.size() * sizeof(vrt_sg),
                                  hipMemcpyHostToDevice));
                 tot += sz_pn + sz_pr + sz_pb + sz_sg;
@@ -4324,24 +4331,35 @@ extern "C" int vrt_device_selftest_order(int device, const float *dist, const ui
 // TriAttr) -- and copies back only what host code reads (nodes, node_vox,
 // ref_tri).  Everything that can refuse happens before the first write to an
 // array the scene is using, so a refused update leaves the scene as it was.
+// A scene with light probes moves through vrt_scene_update_probes[_device],
+// the same path with the probes in the root box and in the frontier build.
 // ---------------------------------------------------------------------------
-static int update_args_ok(vrt_scene *s, const float *pos, const char *what)
+// probe_call: vrt_scene_update_probes[_device], which takes the scenes with
+// light probes that vrt_scene_update refuses, and no others
+static int update_args_ok(vrt_scene *s, const float *pos, const char *what, bool probe_call = false)
 {
         if (!s || !pos)
                 return fail(VRT_E_INVALID, "%s: null argument", what);
-        if (int rc = no_probe_scene(s, what))
-                return rc;
+        if (probe_call && s->probes.empty())
+                return fail(VRT_E_INVALID, "%s: the scene has no light probes; use vrt_scene_update", what);
+        if (!probe_call)
+                if (int rc = no_probe_scene(s, what))
+                        return rc;
         if (s->owned)
                 return fail(VRT_E_INVALID, "%s: the scene is a rank of a vrt_multi handle, whose ranks must stay replicas",
                             what);
         if ((uint32_t)s->ntri > 0x55555555u)
                 return fail(VRT_E_INVALID, "%s: %d triangles, 3 x that must stay below 2^32", what, s->ntri);
+        // the root box's sequence numbers: the vertices, then the probes
+        if (3ull * (uint64_t)s->ntri + (uint64_t)s->probes.size() > 0x100000000ull)
+                return fail(VRT_E_INVALID, "%s: 3 x %d triangles + %zu probes must stay within 2^32", what, s->ntri,
+                            s->probes.size());
         return VRT_OK;
 }
 
 // The host-only scene: the host build and finish on the new arrays, made
 // beside the scene and swapped in.
-static int update_host(vrt_scene *s, const float *pos, const float *nrm)
+static int update_host(vrt_scene *s, const float *pos, const float *nrm, const vrt_probe *probes)
 {
         const double t0 = now_ms();
         std::unique_ptr<vrt_scene> t(new (std::nothrow) vrt_scene);
@@ -4355,6 +4373,11 @@ static int update_host(vrt_scene *s, const float *pos, const float *nrm)
         d.pos = pos;
         d.nrm = nrm;
         try {
+                // a probe scene: the new probes, or the ones it has
+                if (probes)
+                        t->probes.assign(probes, probes + s->probes.size());
+                else
+                        t->probes = s->probes;
                 if (int rc = build_tree(t.get(), &d, false))
                         return rc;
                 const int n = s->ntri;
@@ -4387,6 +4410,10 @@ static int update_host(vrt_scene *s, const float *pos, const float *nrm)
         s->tri_pos.swap(t->tri_pos);
         s->tri_attr.swap(t->tri_attr);
         s->level_begin.swap(t->level_begin);
+        s->probes.swap(t->probes);
+        s->pnode.swap(t->pnode);
+        s->pref.swap(t->pref);
+        s->probe_leaves = t->probe_leaves;
         s->info.nodes = t->info.nodes;
         s->info.internal = t->info.internal;
         s->info.leaves = t->info.leaves;
@@ -4410,9 +4437,13 @@ static hipError_t fetch(void *dst, const void *src, size_t bytes, hipStream_t st
         return bytes ? hipMemcpyAsync(dst, src, bytes, hipMemcpyDeviceToHost, st) : hipSuccess;
 }
 
-// pos / nrm: host arrays (on_device false: copied to the scratch first) or
-// device arrays read in the order of the caller's stream cst
-static int update_device(vrt_scene *s, const float *pos, const float *nrm, bool on_device, hipStream_t cst)
+// pos / nrm / probes: host arrays (on_device false: copied to the scratch
+// first) or device arrays read in the order of the caller's stream cst.  A
+// probe scene (vrt_scene_update_probes; probes == nullptr: they stay) adds the
+// probes' faces to the root box, the probe frontier to the build, and pnode /
+// pref / the probes to what is swapped in and copied back.
+static int update_device(vrt_scene *s, const float *pos, const float *nrm, const vrt_probe *probes, bool on_device,
+                         hipStream_t cst)
 {
         const double t0 = now_ms();
         // Wait for all work the scene has in flight.  Not every launch leaves
@@ -4430,10 +4461,25 @@ static int update_device(vrt_scene *s, const float *pos, const float *nrm, bool 
         }
         BuildScratch &sc = s->bscratch;
         const int n = s->ntri;
+        const int np = (int)s->probes.size();
         const float *d_pos = pos, *d_nrm = nrm;
+        // the probes the build reads: the caller's, or the scene's own
+        const float4 *d_probes = np ? s->pdev.probes : nullptr;
         if (on_device) {
                 HIPCHK(hipEventRecord(s->up_in, cst));
                 HIPCHK(hipStreamWaitEvent(st, s->up_in, 0));
+                if (np && probes) {
+                        d_probes = reinterpret_cast<const float4 *>(probes);
+                        // vrt_probe promises 4-byte alignment (a slice of a larger
+                        // array); the kernels load float4, so such an array goes
+                        // through the scratch copy a host array takes
+                        if (reinterpret_cast<uintptr_t>(probes) % sizeof(float4)) {
+                                HIPCHK(sc.probes.need((size_t)np * sizeof(float4)));
+                                HIPCHK(hipMemcpyAsync(sc.probes, probes, (size_t)np * sizeof(float4),
+                                                      hipMemcpyDeviceToDevice, st));
+                                d_probes = sc.probes.as<float4>();
+                        }
+                }
         } else {
                 HIPCHK(sc.pos.need((size_t)n * 36));
                 HIPCHK(hipMemcpyAsync(sc.pos, pos, (size_t)n * 36, hipMemcpyHostToDevice, st));
@@ -4443,20 +4489,32 @@ static int update_device(vrt_scene *s, const float *pos, const float *nrm, bool 
                         HIPCHK(hipMemcpyAsync(sc.nrm, nrm, (size_t)n * 36, hipMemcpyHostToDevice, st));
                         d_nrm = sc.nrm.as<float>();
                 }
+                if (np && probes) {
+                        HIPCHK(sc.probes.need((size_t)np * sizeof(float4)));
+                        HIPCHK(hipMemcpyAsync(sc.probes, probes, (size_t)np * sizeof(float4), hipMemcpyHostToDevice, st));
+                        d_probes = sc.probes.as<float4>();
+                }
         }
+        const bool new_probes = np && probes;
         HIPCHK(hipEventRecord(s->up_e0, st));
-        // root box: 6 keys, then the 6 floats the host needs for info
-        float root[6];
+        // root box: 6 keys, then the 6 floats the host needs for info and, on a
+        // probe scene, the index of the first probe creation would refuse
+        float root[7];
+        uint32_t bad_probe = 0xFFFFFFFFu;
         HIPCHK(sc.root.need(128));
-        HIPCHK(launch_root_box(d_pos, n, sc.root.as<uint64_t>(), sc.root.as<float>() + 12, st));
-        HIPCHK(fetch(root, sc.root.as<float>() + 12, sizeof root, st));
+        HIPCHK(launch_root_box(d_pos, n, d_probes, np, sc.root.as<uint64_t>(), sc.root.as<float>() + 12, st));
+        HIPCHK(fetch(root, sc.root.as<float>() + 12, (np ? 7 : 6) * sizeof(float), st));
         HIPCHK(hipStreamSynchronize(st));
+        if (np)
+                std::memcpy(&bad_probe, &root[6], sizeof bad_probe);
+        if (new_probes && bad_probe != 0xFFFFFFFFu)
+                return fail(VRT_E_INVALID, "probe %u: centre must be finite, radius finite and >= 0", bad_probe);
         DeviceTree tree;
         try {
                 std::string err;
                 const bool fail_limit = (test_flags() & VRT_TEST_UPDATE_TOO_LARGE) != 0;
-                if (build_frontier_device(sc, d_pos, n, root, root + 3, s->max_depth, nullptr, 0, st, fail_limit, &tree,
-                                          &err) != hipSuccess) {
+                if (build_frontier_device(sc, d_pos, n, root, root + 3, s->max_depth, d_probes, np, st, fail_limit,
+                                          &tree, &err) != hipSuccess) {
                         (void)hipGetLastError();
                         (void)hipStreamSynchronize(st);
                         if (tree.too_large)
@@ -4486,16 +4544,22 @@ static int update_device(vrt_scene *s, const float *pos, const float *nrm, bool 
         const bool rboxes = VRT_LEAF_CULL && !wide && lb_on;
         const size_t refs_bytes = (size_t)nr * (wide ? sizeof(RefRec64) : sizeof(RefRec48));
         const size_t sz_rbox = rboxes ? align_up(((size_t)nr + kRefBoxPad) * sizeof(RefBox)) : 0;
-        const size_t want[4] = { align_up((size_t)nn * sizeof(NodeRec)), align_up((size_t)nn * sizeof(uint32_t)),
-                                 align_up(sz_rbox + std::max<size_t>(64, refs_bytes)),
-                                 align_up((size_t)nn * sizeof(XNodeRec)) };
+        // a probe scene's pnode (one per node) and pref (one per probe
+        // reference) as upload() sizes them; nothing on any other scene
+        const int64_t npr = tree.nprefs;
+        constexpr int kOwners = 6;
+        const size_t want[kOwners] = { align_up((size_t)nn * sizeof(NodeRec)), align_up((size_t)nn * sizeof(uint32_t)),
+                                       align_up(sz_rbox + std::max<size_t>(64, refs_bytes)),
+                                       align_up((size_t)nn * sizeof(XNodeRec)),
+                                       np ? align_up((size_t)nn * sizeof(uint2)) : 0,
+                                       np ? align_up(std::max<size_t>(1, (size_t)npr) * sizeof(uint32_t)) : 0 };
         // larger arrays are made beside the ones in use and swapped in only
         // when all of them exist
-        DevMem *const own[4] = { &s->g_nodes, &s->g_vox, &s->g_refs, &s->g_xnodes };
-        DevMem grown[4];
+        DevMem *const own[kOwners] = { &s->g_nodes, &s->g_vox, &s->g_refs, &s->g_xnodes, &s->g_pnode, &s->g_pref };
+        DevMem grown[kOwners];
         std::vector<NodeRec> &h_nodes = s->up_nodes;
         std::vector<uint32_t> &h_vox = s->up_vox, &h_reftri = s->up_ref_tri;
-        for (int i = 0; i < 4; ++i)
+        for (int i = 0; i < kOwners; ++i)
                 if (own[i]->size() < want[i] && grown[i].alloc(want[i]) != hipSuccess) {
                         (void)hipGetLastError();
                         return fail(VRT_E_DEVICE, "scene update: no device memory for %zu bytes", want[i]);
@@ -4509,6 +4573,12 @@ static int update_device(vrt_scene *s, const float *pos, const float *nrm, bool 
                 h_nodes.resize((size_t)nn);
                 h_vox.resize((size_t)nn);
                 h_reftri.resize((size_t)nr);
+                if (np) {
+                        s->up_pnode.resize((size_t)nn);
+                        s->up_pref.resize((size_t)npr);
+                        if (new_probes)
+                                s->up_probes.resize((size_t)np);
+                }
         } catch (const std::bad_alloc &) {
                 return fail(VRT_E_NOMEM, "scene update: out of host memory");
         }
@@ -4517,7 +4587,7 @@ static int update_device(vrt_scene *s, const float *pos, const float *nrm, bool 
         // later error return leaves one on released memory (after a
         // VRT_E_DEVICE from here on the scene's contents are undefined).
         const size_t old_nodes = s->nodes.size();
-        for (int i = 0; i < 4; ++i)
+        for (int i = 0; i < kOwners; ++i)
                 if (grown[i])
                         *own[i] = std::move(grown[i]);
         s->wide_leaves = wide;
@@ -4529,6 +4599,19 @@ static int update_device(vrt_scene *s, const float *pos, const float *nrm, bool 
         s->dev.wide_leaves = wide ? 1 : 0;
         HIPCHK(hipMemcpyAsync(s->g_nodes, tree.nodes, (size_t)nn * sizeof(NodeRec), hipMemcpyDeviceToDevice, st));
         HIPCHK(hipMemcpyAsync(s->g_vox, tree.node_vox, (size_t)nn * sizeof(uint32_t), hipMemcpyDeviceToDevice, st));
+        if (np) {
+                // the probes and the stored SGs keep their place in d_probe,
+                // whose size never changes: only the probes' values move
+                s->pdev.pnode = s->g_pnode.as<uint2>();
+                s->pdev.pref = s->g_pref.as<uint32_t>();
+                HIPCHK(hipMemcpyAsync(s->g_pnode, tree.pnode, (size_t)nn * sizeof(uint2), hipMemcpyDeviceToDevice, st));
+                if (npr)
+                        HIPCHK(hipMemcpyAsync(s->g_pref, tree.pref, (size_t)npr * sizeof(uint32_t),
+                                              hipMemcpyDeviceToDevice, st));
+                if (new_probes)
+                        HIPCHK(hipMemcpyAsync(const_cast<float4 *>(s->pdev.probes), d_probes,
+                                              (size_t)np * sizeof(float4), hipMemcpyDeviceToDevice, st));
+        }
         FinishArgs fa{};
         fa.tree = &tree;
         fa.pos = d_pos;
@@ -4556,6 +4639,15 @@ static int update_device(vrt_scene *s, const float *pos, const float *nrm, bool 
         HIPCHK(fetch(h_reftri.data(), fa.ref_tri, (size_t)nr * 4, st));
         if (fast)
                 HIPCHK(fetch(chain, fa.chain_out, sizeof chain, st));
+        unsigned int probe_leaves = 0;
+        if (np) {
+                HIPCHK(fetch(s->up_pnode.data(), tree.pnode, (size_t)nn * sizeof(uint2), st));
+                HIPCHK(fetch(s->up_pref.data(), tree.pref, (size_t)npr * sizeof(uint32_t), st));
+                if (tree.probe_leaves)
+                        HIPCHK(fetch(&probe_leaves, tree.probe_leaves, sizeof probe_leaves, st));
+                if (new_probes)
+                        HIPCHK(fetch(s->up_probes.data(), d_probes, (size_t)np * sizeof(float4), st));
+        }
         HIPCHK(hipStreamSynchronize(st));
         const double t2 = now_ms();
         // ---- host mirrors and the scene's constants
@@ -4563,6 +4655,13 @@ static int update_device(vrt_scene *s, const float *pos, const float *nrm, bool 
         s->node_vox.swap(h_vox);
         s->ref_tri.swap(h_reftri);
         s->level_begin.swap(tree.level_begin);
+        if (np) {
+                s->pnode.swap(s->up_pnode);
+                s->pref.swap(s->up_pref);
+                s->probe_leaves = probe_leaves;
+                if (new_probes)
+                        s->probes.swap(s->up_probes);
+        }
         // no reader after upload() on a scene that cannot be replicated
         std::vector<RefRec48>().swap(s->refs48);
         std::vector<RefRec64>().swap(s->refs64);
@@ -4600,7 +4699,7 @@ static int update_device(vrt_scene *s, const float *pos, const float *nrm, bool 
                                 s->ord_wmin[k] = f[k];
         }
         int64_t bytes = (int64_t)(s->d_mem.size() + s->d_probe.size());
-        for (int i = 0; i < 4; ++i)
+        for (int i = 0; i < kOwners; ++i)
                 bytes += (int64_t)own[i]->size();
         s->info.device_bytes = bytes;
         // ---- derived state back to a fresh scene's; the allocations stay
@@ -4653,8 +4752,8 @@ extern "C" int vrt_scene_update(vrt_scene *s, const float *pos, const float *nrm
                 return rc;
         std::lock_guard<std::mutex> lk(s->mu);
         if (!s->d_mem)
-                return update_host(s, pos, nrm);
-        return update_device(s, pos, nrm, false, nullptr);
+                return update_host(s, pos, nrm, nullptr);
+        return update_device(s, pos, nrm, nullptr, false, nullptr);
 }
 
 extern "C" int vrt_scene_update_device(vrt_scene *s, const float *d_pos, const float *d_nrm, void *stream)
@@ -4664,7 +4763,36 @@ extern "C" int vrt_scene_update_device(vrt_scene *s, const float *d_pos, const f
         if (int rc = update_args_ok(s, d_pos, "vrt_scene_update_device"))
                 return rc;
         std::lock_guard<std::mutex> lk(s->mu);
-        return update_device(s, d_pos, d_nrm, true, static_cast<hipStream_t>(stream));
+        return update_device(s, d_pos, d_nrm, nullptr, true, static_cast<hipStream_t>(stream));
+}
+
+extern "C" int vrt_scene_update_probes(vrt_scene *s, const float *pos, const float *nrm, const vrt_probe *probes)
+{
+        if (int rc = update_args_ok(s, pos, "vrt_scene_update_probes", true))
+                return rc;
+        std::lock_guard<std::mutex> lk(s->mu);
+        // as at creation; the device variant's check is the root-box kernel's
+        if (probes)
+                for (size_t k = 0; k < s->probes.size(); ++k) {
+                        const vrt_probe &pb = probes[k];
+                        if (!std::isfinite(pb.o[0]) || !std::isfinite(pb.o[1]) || !std::isfinite(pb.o[2]) ||
+                            !std::isfinite(pb.r) || pb.r < 0.f)
+                                return fail(VRT_E_INVALID, "probe %zu: centre must be finite, radius finite and >= 0", k);
+                }
+        if (!s->d_mem)
+                return update_host(s, pos, nrm, probes);
+        return update_device(s, pos, nrm, probes, false, nullptr);
+}
+
+extern "C" int vrt_scene_update_probes_device(vrt_scene *s, const float *d_pos, const float *d_nrm,
+                                              const vrt_probe *d_probes, void *stream)
+{
+        if (s && need_device(s))
+                return VRT_E_NODEVICE;
+        if (int rc = update_args_ok(s, d_pos, "vrt_scene_update_probes_device", true))
+                return rc;
+        std::lock_guard<std::mutex> lk(s->mu);
+        return update_device(s, d_pos, d_nrm, d_probes, true, static_cast<hipStream_t>(stream));
 }
 
 extern "C" int vrt_scene_update_stats(const vrt_scene *s, double ms[4])
@@ -4692,6 +4820,9 @@ extern "C" int vrt_scene_update_scratch(vrt_scene *s, int release, int64_t *byte
         std::vector<NodeRec>().swap(s->up_nodes);
         std::vector<uint32_t>().swap(s->up_vox);
         std::vector<uint32_t>().swap(s->up_ref_tri);
+        std::vector<uint2>().swap(s->up_pnode);
+        std::vector<uint32_t>().swap(s->up_pref);
+        std::vector<vrt_probe>().swap(s->up_probes);
         return VRT_OK;
 }
 
@@ -4705,6 +4836,9 @@ extern "C" int vrt_scene_device_array(vrt_scene *s, int kind, void *out, int64_t
         const size_t nr = s->ref_tri.size();
         const void *src = nullptr;
         size_t n = 0;
+        const int last = s->probes.empty() ? 4 : 7;  // 5 to 7: a probe scene's side arrays
+        if (kind < 0 || kind > last)
+                return fail(VRT_E_INVALID, "vrt_scene_device_array: kind %d outside [0, %d]", kind, last);
         switch (kind) {
         case 0:
                 src = s->dev.refs;
@@ -4726,8 +4860,18 @@ extern "C" int vrt_scene_device_array(vrt_scene *s, int kind, void *out, int64_t
                 src = s->dev.tri_attr;
                 n = (size_t)s->ntri * sizeof(TriAttr);
                 break;
-        default:
-                return fail(VRT_E_INVALID, "vrt_scene_device_array: kind %d outside [0, 4]", kind);
+        case 5:
+                src = s->pdev.pnode;
+                n = s->pnode.size() * sizeof(uint2);
+                break;
+        case 6:
+                src = s->pdev.pref;
+                n = s->pref.size() * sizeof(uint32_t);
+                break;
+        case 7:
+                src = s->pdev.probes;
+                n = s->probes.size() * sizeof(vrt_probe);
+                break;
         }
         *bytes = (int64_t)n;
         if (!out)

@@ -809,16 +809,18 @@ struct BuildScratch {
         // ... and the probe frontier with its outputs
         GrowMem qa, qb, pkeys, pkeys_s, pref, pnode, phas;
         // the callers': positions and normals (build_tree_device: the probes in
-        // nrm), root-box keys (6 x 8 B) then the box (6 floats), and the
-        // finish kernels' ref_tri, per-node lo/hi, chain minima, leaf counts
-        GrowMem pos, nrm, root, ref_tri, lohi, chain, counts;
+        // nrm), root-box keys (6 x 8 B) then the box (6 floats) and the bad-probe
+        // word, and the finish kernels' ref_tri, per-node lo/hi, chain minima,
+        // leaf counts; probes: a probe update's host probes on the device
+        GrowMem pos, nrm, root, ref_tri, lohi, chain, counts, probes;
 
         size_t bytes() const
         {
                 size_t b = 0;
                 for (const GrowMem *g : { &cnt, &pa, &pb, &codes, &codes_s, &uniq, &nuniq, &temp, &iall, &keys,
                                           &keys_s, &inode, &nodes, &vox, &has, &qa, &qb, &pkeys, &pkeys_s, &pref,
-                                          &pnode, &phas, &pos, &nrm, &root, &ref_tri, &lohi, &chain, &counts })
+                                          &pnode, &phas, &pos, &nrm, &root, &ref_tri, &lohi, &chain, &counts,
+                                          &probes })
                         b += g->size();
                 return b;
         }
@@ -830,7 +832,7 @@ struct DeviceTree {
         const uint64_t *refs = nullptr;    // sorted (leaf code << 32 | tri)
         int64_t nnodes = 0, nrefs = 0, ninternal = 0;
         std::vector<int64_t> level_begin;
-        // probe scenes (build_tree_device only)
+        // probe scenes (nprobe > 0)
         const uint2 *pnode = nullptr;
         const uint32_t *pref = nullptr;
         int64_t nprefs = 0;
@@ -846,8 +848,13 @@ hipError_t build_frontier_device(BuildScratch &sc, const float *d_pos, int ntri,
                                  hipStream_t st, bool fail_limit, DeviceTree *out, std::string *err);
 // Root box of ntri triangles as build_tree merges it: NaN ignored, the first
 // of equal extremes in (triangle, vertex) order wins.  keys: 6 uint64 of
-// device scratch; box: 6 floats on the device (min xyz, max xyz).
-hipError_t launch_root_box(const float *d_pos, int ntri, uint64_t *keys, float *box, hipStream_t st);
+// device scratch; box: 6 floats on the device (min xyz, max xyz).  With
+// nprobe > 0 the probes' faces {o - r, o + r} follow the vertices in probe
+// order (3 * ntri + nprobe must not exceed 2^32), and a seventh word behind
+// the box receives the lowest index of a probe that vrt_scene_create_probes
+// would refuse, 0xFFFFFFFF when there is none.
+hipError_t launch_root_box(const float *d_pos, int ntri, const float4 *d_probes, int nprobe, uint64_t *keys,
+                           float *box, hipStream_t st);
 // counts[0] = leaves, counts[1] = non-empty leaves of nodes[0, n) (zeroed here)
 hipError_t launch_leaf_counts(const NodeRec *nodes, int64_t n, unsigned int *counts, hipStream_t st);
 // The finish of a build on the device (finish_tree, ref_boxes, march_nodes,
