@@ -335,6 +335,16 @@ int vrt_device_selftest(int device, const double *mt_in, double *mt_out,
  * expanded: the refusal a huge scene would meet, which must leave the scene
  * on its previous geometry.  A host-side error return. */
 #define VRT_TEST_UPDATE_TOO_LARGE 0x80000
+/* VRT_TEST_MULTI_REFUSE_LAST: in vrt_multi_update[_device] the last rank's
+ * prepare reports the build's size limit (as VRT_TEST_UPDATE_TOO_LARGE does,
+ * for that rank only) while the other ranks succeed: the refusal of one rank
+ * must leave every rank on its previous geometry. */
+#define VRT_TEST_MULTI_REFUSE_LAST 0x100000
+/* VRT_TEST_MULTI_DIVERGE: after a successful commit of vrt_multi_update
+ * [_device] the lowest mantissa bit of the first float of the last rank's
+ * TriAttr array is flipped (a 4-byte device copy of a normal component), so
+ * that VRT_MULTI_UPDATE_VERIFY has a real one-bit difference to report. */
+#define VRT_TEST_MULTI_DIVERGE 0x200000
 int vrt_set_test_flags(int flags);
 /* The current vrt_set_test_flags value (so a caller can restore it). */
 int vrt_test_flags(void);
@@ -443,6 +453,26 @@ int vrt_scene_update_scratch(vrt_scene *s, int release, int64_t *bytes);
  * other): 5 pnode (8 B per node), 6 pref (4 B per probe reference), 7 the
  * probes (16 B each).  out == NULL returns only *bytes. */
 int vrt_scene_device_array(vrt_scene *s, int kind, void *out, int64_t cap, int64_t *bytes);
+
+/* ---- scene digest ---------------------------------------------------------
+ * The digest of a byte array read as W = nbytes / 4 little-endian 32-bit
+ * words w_0 .. w_{W-1} (nbytes % 4 != 0: VRT_E_INVALID):
+ *   sum over i of mix(((i + 1) * 0x9E3779B97F4A7C15) ^ w_i)   (mod 2^64)
+ *   mix(z): z ^= z >> 30; z *= 0xBF58476D1CE4E5B9; z ^= z >> 27;
+ *           z *= 0x94D049BB133111EB; z ^= z >> 31
+ * with i a 64-bit index from the array's first word.  The sum commutes, so
+ * every reduction order gives the same word; the empty array digests to 0.
+ * vrt_digest_host is the plain statement; vrt_scene_digest runs the device
+ * kernel (one launch) over the arrays an update rewrites and waits for it:
+ * items 0-7 are vrt_scene_device_array's kinds (an absent array digests to 0),
+ * 8 the node records, 9 the nodes' voxel indices.  VRT_E_NODEVICE on a
+ * host-only scene.  vrt_device_selftest_digest uploads `bytes` to a 16-byte-
+ * aligned buffer + misalign (0, 4, 8 or 12) and runs the kernel's own code;
+ * device < 0 is the host model. */
+#define VRT_DIGEST_ITEMS 10
+int vrt_scene_digest(vrt_scene *s, uint64_t out[VRT_DIGEST_ITEMS]);
+int vrt_digest_host(const void *bytes, int64_t nbytes, uint64_t *out);
+int vrt_device_selftest_digest(int device, const void *bytes, int64_t nbytes, int misalign, uint64_t *out);
 
 /* ---- multi-device frame (render_mt, VRT/camera.h:42-68,
  * over the GPUs of one node) --------------------------------------------------
@@ -826,6 +856,53 @@ int vrt_trace_frame_probes_device(vrt_scene *s, const vrt_camera *light_cam, con
 int vrt_scene_create_multi_probes(const vrt_scene_desc *desc, const vrt_probe *probes, int32_t nprobe,
                                   int max_depth, uint32_t device_mask, int flags, vrt_multi **out);
 int vrt_multi_set_probe_sgs(vrt_multi *m, const vrt_sg *sgs);
+
+/* ---- moving a multi-device scene (the vrt_multi handle) --------------------
+ * vrt_scene_update / vrt_scene_update_probes for every rank of a handle at
+ * once, so that the ranks stay replicas.  pos is required (ntri*9); nrm is
+ * optional (NULL: the stored normals stay); probes (nprobe records) is
+ * optional on a handle made by vrt_scene_create_multi_probes with probes
+ * (NULL: the probes stay where they are) and VRT_E_INVALID on any other.  On
+ * success every rank's scene equals, bit for bit, the same rank's scene of a
+ * handle freshly created from these arrays with VRT_BUILD_DEVICE (| VRT_BUILD_
+ * DEVICE_PROBES), whichever flags this handle was created with: every query,
+ * march, render and device array, and the host copy of the probes.  Derived
+ * state is a fresh scene's on every rank (no light map: vrt_render_trace_
+ * multi* return VRT_E_INVALID until vrt_lightmap_build_multi or
+ * vrt_trace_frame_multi* runs).  What the handle owns stays: communicator,
+ * streams, events, send / gather buffers, config-5 scratch, the image pair,
+ * the light mode, each rank scene's frames-in-flight hint, queues, scratch and
+ * update scratch, and the stored SGs on every rank.  Waiting and thread rules
+ * are vrt_scene_update's, per device; the call returns when every rank is
+ * ready, and the caller may then overwrite the arrays.
+ * All ranks or none: every rank first does everything that can refuse (bad
+ * arguments, a bad probe, a size limit of the build, no host or device memory:
+ * VRT_E_INVALID, VRT_E_NOMEM, or VRT_E_DEVICE from an allocation; the text
+ * names the rank and its device), and only when no rank refused is any array
+ * that a frame reads written on any rank.  A refusal leaves every rank on its
+ * previous geometry and probes, fully usable.  Only a failed launch or copy
+ * after that point (VRT_E_DEVICE) can leave the handle half rebuilt: destroy
+ * it then.
+ * flags: 0, or VRT_MULTI_UPDATE_VERIFY: after the update every rank computes
+ * vrt_scene_digest on its stream and the host compares the ten words of every
+ * rank, its vrt_scene_info counts, record format, root box and chain spacing
+ * with rank 0's; a difference is VRT_E_DEVICE "replicas diverged: rank %d
+ * (device %d), <item>".  Other bits are VRT_E_INVALID. */
+#define VRT_MULTI_UPDATE_VERIFY 1
+int vrt_multi_update(vrt_multi *m, const float *pos, const float *nrm, const vrt_probe *probes, int flags);
+/* The same from arrays on rank 0's device, read in `stream` order (a stream of
+ * that device; NULL = its null stream) and distributed to the other ranks by
+ * one ncclBroadcast per array (virtual ranks: device copies).  d_probes needs
+ * only a float's alignment.  A bad probe is found by the root-box kernel and
+ * reported as VRT_E_INVALID with its index. */
+int vrt_multi_update_device(vrt_multi *m, const float *d_pos, const float *d_nrm, const vrt_probe *d_probes,
+                            int flags, void *stream);
+/* The last successful update's wall-clock split: {total, the slowest rank's
+ * own vrt_scene_update_stats total, distribution of device arrays to ranks
+ * >= 1 (events on rank 0's stream; 0 for host arrays and for one rank), verify
+ * (0 without the flag)}.  VRT_E_INVALID before the first update. */
+int vrt_multi_update_stats(const vrt_multi *m, double ms[4]);
+
 /* How the ranks share a light-map build.  REPLICATED (the default): every rank
  * marches the whole light film.  SHARDED: rank i marches its tiles of the
  * light film's tile deal (the view's deal, vrt_tile_deal_map), the ranks

@@ -26,6 +26,17 @@ not counted (the first one in a process loads the code object).
                  triangles' box, moved with the placement, radius 0.1 x the
                  grid spacing.  (a) is vrt_scene_create_probes(VRT_BUILD_DEVICE |
                  VRT_BUILD_DEVICE_PROBES), (b) vrt_scene_update_probes[_device]
+  --ranks N      the multi-device handle on N virtual ranks of device 0 (all
+                 ranks share the one GPU: expect about N x a single update,
+                 and nothing from the per-rank host threads).  (a) is
+                 vrt_multi_destroy + vrt_scene_create_multi[_probes](VRT_BUILD_
+                 DEVICE), (b) vrt_multi_update[_device] with vrt_multi_update_
+                 stats' split, and one more update of each placement with
+                 VRT_MULTI_UPDATE_VERIFY for the verify time
+  --mask M       with or without --ranks: the handle on the real devices of
+                 mask M (--ranks then must be left out)
+Without --ranks / --mask the updated scene's vrt_scene_digest is timed too
+(blocking call, best of five) and reported with the bytes it digests.
 Prints and, with --out, writes one JSON document."""
 import argparse
 import json
@@ -47,8 +58,13 @@ def main():
     ap.add_argument("--lib")
     ap.add_argument("--create-only", action="store_true")
     ap.add_argument("--probes", type=int, default=0)
+    ap.add_argument("--ranks", type=int, default=0)
+    ap.add_argument("--mask", type=lambda x: int(x, 0), default=0)
     ap.add_argument("--out")
     a = ap.parse_args()
+    multi = bool(a.ranks or a.mask)
+    if a.ranks and a.mask:
+        ap.error("--ranks (virtual ranks on device 0) and --mask (real devices) exclude each other")
 
     import torch  # first: one HIP runtime per process
     from voxelraytrace20190722_amd import _ffi
@@ -86,13 +102,25 @@ def main():
     doc = {"scene": "sponza-proxy", "detail": a.detail, "triangles": int(sd.ntri), "reps": a.reps,
            "probes": 0 if probes is None else int(len(probes[0])),
            "library": vrt.build_id(), "device": torch.cuda.get_device_name(0), "depths": {}}
+    if multi:
+        doc["ranks"] = a.ranks if a.ranks else bin(a.mask).count("1")
+        doc["virtual_ranks"] = bool(a.ranks)
 
     def make(k, depth):
+        if multi:
+            return vrt.MultiOctree(scenes[k], depth, device_mask=a.mask or 1, build_on_device=True,
+                                   virtual_ranks=a.ranks or None, probes=None if probes is None else probes[k])
         return vrt.VoxelOctree(scenes[k], depth, build_on_device=True, probes=None if probes is None else probes[k])
 
-    def timed_update(live, kind, k):
+    def timed_update(live, kind, k, verify=False):
         t0 = time.perf_counter()
-        if probes is not None:
+        if multi:
+            if kind == "host":
+                live.update(places[k], None, None if probes is None else probes[k], verify=verify)
+            else:
+                live.update_device(d_places[k].data_ptr(), None, None if probes is None else d_probes[k].data_ptr(),
+                                   verify=verify)
+        elif probes is not None:
             if kind == "host":
                 live.update_probes(places[k], None, probes[k])
             else:
@@ -102,6 +130,9 @@ def main():
         else:
             live.update_device(d_places[k].data_ptr())
         return dict(live.update_stats(), wall=(time.perf_counter() - t0) * 1e3, placement=k)
+
+    def pinfo(t):
+        return (t.scene(0) if multi else t).probe_info()
 
     for depth in [int(x) for x in a.depths.split(",")]:
         tree = make(0, depth)  # warm-up, not counted
@@ -134,9 +165,9 @@ def main():
             timed_update(live, "host", k ^ 1)
             upd_dev.append(timed_update(live, "device", k))
             assert int(live.info.nodes) == int(tree.info.nodes) and int(live.info.tri_refs) == int(tree.info.tri_refs)
-            assert live.probe_info() == tree.probe_info()
+            assert pinfo(live) == pinfo(tree)
         row = {"nodes": int(tree.info.nodes), "tri_refs": int(tree.info.tri_refs),
-               "probe_leaves": int(tree.probe_info()[1]), "probe_refs": int(tree.probe_info()[2]),
+               "probe_leaves": int(pinfo(tree)[1]), "probe_refs": int(pinfo(tree)[2]),
                "create": min(create, key=lambda r: r["total"])}
         if not a.create_only:
             row["update_first"] = first
@@ -146,7 +177,22 @@ def main():
             row["moved"] = {"create": min(r["total"] for r in create if r["placement"] == 1),
                             "update": min(r["wall"] for r in upd if r["placement"] == 1),
                             "update_device": min(r["wall"] for r in upd_dev if r["placement"] == 1)}
-            row["update_scratch_bytes"] = int(live.update_scratch())
+            if multi:
+                # the replica check: one more update of each kind with the flag
+                row["verify"] = {"update": timed_update(live, "host", 1, verify=True),
+                                 "update_device": timed_update(live, "device", 0, verify=True)}
+                row["update_scratch_bytes"] = int(live.scene(0).update_scratch())
+            elif "vrt_scene_digest" not in _ffi.SIGNATURES:  # an older library
+                row["update_scratch_bytes"] = int(live.update_scratch())
+            else:
+                walls = []
+                for _ in range(5):
+                    t0 = time.perf_counter()
+                    live.digest()
+                    walls.append((time.perf_counter() - t0) * 1e3)
+                nb = sum(int(live.device_array(kk).size) for kk in range(5 if probes is None else 8))
+                row["digest"] = {"wall_ms": min(walls), "bytes": nb + int(live.info.nodes) * 36}
+                row["update_scratch_bytes"] = int(live.update_scratch())
             row["device_bytes"] = int(live.info.device_bytes)
             row["rounds"] = {"create": create, "update": upd, "update_device": upd_dev}
             live.close()

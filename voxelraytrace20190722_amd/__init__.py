@@ -14,6 +14,7 @@ from .api import (  # noqa: F401
     unpack_tiles_device, pack_tiles_c_device, unpack_tiles_c_device, write_hdr, rgbe_device, write_hdr_device,
     SG, LightProbe, probe_points, probe_eval, PROBE_SGS, PROBE_DIRS, TEST_SMALL_PROBE_CHUNK,
     probe_eval_device, expf_flavour, expf_model, expf_selftest,
+    digest, DIGEST_ITEMS, TEST_MULTI_REFUSE_LAST, TEST_MULTI_DIVERGE,
 )
 
 __all__ = [
@@ -24,5 +25,5 @@ __all__ = [
     "tri_box_overlap", "unpack_tiles_device", "pack_tiles_c_device", "unpack_tiles_c_device", "write_hdr", "ObjModel", "obj2voxel", "load_image",
     "tga_decode", "hdr_bytes_from_rgbe", "rgbe_device", "write_hdr_device", "build_id", "build_flag", "test_flags", "device_selftest_order", "set_test_flags",
     "device_selftest_chain", "SG", "LightProbe", "probe_points", "probe_eval",
-    "probe_eval_device", "expf_flavour", "expf_model", "expf_selftest",
+    "probe_eval_device", "expf_flavour", "expf_model", "expf_selftest", "digest",
 ]

@@ -108,6 +108,8 @@ VRT_MARCH_EVEN_INVISIBLE = 1
 VRT_TEST_UPDATE_TOO_LARGE = 0x80000
 VRT_MULTI_LIGHT_REPLICATED = 0
 VRT_MULTI_LIGHT_SHARDED = 1
+VRT_MULTI_UPDATE_VERIFY = 1
+VRT_DIGEST_ITEMS = 10
 
 _P = C.c_void_p
 SIGNATURES = {
@@ -251,6 +253,12 @@ SIGNATURES = {
                                         C.POINTER(Film), C.c_float, f32p, i64p]),
     "vrt_trace_frame_multi_device": (C.c_int, [_P, C.POINTER(Camera), C.POINTER(Film), f32p, C.POINTER(Camera),
                                                C.POINTER(Film), C.c_float, _P, _P, i64p]),
+    "vrt_multi_update": (C.c_int, [_P, f32p, f32p, C.POINTER(Probe), C.c_int]),
+    "vrt_multi_update_device": (C.c_int, [_P, _P, _P, _P, C.c_int, _P]),
+    "vrt_multi_update_stats": (C.c_int, [_P, f64p]),
+    "vrt_scene_digest": (C.c_int, [_P, C.POINTER(C.c_uint64)]),
+    "vrt_digest_host": (C.c_int, [_P, C.c_int64, C.POINTER(C.c_uint64)]),
+    "vrt_device_selftest_digest": (C.c_int, [C.c_int, _P, C.c_int64, C.c_int, C.POINTER(C.c_uint64)]),
     "vrt_render_secondary_multi": (C.c_int, [_P, C.POINTER(Camera), C.POINTER(Film), C.c_int, f32p, i64p]),
     "vrt_render_secondary_multi_device": (C.c_int, [_P, C.POINTER(Camera), C.POINTER(Film), C.c_int, _P, _P]),
     "vrt_status_string": (C.c_char_p, [C.c_int]),

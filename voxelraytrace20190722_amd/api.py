@@ -460,6 +460,14 @@ class VoxelOctree:
                                            C.byref(nb)), "vrt_scene_device_array")
         return out
 
+    def digest(self):
+        """The ten digest words of the arrays an update rewrites
+        (vrt_scene_digest): items 0-7 are device_array's kinds (an absent
+        array digests to 0), 8 the node records, 9 the nodes' voxel indices."""
+        out = np.zeros(DIGEST_ITEMS, np.uint64)
+        check(lib().vrt_scene_digest(self.h, out.ctypes.data_as(C.POINTER(C.c_uint64))), "vrt_scene_digest")
+        return out
+
     def leaves(self):
         """(voxel ids, counts, concatenated triangle lists) of the non-empty leaves."""
         nl, nr = self.info.nonempty_leaves, self.info.tri_refs
@@ -982,6 +990,59 @@ class MultiOctree:
                                                       C.c_void_p(stream_ptr) if stream_ptr else None),
               "vrt_render_secondary_multi_device")
 
+    # ---- moving geometry ----
+    def _update_done(self, probes):
+        if probes is not None:
+            self.probes = probes
+        s0 = C.c_void_p()
+        check(lib().vrt_multi_scene(self.h, 0, C.byref(s0)), "vrt_multi_scene")
+        check(lib().vrt_scene_info(s0, C.byref(self.info)), "vrt_scene_info")
+
+    def update(self, pos, nrm=None, probes=None, verify=False):
+        """Rebuild every rank's scene in place from new vertex positions
+        (ntri*9 floats), unless nrm is None new normals, and on a probe handle
+        unless probes is None new probes (vrt_multi_update).  All ranks or
+        none: a refusal raises and leaves every rank on its previous geometry.
+        verify: compare the ranks' digests afterwards."""
+        pos = np.ascontiguousarray(pos, np.float32).reshape(-1)
+        n9 = 9 * self.scene_data.ntri
+        if pos.size != n9:
+            raise ValueError(f"pos has {pos.size} floats, the scene needs {n9}")
+        if nrm is not None:
+            nrm = np.ascontiguousarray(nrm, np.float32).reshape(-1)
+            if nrm.size != n9:
+                raise ValueError(f"nrm has {nrm.size} floats, the scene needs {n9}")
+        pp = None
+        if probes is not None:
+            probes = _probes_arg(probes)
+            have = 0 if self.probes is None else len(self.probes)
+            if probes is None:
+                raise ValueError("probes is empty")
+            if have and len(probes) != have:
+                raise ValueError(f"probes has {len(probes)} records, the handle has {have}")
+            pp = probes.ctypes.data_as(C.POINTER(_ffi.Probe))
+        check(lib().vrt_multi_update(self.h, ptr(pos, _ffi.f32p), ptr(nrm, _ffi.f32p), pp,
+                                     _ffi.VRT_MULTI_UPDATE_VERIFY if verify else 0), "vrt_multi_update")
+        self._update_done(probes)
+
+    def update_device(self, d_pos_ptr, d_nrm_ptr=None, d_probes_ptr=None, stream_ptr=None, verify=False):
+        """update() from arrays on the first device, read in the order of
+        stream_ptr (vrt_multi_update_device); every rank is ready on return."""
+        check(lib().vrt_multi_update_device(self.h, C.c_void_p(d_pos_ptr),
+                                            C.c_void_p(d_nrm_ptr) if d_nrm_ptr else None,
+                                            C.c_void_p(d_probes_ptr) if d_probes_ptr else None,
+                                            _ffi.VRT_MULTI_UPDATE_VERIFY if verify else 0,
+                                            C.c_void_p(stream_ptr) if stream_ptr else None),
+              "vrt_multi_update_device")
+        self._update_done(self.scene(0).device_array(7).view(np.float32).reshape(-1, 4).copy()
+                          if d_probes_ptr else None)
+
+    def update_stats(self):
+        """The last update's wall-clock split in ms (vrt_multi_update_stats)."""
+        ms = np.zeros(4, np.float64)
+        check(lib().vrt_multi_update_stats(self.h, ptr(ms, _ffi.f64p)), "vrt_multi_update_stats")
+        return dict(total=ms[0], slowest_rank=ms[1], distribute=ms[2], verify=ms[3])
+
     # ---- trace() frames (light pass + filter + cone-traced view) ----
     LIGHT_MODES = {"replicated": _ffi.VRT_MULTI_LIGHT_REPLICATED, "sharded": _ffi.VRT_MULTI_LIGHT_SHARDED}
 
@@ -1443,6 +1504,26 @@ def device_selftest_chain(cases, device=0):
     return out
 
 
+DIGEST_ITEMS = 10  # include/vrt.h VRT_DIGEST_ITEMS
+
+
+def digest(data, device=None, misalign=0):
+    """The digest of include/vrt.h over `data`'s bytes (a whole number of
+    32-bit words): the host statement (device None, vrt_digest_host) or the
+    kernel's own code on `device`, from a 16-byte-aligned buffer + misalign
+    (vrt_device_selftest_digest)."""
+    a = np.ascontiguousarray(data)
+    b = a.view(np.uint8).reshape(-1) if a.size else np.zeros(0, np.uint8)
+    out = C.c_uint64()
+    p = b.ctypes.data_as(C.c_void_p) if b.size else None
+    if device is None:
+        check(lib().vrt_digest_host(p, b.size, C.byref(out)), "vrt_digest_host")
+    else:
+        check(lib().vrt_device_selftest_digest(int(device), p, b.size, int(misalign), C.byref(out)),
+              "vrt_device_selftest_digest")
+    return out.value
+
+
 def build_id():
     """Source hash libvrt.so was built from (tools/build_id.py)."""
     return lib().vrt_build_id().decode()
@@ -1469,6 +1550,8 @@ TEST_SMALL_BATCH_CHUNK = 0x10000  # include/vrt.h VRT_TEST_SMALL_BATCH_CHUNK
 TEST_SMALL_PROBE_CHUNK = 0x20000  # include/vrt.h VRT_TEST_SMALL_PROBE_CHUNK
 TEST_SMALL_BEAM_ENTRY = 0x40000  # include/vrt.h VRT_TEST_SMALL_BEAM_ENTRY
 TEST_UPDATE_TOO_LARGE = 0x80000  # include/vrt.h VRT_TEST_UPDATE_TOO_LARGE
+TEST_MULTI_REFUSE_LAST = 0x100000  # include/vrt.h VRT_TEST_MULTI_REFUSE_LAST
+TEST_MULTI_DIVERGE = 0x200000  # include/vrt.h VRT_TEST_MULTI_DIVERGE
 
 
 def set_test_flags(flags):

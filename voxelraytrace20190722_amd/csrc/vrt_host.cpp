@@ -455,6 +455,7 @@ struct vrt_scene {
         std::vector<uint32_t> up_pref;
         std::vector<vrt_probe> up_probes;
         Event up_in, up_e0, up_e1;
+        GrowMem digest;  // vrt_scene_digest: the ten words (80 B), made on first use
         double up_ms[4] = {};
         bool updated = false;
         bool owned = false;
@@ -1531,6 +1532,10 @@ extern "C" int vrt_build_flag(const char *name, int64_t *value)
 {
         if (!name || !value)
                 return fail(VRT_E_INVALID, "null argument");
+        if (std::strcmp(name, "VRT_DIGEST_PASS_WORDS") == 0) {  // vrt_digest.hip
+                *value = digest_pass_words();
+                return VRT_OK;
+        }
         if (!build_flag(name, value))
                 return fail(VRT_E_INVALID, "unknown build flag %s", name);
         return VRT_OK;
@@ -4336,7 +4341,9 @@ extern "C" int vrt_device_selftest_order(int device, const float *dist, const ui
 // ---------------------------------------------------------------------------
 // probe_call: vrt_scene_update_probes[_device], which takes the scenes with
 // light probes that vrt_scene_update refuses, and no others
-static int update_args_ok(vrt_scene *s, const float *pos, const char *what, bool probe_call = false)
+// for_handle: the call is vrt_multi_update's, which moves every rank alike
+static int update_args_ok(vrt_scene *s, const float *pos, const char *what, bool probe_call = false,
+                          bool for_handle = false)
 {
         if (!s || !pos)
                 return fail(VRT_E_INVALID, "%s: null argument", what);
@@ -4345,7 +4352,7 @@ static int update_args_ok(vrt_scene *s, const float *pos, const char *what, bool
         if (!probe_call)
                 if (int rc = no_probe_scene(s, what))
                         return rc;
-        if (s->owned)
+        if (s->owned && !for_handle)
                 return fail(VRT_E_INVALID, "%s: the scene is a rank of a vrt_multi handle, whose ranks must stay replicas",
                             what);
         if ((uint32_t)s->ntri > 0x55555555u)
@@ -4442,10 +4449,16 @@ static hipError_t fetch(void *dst, const void *src, size_t bytes, hipStream_t st
 // probe scene (vrt_scene_update_probes; probes == nullptr: they stay) adds the
 // probes' faces to the root box, the probe frontier to the build, and pnode /
 // pref / the probes to what is swapped in and copied back.
-static int update_device(vrt_scene *s, const float *pos, const float *nrm, const vrt_probe *probes, bool on_device,
-                         hipStream_t cst)
+//
+// The update's first half: everything that can refuse.  It writes only the
+// scene's BuildScratch and memory the scene does not read yet (plan->grown,
+// the spare host mirrors), so that a plan which is dropped leaves the scene
+// as it was.
+int vrt::update_prepare(vrt_scene *s, const float *pos, const float *nrm, const vrt_probe *probes, bool on_device,
+                        hipStream_t cst, bool fail_limit, UpdatePlan *plan)
 {
-        const double t0 = now_ms();
+        UpdatePlan &pl = *plan;
+        pl.t0 = now_ms();
         // Wait for all work the scene has in flight.  Not every launch leaves
         // an event to wait for: a grid-kind render (every 64-B-record scene)
         // and the device ray-march batches run on the caller's stream and
@@ -4496,10 +4509,14 @@ static int update_device(vrt_scene *s, const float *pos, const float *nrm, const
                 }
         }
         const bool new_probes = np && probes;
+        pl.d_pos = d_pos;
+        pl.d_nrm = d_nrm;
+        pl.d_probes = d_probes;
+        pl.new_probes = new_probes;
         HIPCHK(hipEventRecord(s->up_e0, st));
         // root box: 6 keys, then the 6 floats the host needs for info and, on a
         // probe scene, the index of the first probe creation would refuse
-        float root[7];
+        float *const root = pl.root;
         uint32_t bad_probe = 0xFFFFFFFFu;
         HIPCHK(sc.root.need(128));
         HIPCHK(launch_root_box(d_pos, n, d_probes, np, sc.root.as<uint64_t>(), sc.root.as<float>() + 12, st));
@@ -4509,10 +4526,9 @@ static int update_device(vrt_scene *s, const float *pos, const float *nrm, const
                 std::memcpy(&bad_probe, &root[6], sizeof bad_probe);
         if (new_probes && bad_probe != 0xFFFFFFFFu)
                 return fail(VRT_E_INVALID, "probe %u: centre must be finite, radius finite and >= 0", bad_probe);
-        DeviceTree tree;
+        DeviceTree &tree = pl.tree;
         try {
                 std::string err;
-                const bool fail_limit = (test_flags() & VRT_TEST_UPDATE_TOO_LARGE) != 0;
                 if (build_frontier_device(sc, d_pos, n, root, root + 3, s->max_depth, d_probes, np, st, fail_limit,
                                           &tree, &err) != hipSuccess) {
                         (void)hipGetLastError();
@@ -4527,10 +4543,10 @@ static int update_device(vrt_scene *s, const float *pos, const float *nrm, const
                 return fail(VRT_E_NOMEM, "scene update: out of host memory");
         }
         const int64_t nn = tree.nnodes, nr = tree.nrefs;
-        unsigned int counts[2] = {};
+        unsigned int *const counts = pl.counts;
         HIPCHK(sc.counts.need(16));
         HIPCHK(launch_leaf_counts(tree.nodes, nn, sc.counts.as<unsigned int>(), st));
-        HIPCHK(fetch(counts, sc.counts, sizeof counts, st));
+        HIPCHK(fetch(counts, sc.counts, sizeof pl.counts, st));
         HIPCHK(hipStreamSynchronize(st));
         // the choices upload() makes, on the new geometry
         const bool wide = (size_t)nr >= 8 * (size_t)std::max<int64_t>(1, (int64_t)counts[1]);
@@ -4547,7 +4563,7 @@ static int update_device(vrt_scene *s, const float *pos, const float *nrm, const
         // a probe scene's pnode (one per node) and pref (one per probe
         // reference) as upload() sizes them; nothing on any other scene
         const int64_t npr = tree.nprefs;
-        constexpr int kOwners = 6;
+        constexpr int kOwners = UpdatePlan::kOwners;
         const size_t want[kOwners] = { align_up((size_t)nn * sizeof(NodeRec)), align_up((size_t)nn * sizeof(uint32_t)),
                                        align_up(sz_rbox + std::max<size_t>(64, refs_bytes)),
                                        align_up((size_t)nn * sizeof(XNodeRec)),
@@ -4556,7 +4572,7 @@ static int update_device(vrt_scene *s, const float *pos, const float *nrm, const
         // larger arrays are made beside the ones in use and swapped in only
         // when all of them exist
         DevMem *const own[kOwners] = { &s->g_nodes, &s->g_vox, &s->g_refs, &s->g_xnodes, &s->g_pnode, &s->g_pref };
-        DevMem grown[kOwners];
+        DevMem *const grown = pl.grown;
         std::vector<NodeRec> &h_nodes = s->up_nodes;
         std::vector<uint32_t> &h_vox = s->up_vox, &h_reftri = s->up_ref_tri;
         for (int i = 0; i < kOwners; ++i)
@@ -4582,6 +4598,40 @@ static int update_device(vrt_scene *s, const float *pos, const float *nrm, const
         } catch (const std::bad_alloc &) {
                 return fail(VRT_E_NOMEM, "scene update: out of host memory");
         }
+        pl.wide = wide;
+        pl.fast = fast;
+        pl.lb_on = lb_on;
+        pl.rboxes = rboxes;
+        pl.ext = ext;
+        pl.sz_rbox = sz_rbox;
+        return VRT_OK;
+}
+
+// The update's second half.
+int vrt::update_commit(vrt_scene *s, UpdatePlan *plan)
+{
+        UpdatePlan &pl = *plan;
+        constexpr int kOwners = UpdatePlan::kOwners;
+        hipStream_t st = s->stream;
+        BuildScratch &sc = s->bscratch;
+        const int n = s->ntri;
+        const int np = (int)s->probes.size();
+        const float *const d_pos = pl.d_pos, *const d_nrm = pl.d_nrm;
+        const float4 *const d_probes = pl.d_probes;
+        const bool new_probes = pl.new_probes;
+        const float *const root = pl.root;
+        DeviceTree &tree = pl.tree;
+        const int64_t nn = tree.nnodes, nr = tree.nrefs, npr = tree.nprefs;
+        const unsigned int *const counts = pl.counts;
+        const bool wide = pl.wide, fast = pl.fast, lb_on = pl.lb_on, rboxes = pl.rboxes;
+        const float ext = pl.ext;
+        const size_t sz_rbox = pl.sz_rbox;
+        const double t0 = pl.t0;
+        DevMem *const own[kOwners] = { &s->g_nodes, &s->g_vox, &s->g_refs, &s->g_xnodes, &s->g_pnode, &s->g_pref };
+        DevMem *const grown = pl.grown;
+        std::vector<NodeRec> &h_nodes = s->up_nodes;
+        std::vector<uint32_t> &h_vox = s->up_vox, &h_reftri = s->up_ref_tri;
+        HIPCHK(hipSetDevice(s->device));
         // ---- nothing below refuses: the scene's arrays are written from here
         // on.  The device pointers follow their owners at once, so that no
         // later error return leaves one on released memory (after a
@@ -4746,6 +4796,88 @@ static int update_device(vrt_scene *s, const float *pos, const float *nrm, const
         return VRT_OK;
 }
 
+// the single-scene entry points: the two halves back to back
+static int update_device(vrt_scene *s, const float *pos, const float *nrm, const vrt_probe *probes, bool on_device,
+                         hipStream_t cst)
+{
+        UpdatePlan plan;
+        if (int rc = update_prepare(s, pos, nrm, probes, on_device, cst,
+                                    (test_flags() & VRT_TEST_UPDATE_TOO_LARGE) != 0, &plan))
+                return rc;
+        return update_commit(s, &plan);
+}
+
+int vrt::update_probes_ok(const vrt_probe *probes, size_t n)
+{
+        for (size_t k = 0; k < n; ++k) {
+                const vrt_probe &pb = probes[k];
+                if (!std::isfinite(pb.o[0]) || !std::isfinite(pb.o[1]) || !std::isfinite(pb.o[2]) ||
+                    !std::isfinite(pb.r) || pb.r < 0.f)
+                        return fail(VRT_E_INVALID, "probe %zu: centre must be finite, radius finite and >= 0", k);
+        }
+        return VRT_OK;
+}
+
+// A rank scene of a vrt_multi handle, checked once for the handle's update:
+// update_args_ok without the refusal of an owned scene, which is the handle's
+// own to lift.
+int vrt::update_multi_args_ok(vrt_scene *s, const float *pos, bool has_probes, const char *what)
+{
+        if (has_probes && s->probes.empty())
+                return fail(VRT_E_INVALID, "%s: the handle has no light probes", what);
+        return update_args_ok(s, pos, what, !s->probes.empty(), true);
+}
+
+int vrt::update_stage(vrt_scene *s, bool nrm, bool probes, float **d_pos, float **d_nrm, vrt_probe **d_probes,
+                      size_t bytes[3])
+{
+        BuildScratch &sc = s->bscratch;
+        bytes[0] = (size_t)s->ntri * 36;
+        bytes[1] = nrm ? bytes[0] : 0;
+        bytes[2] = probes ? s->probes.size() * sizeof(vrt_probe) : 0;
+        // the scratch's last user (the previous update) returned with its work done
+        HIPCHK(hipSetDevice(s->device));
+        HIPCHK(sc.pos.need(bytes[0]));
+        *d_pos = sc.pos.as<float>();
+        *d_nrm = nullptr;
+        *d_probes = nullptr;
+        if (nrm) {
+                HIPCHK(sc.nrm.need(bytes[1]));
+                *d_nrm = sc.nrm.as<float>();
+        }
+        if (probes) {
+                HIPCHK(sc.probes.need(bytes[2]));
+                *d_probes = sc.probes.as<vrt_probe>();
+        }
+        return VRT_OK;
+}
+
+std::mutex &vrt::scene_mutex(vrt_scene *s) { return s->mu; }
+
+void vrt::scene_replica_key(const vrt_scene *s, int *wide, float wmin[3])
+{
+        *wide = s->wide_leaves ? 1 : 0;
+        for (int k = 0; k < 3; ++k)
+                wmin[k] = s->ord_wmin[k];
+}
+
+int vrt::scene_device(const vrt_scene *s) { return s->device; }
+
+size_t vrt::scene_nprobe(const vrt_scene *s) { return s->probes.size(); }
+
+int vrt::scene_test_flip_attr(vrt_scene *s)
+{
+        if (s->ntri < 1)
+                return VRT_OK;
+        std::lock_guard<std::mutex> lk(s->mu);
+        HIPCHK(hipSetDevice(s->device));
+        uint32_t w = 0;
+        HIPCHK(hipMemcpy(&w, s->dev.tri_attr, sizeof w, hipMemcpyDeviceToHost));
+        w ^= 1u;
+        HIPCHK(hipMemcpy(const_cast<TriAttr *>(s->dev.tri_attr), &w, sizeof w, hipMemcpyHostToDevice));
+        return VRT_OK;
+}
+
 extern "C" int vrt_scene_update(vrt_scene *s, const float *pos, const float *nrm)
 {
         if (int rc = update_args_ok(s, pos, "vrt_scene_update"))
@@ -4773,12 +4905,8 @@ extern "C" int vrt_scene_update_probes(vrt_scene *s, const float *pos, const flo
         std::lock_guard<std::mutex> lk(s->mu);
         // as at creation; the device variant's check is the root-box kernel's
         if (probes)
-                for (size_t k = 0; k < s->probes.size(); ++k) {
-                        const vrt_probe &pb = probes[k];
-                        if (!std::isfinite(pb.o[0]) || !std::isfinite(pb.o[1]) || !std::isfinite(pb.o[2]) ||
-                            !std::isfinite(pb.r) || pb.r < 0.f)
-                                return fail(VRT_E_INVALID, "probe %zu: centre must be finite, radius finite and >= 0", k);
-                }
+                if (int rc = update_probes_ok(probes, s->probes.size()))
+                        return rc;
         if (!s->d_mem)
                 return update_host(s, pos, nrm, probes);
         return update_device(s, pos, nrm, probes, false, nullptr);
@@ -4882,5 +5010,106 @@ extern "C" int vrt_scene_device_array(vrt_scene *s, int kind, void *out, int64_t
         HIPCHK(hipSetDevice(s->device));
         if (n)
                 HIPCHK(hipMemcpy(out, src, n, hipMemcpyDeviceToHost));
+        return VRT_OK;
+}
+
+// ---- scene digest (vrt_digest.hip) -----------------------------------------
+static uint64_t digest_words(const unsigned char *b, uint64_t W)
+{
+        uint64_t sum = 0;
+        for (uint64_t i = 0; i < W; ++i) {
+                const uint32_t w = (uint32_t)b[4 * i] | (uint32_t)b[4 * i + 1] << 8 | (uint32_t)b[4 * i + 2] << 16 |
+                                   (uint32_t)b[4 * i + 3] << 24;
+                uint64_t z = ((i + 1) * 0x9E3779B97F4A7C15ull) ^ (uint64_t)w;
+                z ^= z >> 30;
+                z *= 0xBF58476D1CE4E5B9ull;
+                z ^= z >> 27;
+                z *= 0x94D049BB133111EBull;
+                z ^= z >> 31;
+                sum += z;
+        }
+        return sum;
+}
+
+extern "C" int vrt_digest_host(const void *bytes, int64_t nbytes, uint64_t *out)
+{
+        if (!out || nbytes < 0 || (nbytes > 0 && !bytes))
+                return fail(VRT_E_INVALID, "vrt_digest_host: null argument or negative size");
+        if (nbytes % 4)
+                return fail(VRT_E_INVALID, "vrt_digest_host: %lld bytes are no whole number of 32-bit words",
+                            (long long)nbytes);
+        *out = digest_words(static_cast<const unsigned char *>(bytes), (uint64_t)nbytes / 4);
+        return VRT_OK;
+}
+
+extern "C" int vrt_device_selftest_digest(int device, const void *bytes, int64_t nbytes, int misalign, uint64_t *out)
+{
+        if (device < 0)
+                return vrt_digest_host(bytes, nbytes, out);
+        if (!out || nbytes < 0 || (nbytes > 0 && !bytes))
+                return fail(VRT_E_INVALID, "vrt_device_selftest_digest: null argument or negative size");
+        if (nbytes % 4)
+                return fail(VRT_E_INVALID, "vrt_device_selftest_digest: %lld bytes are no whole number of 32-bit words",
+                            (long long)nbytes);
+        if (misalign != 0 && misalign != 4 && misalign != 8 && misalign != 12)
+                return fail(VRT_E_INVALID, "vrt_device_selftest_digest: misalign %d (0, 4, 8 or 12)", misalign);
+        if (int rc = check_device(device))
+                return rc;
+        HIPCHK(hipSetDevice(device));
+        DevMem buf, d_out;
+        HIPCHK(buf.alloc((size_t)nbytes + 32));
+        HIPCHK(d_out.alloc(sizeof(uint64_t)));
+        if (nbytes)
+                HIPCHK(hipMemcpy(buf.as<char>() + misalign, bytes, (size_t)nbytes, hipMemcpyHostToDevice));
+        DigestItems it{};
+        it.n = 1;
+        it.p[0] = buf.as<char>() + misalign;
+        it.bytes[0] = nbytes;
+        HIPCHK(launch_digest(it, d_out.as<uint64_t>(), nullptr));
+        HIPCHK(hipMemcpy(out, d_out, sizeof(uint64_t), hipMemcpyDeviceToHost));
+        return VRT_OK;
+}
+
+extern "C" int vrt_scene_digest(vrt_scene *s, uint64_t out[VRT_DIGEST_ITEMS])
+{
+        if (s && need_device(s))
+                return VRT_E_NODEVICE;
+        if (!s || !out)
+                return fail(VRT_E_INVALID, "null argument");
+        static_assert(VRT_DIGEST_ITEMS == kDigestItems, "digest items");
+        std::lock_guard<std::mutex> lk(s->mu);
+        const size_t nr = s->ref_tri.size(), nn = s->nodes.size();
+        const size_t nbox = s->rboxes ? nr * sizeof(RefBox) : 0;
+        DigestItems it{};
+        it.n = kDigestItems;
+        const void *p[kDigestItems] = { s->dev.refs,
+                                        static_cast<const char *>(s->dev.refs) - nbox,
+                                        s->dev.xnodes,
+                                        s->dev.tri_pos,
+                                        s->dev.tri_attr,
+                                        s->pdev.pnode,
+                                        s->pdev.pref,
+                                        s->pdev.probes,
+                                        s->dev.nodes,
+                                        s->dev.node_vox };
+        const size_t bytes[kDigestItems] = { nr * (s->wide_leaves ? sizeof(RefRec64) : sizeof(RefRec48)),
+                                             nbox,
+                                             nn * sizeof(XNodeRec),
+                                             (size_t)s->ntri * sizeof(TriPos),
+                                             (size_t)s->ntri * sizeof(TriAttr),
+                                             s->probes.empty() ? 0 : s->pnode.size() * sizeof(uint2),
+                                             s->probes.empty() ? 0 : s->pref.size() * sizeof(uint32_t),
+                                             s->probes.size() * sizeof(vrt_probe),
+                                             nn * sizeof(NodeRec),
+                                             nn * sizeof(uint32_t) };
+        for (int k = 0; k < kDigestItems; ++k) {
+                it.p[k] = bytes[k] ? p[k] : nullptr;
+                it.bytes[k] = (int64_t)bytes[k];
+        }
+        HIPCHK(hipSetDevice(s->device));
+        HIPCHK(s->digest.need(kDigestItems * sizeof(uint64_t)));
+        HIPCHK(launch_digest(it, s->digest.as<uint64_t>(), s->stream));
+        HIPCHK(hipMemcpyAsync(out, s->digest, kDigestItems * sizeof(uint64_t), hipMemcpyDeviceToHost, s->stream));
+        HIPCHK(hipStreamSynchronize(s->stream));
         return VRT_OK;
 }

@@ -5,6 +5,7 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include <mutex>
 #include <string>
 #include <vector>
 
@@ -880,6 +881,61 @@ struct FinishArgs {
 hipError_t launch_finish(const FinishArgs &a, hipStream_t st);
 // the ordered key of launch_finish's chain minima back to the double
 double chain_key_value(uint64_t key);
+
+// A device scene's update in two halves (vrt_host.cpp), so that a vrt_multi
+// handle can have every rank refuse before any rank writes.  update_prepare
+// is everything that can refuse: it writes only the scene's BuildScratch and
+// memory the scene does not read yet, and fills the plan.  update_commit is
+// the rest; only a failed launch or copy stops it (VRT_E_DEVICE, the scene's
+// contents then undefined).  A plan that is not committed is abandoned by
+// destroying it: its grown[] arrays are released and the scene is as it was.
+struct UpdatePlan {
+        static constexpr int kOwners = 6;  // nodes, node_vox, refs, xnodes, pnode, pref
+        double t0 = 0;
+        const float *d_pos = nullptr, *d_nrm = nullptr;
+        const float4 *d_probes = nullptr;
+        bool new_probes = false;
+        float root[7] = {};
+        DeviceTree tree;
+        unsigned int counts[2] = {};
+        bool wide = false, fast = false, lb_on = false, rboxes = false;
+        float ext = 0.f;
+        size_t sz_rbox = 0;
+        DevMem grown[kOwners];  // larger arrays made beside the ones in use
+};
+// pos / nrm / probes as update_device's; fail_limit: VRT_TEST_UPDATE_TOO_LARGE
+// for this scene.  The caller holds the scene's mutex over both halves.
+int update_prepare(vrt_scene *s, const float *pos, const float *nrm, const vrt_probe *probes, bool on_device,
+                   hipStream_t cst, bool fail_limit, UpdatePlan *plan);
+int update_commit(vrt_scene *s, UpdatePlan *plan);
+// what vrt_scene_update_probes checks of host probes; the scene's argument
+// checks for a rank of a handle (where the owned refusal does not apply)
+int update_probes_ok(const vrt_probe *probes, size_t n);
+int update_multi_args_ok(vrt_scene *s, const float *pos, bool has_probes, const char *what);
+// Room in the scene's BuildScratch for positions, and when asked normals and
+// probes, arriving from another device: the staging a host array's upload
+// would use.  bytes: the three byte counts (0: not asked for).
+int update_stage(vrt_scene *s, bool nrm, bool probes, float **d_pos, float **d_nrm, vrt_probe **d_probes,
+                 size_t bytes[3]);
+// the scene's mutex (vrt_multi_update holds every rank's over both halves)
+std::mutex &scene_mutex(vrt_scene *s);
+// what a replica must share beyond its arrays: record format, chain spacing
+void scene_replica_key(const vrt_scene *s, int *wide, float wmin[3]);
+int scene_device(const vrt_scene *s);
+size_t scene_nprobe(const vrt_scene *s);
+// VRT_TEST_MULTI_DIVERGE: flip the lowest bit of the first float of TriAttr
+int scene_test_flip_attr(vrt_scene *s);
+
+// The digest of vrt.h (vrt_build.hip).  One launch for all items (blockIdx.y):
+// out[i] += digest of item i; out is zeroed on st first.
+constexpr int kDigestItems = 10;
+struct DigestItems {
+        const void *p[kDigestItems];
+        int64_t bytes[kDigestItems];  // multiples of 4; 0 = absent
+        int n;
+};
+hipError_t launch_digest(const DigestItems &it, uint64_t *out, hipStream_t st);
+int64_t digest_pass_words();
 
 // Kernel launchers (vrt_kernels.hip)
 // Which primary-render kernel launch_render runs: the one-wave grid

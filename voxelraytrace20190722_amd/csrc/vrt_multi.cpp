@@ -16,6 +16,8 @@
 #include <rccl/rccl.h>
 
 #include <algorithm>
+#include <array>
+#include <chrono>
 #include <cstring>
 #include <functional>
 #include <memory>
@@ -44,6 +46,11 @@ struct vrt_multi {
         Event ev_in;                    // caller's stream -> rank 0's stream
         int light_mode = VRT_MULTI_LIGHT_REPLICATED;  // vrt_multi_set_light_mode
         std::vector<Event> ev_x;        // virtual ranks, sharded light pass: rank i has read the others' hit lists
+        // vrt_multi_update: the distribution's events on st[0] (made by the first
+        // device update) and the last update's {total, slowest rank, distribute, verify} ms
+        Event up_d0, up_d1;
+        double up_ms[4] = {};
+        bool updated = false;
         std::mutex mu;
 };
 
@@ -504,6 +511,250 @@ int render_trace_multi(vrt_multi *m, const char *what, const vrt_camera *cam, co
         });
 }
 
+// ---- vrt_multi_update ------------------------------------------------------
+double now_ms()
+{
+        using namespace std::chrono;
+        return duration<double, std::milli>(steady_clock::now().time_since_epoch()).count();
+}
+
+// f(rank) for every rank on a host thread of its own (rank 0 on the caller's),
+// each with its status and its thread's vrt_last_error()
+void for_ranks(int n, std::vector<int> &rcs, std::vector<std::string> &errs, const std::function<int(int)> &f)
+{
+        rcs.assign(n, VRT_OK);
+        errs.assign(n, std::string());
+        auto run = [&](int i) {
+                rcs[i] = f(i);
+                if (rcs[i])
+                        errs[i] = vrt_last_error();
+        };
+        std::vector<std::thread> th;
+        for (int i = 1; i < n; ++i)
+                th.emplace_back(run, i);
+        run(0);
+        for (auto &t : th)
+                t.join();
+}
+
+// The caller's device arrays (rank 0's device, complete once st[0] reaches this
+// point) into the staging of every rank >= 1, on the ranks' handle streams;
+// timed by up_d0 / up_d1 on st[0].  src / dst[i] / bytes: positions, normals,
+// probes (bytes 0: not passed).
+int distribute(vrt_multi *m, const void *const src[3], const std::vector<std::array<void *, 3>> &dst,
+               const size_t bytes[3])
+{
+        const int n = (int)m->devs.size();
+        HIPCHK(hipSetDevice(m->devs[0]));
+        HIPCHK(hipEventRecord(m->up_d0, m->st[0]));
+        if (m->virt) {
+                // as gather() orders its copies: rank i's stream waits for rank
+                // 0's, copies, and rank 0's stream waits for every copy
+                HIPCHK(hipEventRecord(m->ev[0], m->st[0]));
+                for (int i = 1; i < n; ++i)
+                        HIPCHK(hipStreamWaitEvent(m->st[i], m->ev[0], 0));
+                for (int i = 1; i < n; ++i) {
+                        for (int k = 0; k < 3; ++k)
+                                if (bytes[k])
+                                        HIPCHK(hipMemcpyAsync(dst[i][k], src[k], bytes[k], hipMemcpyDeviceToDevice,
+                                                              m->st[i]));
+                        HIPCHK(hipEventRecord(m->ev[i], m->st[i]));
+                        HIPCHK(hipStreamWaitEvent(m->st[0], m->ev[i], 0));
+                }
+        } else {
+                // one broadcast of bytes per array from rank 0 (in place there)
+                NCCLCHK(ncclGroupStart());
+                for (int k = 0; k < 3; ++k) {
+                        if (!bytes[k])
+                                continue;
+                        for (int i = 0; i < n; ++i) {
+                                void *buf = i == 0 ? const_cast<void *>(src[k]) : dst[i][k];
+                                const ncclResult_t e = ncclBroadcast(buf, buf, bytes[k], ncclUint8, 0, m->comm[i], m->st[i]);
+                                if (e != ncclSuccess) {
+                                        (void)ncclGroupEnd();
+                                        return set_error(VRT_E_DEVICE, "ncclBroadcast (array %d, rank %d): %s", k, i,
+                                                         ncclGetErrorString(e));
+                                }
+                        }
+                }
+                NCCLCHK(ncclGroupEnd());
+                HIPCHK(hipSetDevice(m->devs[0]));
+        }
+        HIPCHK(hipEventRecord(m->up_d1, m->st[0]));
+        return VRT_OK;
+}
+
+// VRT_MULTI_UPDATE_VERIFY: every rank's digest on its stream, then the ten
+// words and the host-side constants of every rank against rank 0's
+int verify_replicas(vrt_multi *m)
+{
+        static const char *const kItem[VRT_DIGEST_ITEMS] = { "leaf records", "per-record boxes", "xnodes", "TriPos",
+                                                             "TriAttr",      "pnode",            "pref",   "probes",
+                                                             "nodes",        "node_vox" };
+        const int n = (int)m->devs.size();
+        std::vector<std::array<uint64_t, VRT_DIGEST_ITEMS>> dig(n);
+        std::vector<int> rcs;
+        std::vector<std::string> errs;
+        for_ranks(n, rcs, errs, [&](int i) { return vrt_scene_digest(m->sc[i], dig[i].data()); });
+        for (int i = 0; i < n; ++i)
+                if (rcs[i])
+                        return set_error(rcs[i], "verify: rank %d (device %d): %s", i, m->devs[i], errs[i].c_str());
+        vrt_scene_info_t i0{};
+        int w0 = 0;
+        float c0[3];
+        if (int rc = vrt_scene_info(m->sc[0], &i0))
+                return rc;
+        scene_replica_key(m->sc[0], &w0, c0);
+        for (int i = 1; i < n; ++i) {
+                const char *what = nullptr;
+                vrt_scene_info_t ii{};
+                int wi = 0;
+                float ci[3];
+                if (int rc = vrt_scene_info(m->sc[i], &ii))
+                        return rc;
+                scene_replica_key(m->sc[i], &wi, ci);
+                if (ii.nodes != i0.nodes || ii.internal != i0.internal || ii.leaves != i0.leaves ||
+                    ii.nonempty_leaves != i0.nonempty_leaves || ii.tri_refs != i0.tri_refs)
+                        what = "scene counts";
+                else if (wi != w0)
+                        what = "record format";
+                else if (std::memcmp(ii.root_min, i0.root_min, sizeof i0.root_min) ||
+                         std::memcmp(ii.root_max, i0.root_max, sizeof i0.root_max))
+                        what = "root box";
+                else if (std::memcmp(ci, c0, sizeof c0))
+                        what = "chain spacing";
+                for (int k = 0; !what && k < VRT_DIGEST_ITEMS; ++k)
+                        if (dig[i][k] != dig[0][k])
+                                what = kItem[k];
+                if (what)
+                        return set_error(VRT_E_DEVICE, "replicas diverged: rank %d (device %d), %s", i, m->devs[i], what);
+        }
+        return VRT_OK;
+}
+
+int multi_update(vrt_multi *m, const char *what, const float *pos, const float *nrm, const vrt_probe *probes,
+                 int flags, bool on_device, hipStream_t caller)
+{
+        if (!m || !pos)
+                return set_error(VRT_E_INVALID, "%s: null argument", what);
+        if (flags & ~VRT_MULTI_UPDATE_VERIFY)
+                return set_error(VRT_E_INVALID, "%s: unknown flags %#x", what, flags);
+        std::lock_guard<std::mutex> lk(m->mu);
+        DeviceGuard g;
+        const int n = (int)m->devs.size();
+        // the arguments once, as every rank would, before anything is enqueued
+        if (int rc = update_multi_args_ok(m->sc[0], pos, probes != nullptr, what))
+                return rc;
+        if (probes && !on_device)
+                if (int rc = update_probes_ok(probes, scene_nprobe(m->sc[0])))
+                        return rc;
+        const double t0 = now_ms();
+        const int tf = test_flags();
+        // what each rank reads, and the stream that orders it
+        std::vector<const float *> rpos(n, pos), rnrm(n, nrm);
+        std::vector<const vrt_probe *> rprobes(n, probes);
+        std::vector<hipStream_t> rst(n, nullptr);
+        bool distributed = false;
+        std::vector<UpdatePlan> plans(n);
+        std::vector<int> rcs;
+        std::vector<std::string> errs;
+        {
+                // every rank scene is the update's from here to the commit's end
+                std::vector<std::unique_lock<std::mutex>> held;
+                for (vrt_scene *s : m->sc)
+                        held.emplace_back(scene_mutex(s));
+                if (on_device) {
+                        // staging on the other ranks first: an allocation can refuse
+                        std::vector<std::array<void *, 3>> dst(n);
+                        size_t bytes[3] = {};
+                        for (int i = 1; i < n; ++i) {
+                                float *dp = nullptr, *dn = nullptr;
+                                vrt_probe *dq = nullptr;
+                                if (int rc = update_stage(m->sc[i], nrm != nullptr, probes != nullptr, &dp, &dn, &dq, bytes)) {
+                                        const std::string err = vrt_last_error();
+                                        return set_error(rc, "%s: rank %d (device %d): %s", what, i, m->devs[i],
+                                                         err.c_str());
+                                }
+                                dst[i] = { dp, dn, dq };
+                                rpos[i] = dp;
+                                rnrm[i] = dn;
+                                rprobes[i] = dq;
+                        }
+                        HIPCHK(hipSetDevice(m->devs[0]));
+                        if (!m->up_d0) {
+                                HIPCHK(m->up_d0.create());
+                                HIPCHK(m->up_d1.create());
+                        }
+                        // rank 0's stream follows the caller's; every rank then reads
+                        // its arrays in its handle stream's order
+                        HIPCHK(hipEventRecord(m->ev_in, caller));
+                        HIPCHK(hipStreamWaitEvent(m->st[0], m->ev_in, 0));
+                        for (int i = 0; i < n; ++i)
+                                rst[i] = m->st[i];
+                        if (n > 1) {
+                                const void *const src[3] = { pos, nrm, probes };
+                                if (int rc = distribute(m, src, dst, bytes)) {
+                                        held.clear();
+                                        return fail_synced(m, rc);
+                                }
+                                distributed = true;
+                        }
+                }
+                // 1. everything that can refuse, on every rank
+                for_ranks(n, rcs, errs, [&](int i) {
+                        const bool limit = (tf & VRT_TEST_UPDATE_TOO_LARGE) != 0 ||
+                                           ((tf & VRT_TEST_MULTI_REFUSE_LAST) != 0 && i == n - 1);
+                        return update_prepare(m->sc[i], rpos[i], rnrm[i], rprobes[i], on_device, rst[i], limit, &plans[i]);
+                });
+                for (int i = 0; i < n; ++i)
+                        if (rcs[i]) {
+                                // all ranks or none: every plan is abandoned, no rank has
+                                // written an array that a frame reads
+                                plans.clear();
+                                held.clear();
+                                (void)set_error(rcs[i], "%s: rank %d (device %d): %s", what, i, m->devs[i], errs[i].c_str());
+                                return fail_synced(m, rcs[i]);
+                        }
+                // 2. the commit, which only a failed launch or copy can stop
+                for_ranks(n, rcs, errs, [&](int i) { return update_commit(m->sc[i], &plans[i]); });
+                for (int i = 0; i < n; ++i)
+                        if (rcs[i]) {
+                                held.clear();
+                                (void)set_error(rcs[i], "%s: rank %d (device %d) half rebuilt, destroy the handle: %s", what,
+                                                i, m->devs[i], errs[i].c_str());
+                                return fail_synced(m, rcs[i]);
+                        }
+        }
+        if (int rc = sync_all(m))  // the handle's streams: the distribution is over
+                return rc;
+        double ms[4] = {};
+        for (vrt_scene *s : m->sc) {
+                double r[4];
+                if (int rc = vrt_scene_update_stats(s, r))
+                        return rc;
+                ms[1] = std::max(ms[1], r[0]);
+        }
+        if (distributed) {
+                float d = 0.f;
+                HIPCHK(hipSetDevice(m->devs[0]));
+                HIPCHK(hipEventElapsedTime(&d, m->up_d0, m->up_d1));
+                ms[2] = d;
+        }
+        if ((tf & VRT_TEST_MULTI_DIVERGE) != 0)
+                if (int rc = scene_test_flip_attr(m->sc[n - 1]))
+                        return rc;
+        if (flags & VRT_MULTI_UPDATE_VERIFY) {
+                const double v0 = now_ms();
+                if (int rc = verify_replicas(m))
+                        return rc;
+                ms[3] = now_ms() - v0;
+        }
+        ms[0] = now_ms() - t0;
+        std::memcpy(m->up_ms, ms, sizeof ms);
+        m->updated = true;
+        return VRT_OK;
+}
+
 }  // namespace
 
 extern "C" void vrt_multi_destroy(vrt_multi *m)
@@ -777,5 +1028,28 @@ extern "C" int vrt_multi_tile_map(const vrt_film *film, uint32_t device_mask, in
         const int64_t nt = (int64_t)(film->nx / 8) * (film->ny / 8);
         for (int64_t t = 0; t < nt; ++t)
                 device_of_tile[t] = devs[device_of_tile[t]];
+        return VRT_OK;
+}
+
+extern "C" int vrt_multi_update(vrt_multi *m, const float *pos, const float *nrm, const vrt_probe *probes, int flags)
+{
+        return multi_update(m, "vrt_multi_update", pos, nrm, probes, flags, false, nullptr);
+}
+
+extern "C" int vrt_multi_update_device(vrt_multi *m, const float *d_pos, const float *d_nrm, const vrt_probe *d_probes,
+                                       int flags, void *stream)
+{
+        return multi_update(m, "vrt_multi_update_device", d_pos, d_nrm, d_probes, flags, true,
+                            static_cast<hipStream_t>(stream));
+}
+
+extern "C" int vrt_multi_update_stats(const vrt_multi *m, double ms[4])
+{
+        if (!m || !ms)
+                return set_error(VRT_E_INVALID, "null argument");
+        if (!m->updated)
+                return set_error(VRT_E_INVALID, "the handle has not been updated");
+        for (int k = 0; k < 4; ++k)
+                ms[k] = m->up_ms[k];
         return VRT_OK;
 }
