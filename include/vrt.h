@@ -531,8 +531,9 @@ int vrt_lightmap_build(vrt_scene *s, const vrt_camera *light_cam,
  * illum[6][3].  coverage / illum may be NULL. */
 int vrt_lightmap_nodes(vrt_scene *s, uint64_t *key, float *coverage,
                        float *illum);
-/* Diagnostics of the last light-map build (vrt_lightmap_build or a one-call
- * frame): stats = {light samples (64 * (nx/8) * (ny/8) * 4), samples that
+/* Diagnostics of the last light-map build (vrt_lightmap_build[_lights] or a
+ * one-call frame): stats = {light samples (64 * (nx/8) * (ny/8) * 4, summed
+ * over the lights of a light list), samples that
  * hit, samples whose walk passed the triangle-test budget and was handed to
  * the tail walk}.  All 0 before the first build. */
 int vrt_lightmap_stats(vrt_scene *s, int64_t stats[3]);
@@ -564,6 +565,52 @@ int vrt_trace_frame_device(vrt_scene *s, const vrt_camera *light_cam,
                            const vrt_film *film, float min_voxel, int rank,
                            int nranks, int image_layout, float *d_out,
                            void *stream, int64_t *hits);
+
+/* ---- several coloured lights in one light map -----------------------------
+ * The reference's light block (VRT/main.cc:80-97) run once per light,
+ * lights[0] first, into one map, and one cone_trace_init_filter afterwards.
+ * A light is a light camera, its film and the colour the block hands to
+ * Triangle::get_diffuse(isect, ray, color) (VRT/voxel_octree.cc:462-469;
+ * the reference's driver passes (1,1,1)): a hit sample adds
+ * clamp(dot(illum_d[i], normal), 0, 1) * ((albedo * tmp) * color) to
+ * leaf->illum[i], componentwise, one rounding per multiplication.  A leaf's
+ * sum is one sequential float chain from zero over light 0's samples in the
+ * canonical order (vrt_lightmap_build's), then light 1's, and so on: the
+ * order of the lights is part of the result's last bits.  One light with
+ * colour (1,1,1) gives vrt_lightmap_build's map bit for bit.  Colours are
+ * taken as they are (negative, above 1, non-finite).
+ *
+ * One march, one sort, one sum, one filter and one host sync whatever
+ * nlights is.  Each film is checked as vrt_lightmap_build checks its film; a
+ * film without a sample (nx < 8 or ny < 8) contributes nothing.
+ * VRT_E_INVALID: nlights outside 1..VRT_MAX_LIGHTS, a NULL argument, or more
+ * than 2^31 - 1 samples (64 * (nx/8) * (ny/8) * 4 per film) over all lights;
+ * nothing is enqueued then and the current light map stays.  The scene's
+ * light scratch (vrt_scene_scratch_bytes) holds 72 bytes per sample of the
+ * total (keys and slots in and out, the hit records and their sorted copy)
+ * plus the sort's own temporary storage.  *hits (may be NULL): the hit
+ * samples of all lights.  vrt_lightmap_stats afterwards: the samples marched
+ * over all lights, the hits, the samples handed to the tail walk.  A new
+ * build replaces the previous light map; every reader of the map works on it
+ * unchanged. */
+#define VRT_MAX_LIGHTS 16
+typedef struct {
+        vrt_camera cam;
+        vrt_film film;
+        float color[3];
+} vrt_light;
+int vrt_lightmap_build_lights(vrt_scene *s, const vrt_light *lights, int nlights, int64_t *hits);
+/* vrt_trace_frame_device / vrt_trace_frame_probes_device with the light list
+ * above: values equal vrt_lightmap_build_lights followed by
+ * vrt_render_trace_device (on a probe scene: by the probes' gather, then
+ * vrt_render_trace_probes_device).  probe_light_color is NOT a light's
+ * colour: it is the light_color of vrt_trace_frame_probes_device, the value a
+ * probe's gather adds where a gather ray misses (float[3]; NULL keeps the
+ * stored SGs; ignored on a scene without probes). */
+int vrt_trace_frame_lights_device(vrt_scene *s, const vrt_light *lights, int nlights,
+                                  const float *probe_light_color, const vrt_camera *cam,
+                                  const vrt_film *film, float min_voxel, int rank, int nranks,
+                                  int image_layout, float *d_out, void *stream, int64_t *hits);
 
 /* ---- batched trace() / cone_trace over the caller's rays and points -------
  * The reference's per-ray entry points beside ray_march, as its
@@ -946,6 +993,22 @@ int vrt_trace_frame_multi(vrt_multi *m, const vrt_camera *light_cam, const vrt_f
 int vrt_trace_frame_multi_device(vrt_multi *m, const vrt_camera *light_cam, const vrt_film *light_film,
                                  const float *light_color, const vrt_camera *cam, const vrt_film *film,
                                  float min_voxel, float *d_image, void *stream, int64_t *hits);
+/* The three calls above with a light list (vrt_lightmap_build_lights).
+ * Replicated: every rank marches every light's whole film.  Sharded: rank i
+ * marches its tiles of each light film's own tile deal; a key's canonical
+ * index runs over the samples of all lights, so the exchanged lists merge as
+ * one light's do.  Every rank ends with the single-device map bit for bit.
+ * *hits: the total over all lights.  probe_light_color: the light_color of
+ * vrt_trace_frame_multi (the probes' gather on a miss), not a light's colour.
+ * Arguments are checked before anything is enqueued, as above. */
+int vrt_lightmap_build_lights_multi(vrt_multi *m, const vrt_light *lights, int nlights, int64_t *hits);
+int vrt_trace_frame_lights_multi(vrt_multi *m, const vrt_light *lights, int nlights,
+                                 const float *probe_light_color, const vrt_camera *cam,
+                                 const vrt_film *film, float min_voxel, float *rgb, int64_t *hits);
+int vrt_trace_frame_lights_multi_device(vrt_multi *m, const vrt_light *lights, int nlights,
+                                        const float *probe_light_color, const vrt_camera *cam,
+                                        const vrt_film *film, float min_voxel, float *d_image, void *stream,
+                                        int64_t *hits);
 
 /* Config 5 over the handle's ranks: rank i renders its share
  * (vrt_render_secondary_tiles_device) on its stream into scratch the handle

@@ -7,7 +7,7 @@ the library and raises if it is missing: there is no CPU fallback.
 """
 from ._ffi import VrtError, lib, LIB_PATH  # noqa: F401
 from .api import (  # noqa: F401
-    FLT_MAX, Camera, Film, MultiOctree, ObjModel, SceneData, VoxelOctree, multi_tile_map, build_id, build_flag, test_flags, device_count, device_selftest,
+    FLT_MAX, Camera, Film, Light, MultiOctree, ObjModel, SceneData, VoxelOctree, multi_tile_map, build_id, build_flag, test_flags, device_count, device_selftest,
     device_selftest_order, device_selftest_chain,
     hdr_bytes, hdr_bytes_from_rgbe, intersect_triangle3, load_image, make_ray, obj2voxel, ray_march, ray_march_init, trace, cone_trace,
     TEST_FORCE_DEFER, TEST_FAIL_LAUNCH, TEST_SPILL_ALL, TEST_STREAM_LEFTOVER, TEST_LIGHT_TAIL, TEST_PRIM_TAIL, TEST_SEC_DEFER, TEST_SMALL_BATCH_CHUNK, TEST_SMALL_BEAM_ENTRY, TEST_UPDATE_TOO_LARGE, TEST_VIRTUAL_RANKS, render, set_test_flags, sweep_pose, tga_decode, tile_deal_map, tiles_per_rank, to_radian, tri_box_overlap,
@@ -18,7 +18,7 @@ from .api import (  # noqa: F401
 )
 
 __all__ = [
-    "VrtError", "lib", "LIB_PATH", "FLT_MAX", "Camera", "Film", "SceneData", "VoxelOctree", "MultiOctree",
+    "VrtError", "lib", "LIB_PATH", "FLT_MAX", "Camera", "Film", "Light", "SceneData", "VoxelOctree", "MultiOctree",
     "multi_tile_map",
     "device_count", "device_selftest", "hdr_bytes", "intersect_triangle3", "make_ray",
     "ray_march", "ray_march_init", "trace", "cone_trace", "render", "sweep_pose", "tile_deal_map", "tiles_per_rank", "to_radian",

@@ -48,6 +48,11 @@ class Film(C.Structure):
                 ("ny", C.c_int32)]
 
 
+class LightRec(C.Structure):
+    """vrt_light: a light camera, its film, get_diffuse's colour."""
+    _fields_ = [("cam", Camera), ("film", Film), ("color", C.c_float * 3)]
+
+
 class Hit(C.Structure):
     _fields_ = [("hit", C.c_int32), ("tri", C.c_int32), ("voxel", C.c_uint32),
                 ("hit_p", C.c_float * 3), ("normal", C.c_float * 3)]
@@ -215,6 +220,14 @@ SIGNATURES = {
                                   i32p, i32p, f32p, i32p, i32p, i64p, u8p, i64p]),
     "vrt_sweep_pose": (C.c_int, [f32p, f32p, C.c_int, C.c_int, f32p, f32p, f32p, f32p]),
     "vrt_lightmap_build": (C.c_int, [_P, C.POINTER(Camera), C.POINTER(Film), i64p]),
+    "vrt_lightmap_build_lights": (C.c_int, [_P, C.POINTER(LightRec), C.c_int, i64p]),
+    "vrt_trace_frame_lights_device": (C.c_int, [_P, C.POINTER(LightRec), C.c_int, f32p, _P, _P, C.c_float, C.c_int,
+                                                C.c_int, C.c_int, _P, _P, i64p]),
+    "vrt_lightmap_build_lights_multi": (C.c_int, [_P, C.POINTER(LightRec), C.c_int, i64p]),
+    "vrt_trace_frame_lights_multi": (C.c_int, [_P, C.POINTER(LightRec), C.c_int, f32p, C.POINTER(Camera),
+                                               C.POINTER(Film), C.c_float, f32p, i64p]),
+    "vrt_trace_frame_lights_multi_device": (C.c_int, [_P, C.POINTER(LightRec), C.c_int, f32p, C.POINTER(Camera),
+                                                      C.POINTER(Film), C.c_float, _P, _P, i64p]),
     "vrt_lightmap_nodes": (C.c_int, [_P, C.POINTER(C.c_uint64), f32p, f32p]),
     "vrt_lightmap_stats": (C.c_int, [_P, i64p]),
     "vrt_scene_min_voxel": (C.c_int, [_P, C.c_int, f32p]),

@@ -80,6 +80,28 @@ class Camera:
         return self._rays(arr)
 
 
+class Light:
+    """One light of a light list (vrt_light): a light camera, its film and the
+    colour the light pass hands to Triangle::get_diffuse (the reference's
+    driver passes (1, 1, 1)).  The colour is taken as it is."""
+
+    def __init__(self, camera, film, color=(1.0, 1.0, 1.0)):
+        self.camera, self.film, self.color = camera, film, _f3(color)
+
+
+def _lights_arg(lights):
+    """(vrt_light array or None, count) of a sequence of Light."""
+    if lights is None:
+        return None, 0
+    lights = list(lights)
+    arr = (_ffi.LightRec * max(1, len(lights)))()
+    for i, l in enumerate(lights):
+        arr[i].cam = l.camera.c
+        arr[i].film = l.film.c
+        arr[i].color[:] = [float(v) for v in l.color]
+    return arr, len(lights)
+
+
 def make_ray(o, d, tmin=0.0, tmax=FLT_MAX):
     """jql::Ray(o, d, tmin, tmax): normalises d (VRT/graphics_math.h:1159-1166)."""
     r = _ffi.Ray()
@@ -709,6 +731,15 @@ class VoxelOctree:
               "vrt_lightmap_build")
         return h.value
 
+    def lightmap_lights(self, lights):
+        """Several coloured lights into one light map
+        (vrt_lightmap_build_lights): the light pass run light after light in
+        the order given, one filter; returns the hit samples of all lights."""
+        arr, n = _lights_arg(lights)
+        h = C.c_int64()
+        check(lib().vrt_lightmap_build_lights(self.h, arr, n, C.byref(h)), "vrt_lightmap_build_lights")
+        return h.value
+
     def lightmap_nodes(self):
         """(key depth<<32|vox, coverage, illum (n,6,3)) sorted by key."""
         n = self.info.nodes
@@ -755,6 +786,22 @@ class VoxelOctree:
                                            int(image_layout), C.c_void_p(d_out_ptr),
                                            None if stream_ptr is None else C.c_void_p(stream_ptr), C.byref(hits)),
               "vrt_trace_frame_device")
+        return hits.value
+
+    def trace_frame_lights_device(self, lights, cam, film, rank, nranks, image_layout, d_out_ptr, min_voxel=0.0,
+                                  probe_light_color=None, stream_ptr=None):
+        """trace_frame_device over a light list (vrt_trace_frame_lights_device).
+        probe_light_color is not a light's colour: on a probe scene it is what
+        the probes' gather adds on a miss (None keeps the stored SGs).
+        Returns the hit samples of all lights."""
+        arr, n = _lights_arg(lights)
+        hits = C.c_int64()
+        lc = None if probe_light_color is None else _f3(probe_light_color)
+        check(lib().vrt_trace_frame_lights_device(self.h, arr, n, ptr(lc, _ffi.f32p), C.byref(cam.c), C.byref(film.c),
+                                                  float(min_voxel), int(rank), int(nranks), int(image_layout),
+                                                  C.c_void_p(d_out_ptr),
+                                                  None if stream_ptr is None else C.c_void_p(stream_ptr),
+                                                  C.byref(hits)), "vrt_trace_frame_lights_device")
         return hits.value
 
     # ---- trace() frames of a probe scene (probe hits shaded on the device) ----
@@ -1090,6 +1137,39 @@ class MultiOctree:
         h = C.c_int64()
         check(lib().vrt_lightmap_build_multi(self.h, C.byref(light_cam.c), C.byref(light_film.c), C.byref(h)),
               "vrt_lightmap_build_multi")
+        return h.value
+
+    def lightmap_lights(self, lights):
+        """Several coloured lights into one light map on every rank
+        (vrt_lightmap_build_lights_multi); returns the hits of all lights."""
+        arr, n = _lights_arg(lights)
+        h = C.c_int64()
+        check(lib().vrt_lightmap_build_lights_multi(self.h, arr, n, C.byref(h)), "vrt_lightmap_build_lights_multi")
+        return h.value
+
+    def trace_frame_lights(self, lights, cam, film, min_voxel=0.0, probe_light_color=None):
+        """trace_frame over a light list (vrt_trace_frame_lights_multi) ->
+        ((ny, nx, 3) image, hits of all lights).  probe_light_color: the
+        probes' gather's miss colour on a probe handle, not a light's colour."""
+        arr, n = _lights_arg(lights)
+        rgb = np.zeros((film.ny, film.nx, 3), np.float32)
+        h = C.c_int64()
+        lc = None if probe_light_color is None else _f3(probe_light_color)
+        check(lib().vrt_trace_frame_lights_multi(self.h, arr, n, ptr(lc, _ffi.f32p), C.byref(cam.c), C.byref(film.c),
+                                                 float(min_voxel), ptr(rgb, _ffi.f32p), C.byref(h)),
+              "vrt_trace_frame_lights_multi")
+        return rgb, h.value
+
+    def trace_frame_lights_device(self, lights, cam, film, d_image_ptr, min_voxel=0.0, probe_light_color=None,
+                                  stream_ptr=None):
+        """trace_frame_lights into a device image on the first device."""
+        arr, n = _lights_arg(lights)
+        h = C.c_int64()
+        lc = None if probe_light_color is None else _f3(probe_light_color)
+        check(lib().vrt_trace_frame_lights_multi_device(self.h, arr, n, ptr(lc, _ffi.f32p), C.byref(cam.c),
+                                                        C.byref(film.c), float(min_voxel), C.c_void_p(d_image_ptr),
+                                                        C.c_void_p(stream_ptr) if stream_ptr else None, C.byref(h)),
+              "vrt_trace_frame_lights_multi_device")
         return h.value
 
     def render_trace(self, cam, film, min_voxel=0.0):

@@ -2536,14 +2536,17 @@ struct LightBuild {
 // three steps (caller holds s->mu).  Step 1: the leaf case of the filter and
 // the light march of rank `rank` of `nranks` of the light film's tile deal
 // (0 of 1: the whole film) into the compact hit lists.
-static int light_begin(vrt_scene *s, int set, const vrt_camera *light_cam, const vrt_film *light_film, int rank,
-                       int nranks, LightBuild *b)
+static int light_begin(vrt_scene *s, int set, const vrt_light *lights, int nlights, bool fused, int rank, int nranks,
+                       LightBuild *b)
 {
         const int64_t nnodes = (int64_t)s->nodes.size();
-        const int ptx = light_film->nx / 8, pty = light_film->ny / 8;
-        const int64_t ns = (int64_t)64 * ptx * pty * 4;
+        // fused: the *_lights calls' march over all lights (k_light_lights);
+        // otherwise the one light the older calls have (k_light)
+        int64_t ns = 0;
+        for (int l = 0; l < nlights; ++l)
+                ns += (int64_t)64 * (lights[l].film.nx / 8) * (lights[l].film.ny / 8) * 4;
         if (ns > 0x7FFFFFFF)
-                return fail(VRT_E_INVALID, "light film too large (%lld samples)", (long long)ns);
+                return fail(VRT_E_INVALID, "light film%s too large (%lld samples)", fused ? "s" : "", (long long)ns);
         // one block: light map, cone-descent records, finiteness flag
         if (int rc = ensure_lm(s, set))
                 return rc;
@@ -2588,11 +2591,41 @@ static int light_begin(vrt_scene *s, int set, const vrt_camera *light_cam, const
         b->d_seg_end = reinterpret_cast<uint32_t *>(ctr + 256 + bseg);
         LightParams lp;
         std::memset(&lp, 0, sizeof lp);
-        fill_render_params(s, light_cam, light_film, rank, nranks, &lp.r);
-        lp.r.tile_xy = deal_map(s, ptx, pty, nranks, rank, s->stream);  // null for one rank
-        b->ns_rank = (int64_t)lp.r.tiles_this_rank * 256;
-        lp.ptx = ptx;
-        lp.pty = pty;
+        fill_render_params(s, &lights[0].cam, &lights[0].film, rank, nranks, &lp.r);
+        LightsParams lq;
+        if (fused) {
+                std::memset(&lq, 0, sizeof lq);
+                lq.nlights = nlights;
+                int64_t units = 0, base = 0;
+                for (int l = 0; l < VRT_MAX_LIGHTS; ++l) {
+                        if (l >= nlights) {
+                                lq.unit_end[l] = INT32_MAX;
+                                continue;
+                        }
+                        RenderParams rp;
+                        fill_render_params(s, &lights[l].cam, &lights[l].film, rank, nranks, &rp);
+                        LightEntry &e = lq.e[l];
+                        e.cam = rp.cam;
+                        e.ptx = rp.ntx;
+                        e.pty = rp.nty;
+                        e.unit_begin = (int32_t)units;
+                        e.tile_xy = deal_map(s, rp.ntx, rp.nty, nranks, rank, s->stream);  // null for one rank
+                        e.ntx_magic = rp.ntx_magic;
+                        e.key_base = (uint64_t)base;
+                        std::memcpy(e.color, lights[l].color, sizeof e.color);
+                        units += (int64_t)rp.tiles_this_rank * 4;
+                        base += (int64_t)64 * rp.ntx * rp.nty * 4;
+                        lq.unit_end[l] = (int32_t)units;
+                }
+                lq.units = (int32_t)units;
+                b->ns_rank = units * 64;
+        } else {
+                const int ptx = lights[0].film.nx / 8, pty = lights[0].film.ny / 8;
+                lp.r.tile_xy = deal_map(s, ptx, pty, nranks, rank, s->stream);  // null for one rank
+                b->ns_rank = (int64_t)lp.r.tiles_this_rank * 256;
+                lp.ptx = ptx;
+                lp.pty = pty;
+        }
         lp.kbits = kbits;
         lp.count = b->d_count;
         lp.keys = b->k_in;
@@ -2607,7 +2640,12 @@ static int light_begin(vrt_scene *s, int set, const vrt_camera *light_cam, const
         // a leaf whose list holds probes only is non-empty too: coverage 1
         if (!s->probes.empty())
                 HIPCHK(launch_lm_probe_leaves(s->dev.nodes, s->pdev.pnode, nnodes, b->d_lm, s->stream));
-        HIPCHK(launch_light(lp, s->stream));
+        if (fused) {
+                lq.p = lp;
+                HIPCHK(launch_light_lights(lq, s->stream));
+        } else {
+                HIPCHK(launch_light(lp, s->stream));
+        }
         return VRT_OK;
 }
 
@@ -2675,11 +2713,11 @@ static int light_finish(vrt_scene *s, LightBuild *b, unsigned int total, bool me
 // the light pass is enqueued, before the mid-build host sync, so work it
 // enqueues on another stream runs beside the light pass; on return the filter
 // is enqueued and *lm_done (if given) recorded after it.
-static int lightmap_enqueue(vrt_scene *s, int set, const vrt_camera *light_cam, const vrt_film *light_film,
+static int lightmap_enqueue(vrt_scene *s, int set, const vrt_light *lights, int nlights, bool fused,
                             unsigned int *hits, const std::function<int()> &overlap, hipEvent_t lm_done)
 {
         LightBuild b;
-        if (int rc = light_begin(s, set, light_cam, light_film, 0, 1, &b))
+        if (int rc = light_begin(s, set, lights, nlights, fused, 0, 1, &b))
                 return rc;
         if (overlap)
                 if (int rc = overlap())
@@ -2692,6 +2730,52 @@ static int lightmap_enqueue(vrt_scene *s, int set, const vrt_camera *light_cam, 
         return VRT_OK;
 }
 
+// the one light of the calls that take a light camera and film: white, as
+// the reference's driver passes it (VRT/main.cc:89-90)
+static vrt_light white_light(const vrt_camera *cam, const vrt_film *film)
+{
+        vrt_light l;
+        l.cam = *cam;
+        l.film = *film;
+        l.color[0] = l.color[1] = l.color[2] = 1.f;
+        return l;
+}
+
+int vrt::lights_ok(const vrt_light *lights, int nlights)
+{
+        if (!lights)
+                return fail(VRT_E_INVALID, "null argument");
+        if (nlights < 1 || nlights > VRT_MAX_LIGHTS)
+                return fail(VRT_E_INVALID, "nlights %d outside 1..%d", nlights, VRT_MAX_LIGHTS);
+        int64_t ns = 0;
+        for (int l = 0; l < nlights; ++l) {
+                if (int rc = film_ok(&lights[l].film))
+                        return rc;
+                ns += (int64_t)64 * (lights[l].film.nx / 8) * (lights[l].film.ny / 8) * 4;
+        }
+        if (ns > 0x7FFFFFFF)
+                return fail(VRT_E_INVALID, "light films too large (%lld samples over %d lights)", (long long)ns, nlights);
+        return VRT_OK;
+}
+
+// the blocking light-map build of vrt_lightmap_build[_lights]
+static int lightmap_build(vrt_scene *s, const vrt_light *lights, int nlights, bool fused, int64_t *hits)
+{
+        std::lock_guard<std::mutex> lk(s->mu);
+        HIPCHK(hipSetDevice(s->device));
+        unsigned int nhit = 0;
+        const int set = s->ts_next;
+        s->ts_next ^= 1;
+        if (int rc = lightmap_enqueue(s, set, lights, nlights, fused, &nhit, {}, nullptr))
+                return rc;
+        if (int rc = ts_release(s, set, s->stream))
+                return rc;
+        HIPCHK(hipStreamSynchronize(s->stream));
+        if (hits)
+                *hits = (int64_t)nhit;
+        return VRT_OK;
+}
+
 extern "C" int vrt_lightmap_build(vrt_scene *s, const vrt_camera *light_cam,
                                   const vrt_film *light_film, int64_t *hits)
 {
@@ -2701,19 +2785,19 @@ extern "C" int vrt_lightmap_build(vrt_scene *s, const vrt_camera *light_cam,
                 return fail(VRT_E_INVALID, "null argument");
         if (int rc = film_ok(light_film))
                 return rc;
-        std::lock_guard<std::mutex> lk(s->mu);
-        HIPCHK(hipSetDevice(s->device));
-        unsigned int nhit = 0;
-        const int set = s->ts_next;
-        s->ts_next ^= 1;
-        if (int rc = lightmap_enqueue(s, set, light_cam, light_film, &nhit, {}, nullptr))
+        const vrt_light one = white_light(light_cam, light_film);
+        return lightmap_build(s, &one, 1, false, hits);
+}
+
+extern "C" int vrt_lightmap_build_lights(vrt_scene *s, const vrt_light *lights, int nlights, int64_t *hits)
+{
+        if (s && need_device(s))
+                return VRT_E_NODEVICE;
+        if (!s)
+                return fail(VRT_E_INVALID, "null argument");
+        if (int rc = lights_ok(lights, nlights))
                 return rc;
-        if (int rc = ts_release(s, set, s->stream))
-                return rc;
-        HIPCHK(hipStreamSynchronize(s->stream));
-        if (hits)
-                *hits = (int64_t)nhit;
-        return VRT_OK;
+        return lightmap_build(s, lights, nlights, true, hits);
 }
 
 extern "C" int vrt_lightmap_stats(vrt_scene *s, int64_t stats[3])
@@ -3988,6 +4072,12 @@ int vrt::frame_check(vrt_scene *s, const FrameArgs &a)
 {
         // without a light film: the view over the current light map alone
         FramePath fp{ a.what, true };
+        if (a.nlights > 0 || a.lights) {
+                if (int rc = frame_args_ok(s, &fp, a.cam && a.lights, false, nullptr, a.film, a.rank, a.nranks,
+                                           a.image_layout, a.min_voxel))
+                        return rc;
+                return lights_ok(a.lights, a.nlights);
+        }
         const bool has_light = a.light_film != nullptr;
         return frame_args_ok(s, &fp, a.cam && (a.light_cam || !has_light), has_light, a.light_film, a.film, a.rank,
                              a.nranks, a.image_layout, a.min_voxel);
@@ -3997,18 +4087,23 @@ int vrt::frame_begin(vrt_scene *s, const FrameArgs &a, FrameJob **out)
 {
         *out = nullptr;
         FramePath fp{ a.what, a.may_probe };
+        const bool fused = a.nlights > 0 || a.lights;
         if (a.cam) {
-                if (int rc = frame_args_ok(s, &fp, a.light_cam && a.d_out, true, a.light_film, a.film, a.rank, a.nranks,
-                                           a.image_layout, a.min_voxel))
+                if (int rc = frame_args_ok(s, &fp, (fused ? a.lights != nullptr : a.light_cam != nullptr) && a.d_out,
+                                           !fused, a.light_film, a.film, a.rank, a.nranks, a.image_layout, a.min_voxel))
                         return rc;
         } else {
                 if (s && need_device(s))
                         return VRT_E_NODEVICE;
-                if (!s || !a.light_cam)
+                if (!s || !(fused ? (const void *)a.lights : (const void *)a.light_cam))
                         return fail(VRT_E_INVALID, "null argument");
-                if (int rc = film_ok(a.light_film))
-                        return rc;
+                if (!fused)
+                        if (int rc = film_ok(a.light_film))
+                                return rc;
         }
+        if (fused)
+                if (int rc = lights_ok(a.lights, a.nlights))
+                        return rc;
         if (a.light_nranks < 1 || a.light_rank < 0 || a.light_rank >= a.light_nranks)
                 return fail(VRT_E_INVALID, "light rank %d of %d", a.light_rank, a.light_nranks);
         std::unique_ptr<FrameJob> job(new (std::nothrow) FrameJob);
@@ -4053,7 +4148,9 @@ int vrt::frame_begin(vrt_scene *s, const FrameArgs &a, FrameJob **out)
         }
         j->started = true;
         job.release();
-        if (int rc = light_begin(s, set, a.light_cam, a.light_film, a.light_rank, a.light_nranks, &j->lb))
+        const vrt_light one = fused ? vrt_light{} : white_light(a.light_cam, a.light_film);
+        if (int rc = light_begin(s, set, fused ? a.lights : &one, fused ? a.nlights : 1, fused, a.light_rank,
+                                 a.light_nranks, &j->lb))
                 return frame_bail(j, rc);
         if (j->view) {
                 // the view's primary march beside the light pass (its records
@@ -4226,6 +4323,47 @@ extern "C" int vrt_trace_frame_probes_device(vrt_scene *s, const vrt_camera *lig
 {
         return trace_frame_device(s, { "vrt_trace_frame_probes_device", true }, light_cam, light_film, light_color,
                                   cam, film, min_voxel, rank, nranks, image_layout, d_out, stream, hits);
+}
+
+extern "C" int vrt_trace_frame_lights_device(vrt_scene *s, const vrt_light *lights, int nlights,
+                                             const float *probe_light_color, const vrt_camera *cam,
+                                             const vrt_film *film, float min_voxel, int rank, int nranks,
+                                             int image_layout, float *d_out, void *stream, int64_t *hits)
+{
+        FrameArgs a{};
+        a.what = "vrt_trace_frame_lights_device";
+        a.may_probe = true;
+        a.lights = lights;
+        a.nlights = nlights;
+        a.light_color = probe_light_color;
+        a.light_rank = 0;
+        a.light_nranks = 1;
+        a.cam = cam;
+        a.film = film;
+        a.min_voxel = min_voxel;
+        a.rank = rank;
+        a.nranks = nranks;
+        a.image_layout = image_layout;
+        a.d_out = d_out;
+        a.stream = static_cast<hipStream_t>(stream);
+        if (!cam || !lights || nlights < 1) {  // a job without a view is the handle's; here a bad argument
+                if (s && need_device(s))
+                        return VRT_E_NODEVICE;
+                if (!s || !cam || !lights)
+                        return fail(VRT_E_INVALID, "null argument");
+                return lights_ok(lights, nlights);
+        }
+        FrameJob *j = nullptr;
+        if (int rc = frame_begin(s, a, &j))
+                return rc;
+        LightList l{};
+        if (int rc = frame_wait(j, &l))
+                return rc;
+        if (int rc = frame_finish(j, l.n, false))
+                return rc;
+        if (hits)
+                *hits = (int64_t)l.n;
+        return VRT_OK;
 }
 
 extern "C" int vrt_device_selftest(int device, const double *mt_in,

@@ -512,6 +512,37 @@ struct LightParams {
         uint32_t *tail;
 };
 
+// Several lights into one light map (vrt_lightmap_build_lights): one march
+// over the concatenated work units of this rank's share of every light film.
+// Light l owns the global units [unit_begin, unit_end[l]); its samples'
+// canonical indices follow those of lights 0..l-1 (key_base = their whole
+// films' sample count), so the sorted lists sum a leaf's samples light after
+// light, as the reference's light block run once per light does.  The whole
+// table is a kernel argument (under the 4 KB limit, checked below): a
+// block's light is block-uniform, so its entry comes by scalar loads.
+struct LightEntry {
+        CamParams cam;
+        int32_t ptx, pty;        // the film's tile grid (= its render_mt task size)
+        int32_t unit_begin;
+        int32_t pad0;
+        const uint32_t *tile_xy; // as RenderParams::tile_xy, for this film's deal
+        uint64_t ntx_magic;      // as RenderParams::ntx_magic
+        uint64_t key_base;
+        float color[3];          // get_diffuse's colour argument
+        int32_t pad1;
+};
+struct LightsParams {
+        // the lists, counters, scene, rank and test flags; p.r's camera and
+        // tile grid are unused (each light has its own)
+        LightParams p;
+        int32_t nlights;
+        int32_t units;           // unit_end[nlights - 1]
+        // prefix sums of the lights' units; INT32_MAX from nlights on
+        int32_t unit_end[VRT_MAX_LIGHTS];
+        LightEntry e[VRT_MAX_LIGHTS];
+};
+static_assert(sizeof(LightsParams) <= 4096, "LightsParams must fit the kernel-argument limit");
+
 // Cone-tracing render (trace(), VRT/main.cc:10-30 + cone_trace,
 // VRT/voxel_octree.cc:276-330).  split_up[e]: smallest float x in
 // [2^e, 2^(e+1)) with (int)log2f(x) == e+1 under the host libm (the same
@@ -638,6 +669,10 @@ struct FrameArgs {
         const vrt_camera *light_cam;
         const vrt_film *light_film;
         const float *light_color;
+        // nlights > 0: the light list of the *_lights calls (k_light_lights),
+        // and light_cam / light_film are unused; 0: the one light above
+        const vrt_light *lights;
+        int nlights;
         int light_rank, light_nranks;
         const vrt_camera *cam;
         const vrt_film *film;
@@ -654,6 +689,8 @@ struct LightList {
         hipStream_t stream;  // the scene's stream, where the lists are written and read
 };
 int frame_check(vrt_scene *s, const FrameArgs &a);
+// a light list's own arguments (count, pointers, films, total samples)
+int lights_ok(const vrt_light *lights, int nlights);
 int frame_begin(vrt_scene *s, const FrameArgs &a, FrameJob **out);
 int frame_wait(FrameJob *j, LightList *l);
 int frame_finish(FrameJob *j, unsigned int total, bool merged);
@@ -1003,6 +1040,7 @@ SpillQueues spill_defaults();
 // unknown name) -- vrt_build_flag
 bool build_flag(const char *name, int64_t *value);
 hipError_t launch_light(const LightParams &p, hipStream_t st);
+hipError_t launch_light_lights(const LightsParams &q, hipStream_t st);
 // out[k] = rank's k-th tile of the deal (deal_tile), tx | ty << 16, for k <
 // deal_count (ntx, nty < 2^16)
 hipError_t launch_deal_map(int ntx, int nty, int nranks, int rank, uint32_t *out, hipStream_t st);

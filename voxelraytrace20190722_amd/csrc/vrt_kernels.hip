@@ -4798,6 +4798,115 @@ __global__ __launch_bounds__(64, VRT_TAIL_WAVES_PER_EU) void k_light_tail(LightP
         }
 }
 
+// ---- several lights into one light map (vrt_lightmap_build_lights) --------
+// One march over the concatenated units of every light film's share
+// (LightsParams, vrt_internal.h).  The light of global unit u: the number of
+// prefix sums <= u.  For a block's own unit everything here is uniform (the
+// table is a kernel argument): scalar loads and compares.
+__device__ __forceinline__ int lights_find(const LightsParams &q, int u)
+{
+        int l = 0;
+#pragma unroll
+        for (int i = 0; i < VRT_MAX_LIGHTS - 1; ++i)
+                l += u >= q.unit_end[i] ? 1 : 0;
+        return l;
+}
+
+// lane tid of global unit u (of light e): its pixel and sample, as
+// tile_lane_at gives them for the light's own unit u - unit_begin
+__device__ __forceinline__ void lights_lane_at(const LightsParams &q, const LightEntry &e, int u, int tid, int &px,
+                                               int &py, int &s)
+{
+        const int ul = u - e.unit_begin;
+        int tx, ty;
+        rank_tile(e.ptx, e.pty, q.p.r.nranks, q.p.r.rank, e.ntx_magic, e.tile_xy, ul / 4, tx, ty);
+        const int wave = (ul % 4) + (tid >> 6), lane = tid & 63;
+        s = lane & 3;
+        const int pix = lane >> 2;
+        px = tx * 8 + (wave & 1) * 4 + (pix & 3);
+        py = ty * 8 + (wave >> 1) * 4 + (pix >> 2);
+}
+
+__device__ __forceinline__ RayK lights_ray(const LightEntry &e, int px, int py, int s)
+{
+        const CamParams &c = e.cam;
+        const f3 dn = camera_dir(c.s, c.u, c.nf, c.e, c.z, c.nx, c.ny, px, py,
+                                 sample_x(s), sample_y(s));
+        return make_rayk(mk3(c.origin[0], c.origin[1], c.origin[2]), dn, c.tmin, c.tmax);
+}
+
+// light_record for light e: the canonical index follows the samples of the
+// lights before it, and get_diffuse's colour is the light's --
+// (albedo * tmp) * color, one rounding per multiplication
+__device__ __forceinline__ void lights_record(const LightsParams &q, const LightEntry &e, const RayK &r,
+                                              const MarchResult &m, int px, int py, int s)
+{
+        const int tx = px / e.ptx, ty = py / e.pty;
+        const int64_t task = (int64_t)tx * 8 + ty;
+        const int64_t key = ((task * e.pty + (py - ty * e.pty)) * e.ptx + (px - tx * e.ptx)) * 4 + s;
+        f3 nrm;
+        const f3 il = shade_hit(q.p.r.sc, r, m, nrm);
+        const uint32_t j = atomicAdd(q.p.count, 1u);
+        q.p.keys[j] = ((uint64_t)m.node << q.p.kbits) | (e.key_base + (uint64_t)key);
+        q.p.vals[j] = j;
+        float *o = q.p.samp + 6 * (int64_t)j;
+        o[0] = il.x * e.color[0]; o[1] = il.y * e.color[1]; o[2] = il.z * e.color[2];
+        o[3] = nrm.x; o[4] = nrm.y; o[5] = nrm.z;
+}
+
+template <bool kR64>
+__global__ __launch_bounds__(kRenderBlock, VRT_LIGHT_WAVES_PER_EU) void k_light_lights(LightsParams q)
+{
+        __shared__ uint2 stk[kStack * kRenderBlock];
+        const int tid = threadIdx.x;
+        const int u = chunk_place<VRT_LIGHT_CHUNK>(blockIdx.x, gridDim.x);
+        if (u >= q.units)
+                return;
+        const LightEntry &e = q.e[__builtin_amdgcn_readfirstlane(lights_find(q, u))];  // block-uniform
+        int px, py, s;
+        lights_lane_at(q, e, u, tid, px, py, s);
+        const RayK r = lights_ray(e, px, py, s);
+        MarchResult m;
+        if (q.p.r.test_flags & VRT_TEST_LIGHT_TAIL)
+                m.deferred = true;  // test hook: every sample to k_light_lights_tail
+        else
+                ray_march_dispatch<false, kRenderBlock, 1, kR64, VRT_LIGHT_BUDGET>(q.p.r.sc, r, stk + tid, nullptr,
+                                                                                     nullptr, m);
+        if (m.deferred) {
+                const uint32_t j = atomicAdd(q.p.tail_n, 1u);
+                q.p.tail[j] = (uint32_t)u << 6 | (uint32_t)tid;  // the global unit: the tail finds the light again
+                return;
+        }
+        if (m.hit)
+                lights_record(q, e, r, m, px, py, s);
+}
+
+// k_light_tail over the deferred samples of all lights: a slot's global unit
+// gives its light and tile as in the march (per lane group here)
+template <bool kR64>
+__global__ __launch_bounds__(64, VRT_TAIL_WAVES_PER_EU) void k_light_lights_tail(LightsParams q)
+{
+        constexpr int kG = VRT_LIGHT_TAIL_G, kR = 64 / kG;
+        __shared__ uint2 stk[kStack * 64];
+        const uint32_t n = *q.p.tail_n;
+        const uint32_t gl = threadIdx.x & (kG - 1);
+        for (uint32_t i0 = blockIdx.x * kR; i0 < n; i0 += gridDim.x * kR) {
+                const uint32_t i = i0 + threadIdx.x / kG;
+                if (i < n) {  // whole groups
+                        const uint32_t slot = q.p.tail[i];
+                        const int u = (int)(slot >> 6);
+                        const LightEntry &e = q.e[lights_find(q, u)];
+                        int px, py, s;
+                        lights_lane_at(q, e, u, (int)(slot & 63), px, py, s);
+                        const RayK r = lights_ray(e, px, py, s);
+                        MarchResult m;
+                        ray_march_dispatch<false, 64, kG, kR64>(q.p.r.sc, r, stk + threadIdx.x, nullptr, nullptr, m);
+                        if (m.hit && gl == 0)
+                                lights_record(q, e, r, m, px, py, s);
+                }
+        }
+}
+
 // A hit list merged from several ranks' lists (the sharded light pass of the
 // multi-device handle): each record's slot is its position in the merged list.
 __global__ __launch_bounds__(256) void k_lm_slots(int64_t n, uint32_t *__restrict__ vals)
@@ -5952,6 +6061,20 @@ hipError_t launch_light(const LightParams &p, hipStream_t st)
         return hipGetLastError();
 }
 
+// one march and one tail launch whatever q.nlights is
+hipError_t launch_light_lights(const LightsParams &q, hipStream_t st)
+{
+        if (q.units <= 0)
+                return hipSuccess;
+        const int grid = (q.units + 7) & ~7;
+        hipLaunchKernelGGL(q.p.r.sc.wide_leaves ? k_light_lights<true> : k_light_lights<false>, dim3(grid),
+                           dim3(kRenderBlock), 0, st, q);
+        if (VRT_LIGHT_BUDGET > 0 || (q.p.r.test_flags & VRT_TEST_LIGHT_TAIL))
+                hipLaunchKernelGGL(q.p.r.sc.wide_leaves ? k_light_lights_tail<true> : k_light_lights_tail<false>,
+                                   dim3(VRT_LIGHT_TAIL_GRID), dim3(64), 0, st, q);
+        return hipGetLastError();
+}
+
 hipError_t launch_lm_slots(uint32_t *vals, int64_t n, hipStream_t st)
 {
         if (n <= 0)
@@ -6224,6 +6347,8 @@ bool build_flag(const char *name, int64_t *value)
                 { "VRT_DEAL_WEIGHT", VRT_DEAL_WEIGHT },
                 { "VRT_DEAL_SPAN", VRT_DEAL_SPAN },
                 { "VRT_LIGHT_BUDGET", VRT_LIGHT_BUDGET },
+                { "VRT_MAX_LIGHTS", VRT_MAX_LIGHTS },
+                { "VRT_SIZEOF_LIGHT", (int64_t)sizeof(vrt_light) },
                 { "VRT_PRIM_BUDGET", VRT_PRIM_BUDGET },
                 { "VRT_CHAIN_ORDER", VRT_CHAIN_ORDER },
                 { "VRT_BEAM_ENTRY", VRT_BEAM_ENTRY },

@@ -490,6 +490,32 @@ int trace_frame_multi(vrt_multi *m, const char *what, const vrt_camera *light_ca
                          [&](const std::vector<float *> &dst) { return trace_work(m, a, dst, hits); });
 }
 
+// the frame calls over a light list (vrt_lightmap_build_lights); cam ==
+// nullptr: the light map alone
+FrameArgs frame_args_lights(const char *what, const vrt_light *lights, int nlights, const float *probe_light_color,
+                            const vrt_camera *cam, const vrt_film *film, float min_voxel)
+{
+        FrameArgs a = frame_args(what, nullptr, nullptr, probe_light_color, cam, film, min_voxel);
+        a.lights = lights;
+        a.nlights = nlights;
+        return a;
+}
+
+int trace_frame_lights_multi(vrt_multi *m, const char *what, const vrt_light *lights, int nlights,
+                             const float *probe_light_color, const vrt_camera *cam, const vrt_film *film,
+                             float min_voxel, float *rgb, float *d_image, void *stream, int64_t *hits)
+{
+        if (!m || !lights || !cam || !film || !(rgb || d_image))
+                return set_error(VRT_E_INVALID, "null argument");
+        if (int rc = lights_ok(lights, nlights))
+                return rc;
+        const FrameArgs a = frame_args_lights(what, lights, nlights, probe_light_color, cam, film, min_voxel);
+        if (int rc = frame_check(m->sc[0], a))  // as every rank would, before anything is enqueued
+                return rc;
+        return frame_out(m, film, 3, rgb, d_image, stream,
+                         [&](const std::vector<float *> &dst) { return trace_work(m, a, dst, hits); });
+}
+
 int render_trace_multi(vrt_multi *m, const char *what, const vrt_camera *cam, const vrt_film *film, float min_voxel,
                        float *rgb, float *d_image, void *stream)
 {
@@ -987,6 +1013,41 @@ extern "C" int vrt_lightmap_build_multi(vrt_multi *m, const vrt_camera *light_ca
                 if (int rc = scene_stream_sync(s))
                         return rc;
         return VRT_OK;
+}
+
+extern "C" int vrt_lightmap_build_lights_multi(vrt_multi *m, const vrt_light *lights, int nlights, int64_t *hits)
+{
+        if (!m || !lights)
+                return set_error(VRT_E_INVALID, "null argument");
+        if (int rc = lights_ok(lights, nlights))
+                return rc;
+        std::lock_guard<std::mutex> lk(m->mu);
+        DeviceGuard g;
+        const FrameArgs a = frame_args_lights("vrt_lightmap_build_lights_multi", lights, nlights, nullptr, nullptr,
+                                              nullptr, 0.f);
+        if (int rc = trace_work(m, a, std::vector<float *>(m->sc.size(), nullptr), hits))
+                return rc;
+        for (vrt_scene *s : m->sc)  // every rank's map is built on return
+                if (int rc = scene_stream_sync(s))
+                        return rc;
+        return VRT_OK;
+}
+
+extern "C" int vrt_trace_frame_lights_multi(vrt_multi *m, const vrt_light *lights, int nlights,
+                                            const float *probe_light_color, const vrt_camera *cam,
+                                            const vrt_film *film, float min_voxel, float *rgb, int64_t *hits)
+{
+        return trace_frame_lights_multi(m, "vrt_trace_frame_lights_multi", lights, nlights, probe_light_color, cam, film,
+                                        min_voxel, rgb, nullptr, nullptr, hits);
+}
+
+extern "C" int vrt_trace_frame_lights_multi_device(vrt_multi *m, const vrt_light *lights, int nlights,
+                                                   const float *probe_light_color, const vrt_camera *cam,
+                                                   const vrt_film *film, float min_voxel, float *d_image,
+                                                   void *stream, int64_t *hits)
+{
+        return trace_frame_lights_multi(m, "vrt_trace_frame_lights_multi_device", lights, nlights, probe_light_color,
+                                        cam, film, min_voxel, nullptr, d_image, stream, hits);
 }
 
 extern "C" int vrt_render_trace_multi(vrt_multi *m, const vrt_camera *cam, const vrt_film *film, float min_voxel,
