@@ -326,7 +326,7 @@ int vrt_device_selftest(int device, const double *mt_in, double *mt_out,
 #define VRT_TEST_SMALL_PROBE_CHUNK 0x20000
 /* VRT_TEST_SMALL_BEAM_ENTRY: the persistent primary render takes the beam
  * entry for a one-rank frame of any size; without it only
- * frames of at least 65,536 units (4x4-pixel quadrants) do, because the
+ * frames of at least 32,640 units (4x4-pixel quadrants) do, because the
  * pre-pass costs a small frame more than it saves. */
 #define VRT_TEST_SMALL_BEAM_ENTRY 0x40000
 /* VRT_TEST_UPDATE_TOO_LARGE makes the device build of vrt_scene_update[_device]

@@ -217,12 +217,15 @@ constexpr uint32_t kEntryNone = 0xFFFFFFFFu;
 constexpr uint32_t kEntryCountMask = 0xFFu;
 constexpr uint32_t kEntryChainBit = 0x100u;
 // Smallest one-rank frame that takes the entry.  The pre-pass is one long
-// dependent chain per lane (64 rays, then ~10 visits): 0.07-0.11 ms alone at
-// 1080p (kernel trace), whatever the size, against a quarter of the render's
-// time saved.  Measured with 3 frames in flight: 8,160 units 0.180 -> 0.216
-// ms per frame, 32,640 units 0.310 -> 0.312, 129,600 units 0.86 -> 0.72
-// (DESIGN §4.1).  VRT_TEST_SMALL_BEAM_ENTRY lifts the limit.
-constexpr int64_t kEntryMinUnits = 65536;
+// dependent chain per lane (64 rays, then ~10 visits), whatever the size,
+// against a quarter of the render's time saved.  Measured with 3 frames in
+// flight, without -> with the entry: 8,160 units 0.180 -> 0.216 ms per frame
+// and 129,600 units 0.86 -> 0.72 with the first pre-pass; 32,640 units
+// (960x544) 0.310 -> 0.312 with it and 0.3173 -> 0.3023 with the present one
+// (115 instead of 190 VALU per ray), whose margin of 0.010 ms exceeds the
+// spread of 0.007: the limit is that frame's size, the smallest measured to
+// win.  VRT_TEST_SMALL_BEAM_ENTRY lifts the limit.
+constexpr int64_t kEntryMinUnits = 32640;
 // units of slice x: a contiguous range [lo, hi) of the unit order
 __host__ __device__ inline void queue_range(int units, int x, int &lo, int &hi)
 {

@@ -2357,6 +2357,7 @@ __global__ __launch_bounds__(kPersistBlock, VRT_PERSIST_WAVES_PER_EU) void k_ren
                 const int units = p.tiles_this_rank * 4, n = slice_size(units, x, VRT_SLICE_CHUNK);
                 if (n <= 0)
                         continue;
+                bool over = false;  // wave-uniform: this slice's deferred count seen past the cap
                 for (;;) {
 #if VRT_PHASE_STAMPS
                         const unsigned long long d_q0 = __builtin_amdgcn_s_memtime();
@@ -2396,12 +2397,15 @@ __global__ __launch_bounds__(kPersistBlock, VRT_PERSIST_WAVES_PER_EU) void k_ren
                         // vote): the append is one whole-wave take_unit, never
                         // a lane-0-only atomic inside this loop, and every lane
                         // stores the same word
-                        if (!done) {
-                                // past the cap the slice is re-rendered whole: no more appends
+                        if (!done && !over) {
+                                // past the cap the slice is re-rendered whole: no more appends,
+                                // and (the count only grows) no more reads of the count by a
+                                // wave that has seen it there
                                 uint32_t *cnt = p.q.defer + x * kQueueStride + kDeferCount;
                                 const uint32_t c = __builtin_amdgcn_readfirstlane(
                                         __hip_atomic_load(cnt, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT));
-                                if (c <= (uint32_t)kDeferSliceCap) {
+                                over = c > (uint32_t)kDeferSliceCap;
+                                if (!over) {
                                         const uint32_t d = take_unit(cnt);
                                         if (d < (uint32_t)kDeferSliceCap)
                                                 p.q.defer[kDeferList + x * kDeferSliceCap + d] = (uint32_t)kq;
@@ -2529,36 +2533,89 @@ __global__ __launch_bounds__(64) void k_unit_entry(RenderParams p, ChainW cw, ui
         uint32_t a, b;
         load_node(p.sc.nodes, 0, rmin, rmax, a, b);
         const float o[3] = { c.origin[0], c.origin[1], c.origin[2] };
-        float dlo[3] = { 0.f, 0.f, 0.f }, dhi[3] = { 0.f, 0.f, 0.f };
-        uint32_t s_or = 0u, s_and = 7u;
-        bool ok = p.sc.fast_ok != 0, chain = true;
+        // The 64 directions, made with camera_dir's own operations on the same
+        // operands; the loop runs sample by sample so that each of the unit's
+        // 16 + 16 film coordinates (4 columns / 4 rows x 4 samples) is divided
+        // once.  Kept per axis: the smallest and largest component (the loop's
+        // order does not matter to a minimum), and per ray only what has no
+        // monotone shortcut: the chain criterion, and a length that is neither
+        // 0, infinite nor NaN -- any other length leaves every component finite
+        // and not NaN, which the NaN-dropping fminf / fmaxf need; a ray with
+        // such a length fails fast_ok or fin_ok (each component is NaN, +-inf
+        // or 0).
+        float dmn[3] = { INFINITY, INFINITY, INFINITY }, dmx[3] = { -INFINITY, -INFINITY, -INFINITY };
+        bool lenok = true, chain = true;
+        const int px0 = tx * 8 + (wave & 1) * 4, py0 = ty * 8 + (wave >> 1) * 4;
 #pragma unroll 1
-        for (int l = 0; l < 64; ++l) {
-                const int s = l & 3, pix = l >> 2;
-                const int px = tx * 8 + (wave & 1) * 4 + (pix & 3);
-                const int py = ty * 8 + (wave >> 1) * 4 + (pix >> 2);
-                const f3 dn = camera_dir(c.s, c.u, c.nf, c.e, c.z, c.nx, c.ny, px, py, sample_x(s), sample_y(s));
-                const RayK r = make_rayk(mk3(o[0], o[1], o[2]), dn, c.tmin, c.tmax);
-                ok = ok && fast_ok(r) && __float_as_uint(r.tmin) == 0u && r.tmax == kFltMax && fin_ok(r);
-                chain = chain && chain_criterion(rmin, rmax, r, cw.wmin);
-                const uint32_t cs = chain_signs(r);
-                s_or |= cs;
-                s_and &= cs;
-                const float di[3] = { r.dinv.x, r.dinv.y, r.dinv.z };
+        for (int s = 0; s < 4; ++s) {
+                const float sx = sample_x(s), sy = sample_y(s);
+                float xs[4];
 #pragma unroll
-                for (int q = 0; q < 3; ++q) {
-                        dlo[q] = l ? fminf(dlo[q], di[q]) : di[q];
-                        dhi[q] = l ? fmaxf(dhi[q], di[q]) : di[q];
+                for (int i = 0; i < 4; ++i)
+                        xs[i] = ((float)(px0 + i - c.nx / 2) + sx) / (float)c.nx;
+#pragma unroll 1
+                for (int j = 0; j < 4; ++j) {
+                        const float y_ = ((float)((c.ny - 1 - (py0 + j)) - c.ny / 2) + sy) / (float)c.ny;
+                        // (not unrolled: four rays interleaved cost 20 more registers)
+#pragma unroll 1
+                        for (int i = 0; i < 4; ++i) {
+                                const float x_ = i == 0 ? xs[0] : i == 1 ? xs[1] : i == 2 ? xs[2] : xs[3];
+                                float dv[3];
+#pragma unroll
+                                for (int q = 0; q < 3; ++q) {
+                                        float acc = 0.0f;
+                                        acc += c.s[q] * x_;
+                                        acc += c.u[q] * y_;
+                                        acc += c.nf[q] * c.z;
+                                        acc += c.e[q] * 0.0f;
+                                        dv[q] = acc;
+                                }
+                                const float len = length(mk3(dv[0], dv[1], dv[2]));
+                                lenok = lenok && len > 0.0f && len <= kFltMax;
+                                const float d[3] = { dv[0] / len, dv[1] / len, dv[2] / len };
+                                RayK r;  // chain_criterion reads o and d only
+                                r.o = mk3(o[0], o[1], o[2]);
+                                r.d = mk3(d[0], d[1], d[2]);
+                                chain = chain && chain_criterion(rmin, rmax, r, cw.wmin);
+#pragma unroll
+                                for (int q = 0; q < 3; ++q) {
+                                        dmn[q] = fminf(dmn[q], d[q]);
+                                        dmx[q] = fmaxf(dmx[q], d[q]);
+                                }
+                        }
                 }
         }
-        if (!ok || s_or != s_and || (a & kLeafBit) ||
-            beam_box(rmin, rmax, o, dlo, dhi, true) != 1) {
+        // fast_ok and fin_ok of all 64 rays from the extremes: per component
+        // they ask for d == 0 or FLT_MIN <= |d| < 2^64, and |dinv| <= 2^64,
+        // which a zero fails (dinv_of(0) = 2^126).  A unit with a zero or with
+        // both signs on an axis gets "no entry" (as s_or != s_and did): then an
+        // extreme is zero or the extremes' signs differ.  Otherwise the axis's
+        // components have one sign and lie between extremes that pass; |d|'s
+        // tests are thresholds, and fl(1 / d), a correctly rounded division, is
+        // monotone non-increasing on one sign, so every ray's |dinv| passes with
+        // the extremes' -- and the smallest and largest dinv of the 64 rays are
+        // exactly dinv_of(largest d) and dinv_of(smallest d): 6 divisions.
+        bool ok = p.sc.fast_ok != 0 && lenok && __float_as_uint(c.tmin) == 0u && c.tmax == kFltMax;
+        float dlo[3], dhi[3];
+        uint32_t cs = 0u;
+#pragma unroll
+        for (int q = 0; q < 3; ++q) {
+                ok = ok && fabsf(o[q]) < 0x1p60f;
+                const float amn = fabsf(dmn[q]), amx = fabsf(dmx[q]);
+                ok = ok && amn >= kFltMin && amn < 0x1p64f && amx >= kFltMin && amx < 0x1p64f;
+                ok = ok && (__float_as_uint(dmn[q]) >> 31) == (__float_as_uint(dmx[q]) >> 31);
+                cs |= (__float_as_uint(dmn[q]) >> 31) << (2 - q);
+                // a failed axis divides whatever it holds: `ok` discards it
+                dlo[q] = 1.f / dmx[q];
+                dhi[q] = 1.f / dmn[q];
+                ok = ok && fabsf(dlo[q]) <= 0x1p64f && fabsf(dhi[q]) <= 0x1p64f;
+        }
+        if (!ok || (a & kLeafBit) || beam_box(rmin, rmax, o, dlo, dhi, true) != 1) {
                 rec[0] = kEntryNone;
                 return;
         }
         const RayK ro = make_rayk(mk3(o[0], o[1], o[2]), mk3(0.f, 0.f, 0.f), 0.f, 0.f);
         const bool lbok = leaf_box_ok(p.sc, ro);  // the origin alone decides
-        const uint32_t cs = s_or;
         // the root's expansion, then ray_march's loop; (sp, base, order, cnt)
         // is the loop-top state, stack entries 0 .. sp - 1 lie in the record
         int sp = 0, cnt = 0;
@@ -4400,6 +4457,13 @@ hipError_t launch_render(const RenderParams &p, bool instrumented,
                 // a caller with frames in flight (vrt_scene_set_frames_in_flight)
                 // gets 1/grid_div of the resident slots per frame
                 const int full = (p.sc.persist_blocks / std::max(1, p.sc.grid_div)) & ~7;
+                // (no such reserve for the beam pre-pass of one-rank frames in
+                // flight: it does wait for slots -- with two renders holding every
+                // slot its dispatch lasts 0.35-1.07 ms instead of 0.1 -- but the two
+                // renders keep the chip busy meanwhile, and 64 / 128 / 256 slots
+                // left free per frame measured 0.5365 / 0.5295 / 0.5565 ms per
+                // frame against 0.5332 without, and no faster on the bench's lines:
+                // DESIGN appendix)
                 const int cap = std::max(8, p.nranks > 1 ? full - kCollectiveReserve : full);
                 const int g = std::min(cap, need);
                 if (kind == kRenderPersistFast) {
