@@ -373,6 +373,8 @@ struct ora_scene {
         float *lm_illum;  /* VoxelOctree::illum[6] per node, 18 floats */
 };
 
+_Static_assert(sizeof(onode) % sizeof(float) == 0, "onode stride in floats");
+
 static int new_node(ora_scene *s)
 {
         if (s->nnodes == s->capnodes) {
@@ -396,6 +398,19 @@ static int tri_overlap(const ora_scene *s, int tri, const float b[6])
         return 1 == ora_tri_box_overlap(c, h, s->p + 9 * tri);
 }
 
+/* split()'s box of child i: VRT/voxel_octree.cc:30-35 */
+static void child_box(const float box[6], int i, float out[6])
+{
+        float half[3];
+        for (int k = 0; k < 3; ++k)
+                half[k] = (box[3 + k] - box[k]) / 2; /* size()/2 */
+        int m[3] = { (i & 4) ? 1 : 0, (i & 2) ? 1 : 0, (i & 1) ? 1 : 0 };
+        for (int k = 0; k < 3; ++k) {
+                out[k] = box[k] + (float)m[k] * half[k];
+                out[3 + k] = out[k] + half[k];
+        }
+}
+
 /* split(): VRT/voxel_octree.cc:27-39 */
 static void split(ora_scene *s, int ni)
 {
@@ -406,16 +421,10 @@ static void split(ora_scene *s, int ni)
                         first = c;
         }
         onode *nd = &s->nodes[ni];
-        float half[3];
-        for (int k = 0; k < 3; ++k)
-                half[k] = (nd->box[3 + k] - nd->box[k]) / 2; /* size()/2 */
         for (int i = 0; i < 8; ++i) {
                 onode *c = &s->nodes[first + i];
                 int m[3] = { (i & 4) ? 1 : 0, (i & 2) ? 1 : 0, (i & 1) ? 1 : 0 };
-                for (int k = 0; k < 3; ++k) {
-                        c->box[k] = nd->box[k] + (float)m[k] * half[k];
-                        c->box[3 + k] = c->box[k] + half[k];
-                }
+                child_box(nd->box, i, c->box);
                 c->depth = nd->depth + 1;
                 c->ix = nd->ix * 2 + m[0];
                 c->iy = nd->iy * 2 + m[1];
@@ -573,6 +582,15 @@ void ora_scene_info(const ora_scene *s, int64_t info[5], float root_box[6])
 }
 
 static const ora_scene *g_sort_scene;
+void ora_scene_boxes(const ora_scene *s, uint64_t *key, float *box)
+{
+        for (int i = 0; i < s->nnodes; ++i) {
+                const onode *n = &s->nodes[i];
+                key[i] = ((uint64_t)n->depth << 32) | vox_key(n);
+                memcpy(box + 6 * (size_t)i, n->box, sizeof n->box);
+        }
+}
+
 static int cmp_leaf(const void *a, const void *b)
 {
         uint32_t ka = vox_key(&g_sort_scene->nodes[*(const int *)a]);
@@ -712,17 +730,35 @@ int ora_first_min(const float *depth, int n)
 
 /* travorder (VRT/voxel_octree.cc:77-97): dot(ray.d, child.center() - ray.o)
  * for the 8 children, then the std::sort above */
-static void travorder(const ora_scene *s, const onode *nd, const float r[8],
-                      int ord[8])
+static void travorder_boxes(const float *child, int stride, const float r[8],
+                            int ord[8])
 {
         float dist[8];
         v3 o = vget(r), d = vget(r + 3);
         for (int ci = 0; ci < 8; ++ci) {
-                const float *b = s->nodes[nd->child + ci].box;
+                const float *b = child + (size_t)ci * stride;
                 v3 c = muls(add(vget(b), vget(b + 3)), .5f); /* center() */
                 dist[ci] = dot(d, sub(c, o));
         }
         ora_sort8(dist, ord);
+}
+
+static void travorder(const ora_scene *s, const onode *nd, const float r[8],
+                      int ord[8])
+{
+        travorder_boxes(s->nodes[nd->child].box, sizeof(onode) / sizeof(float),
+                        r, ord);
+}
+
+void ora_travorder(const float box[6], const float ray[8], int ord[8],
+                   float child[48])
+{
+        float cb[48];
+        for (int i = 0; i < 8; ++i)
+                child_box(box, i, cb + 6 * i);
+        travorder_boxes(cb, 6, ray, ord);
+        if (child)
+                memcpy(child, cb, sizeof cb);
 }
 
 static int ray_march(const ora_scene *s, const float r[8], omarch *m)
@@ -1476,6 +1512,42 @@ static v3 trace_sample(const ora_scene *s, const float r[8], float res,
         const v3 albedo = get_albedo(s, m->tri, m->is.hit);
         const v3 l = add(indirect, direct);
         return mk(albedo.x * l.x, albedo.y * l.y, albedo.z * l.z);
+}
+
+void ora_cone_trace(const ora_scene *s, const float *isects, int n,
+                    float min_voxel, float *out)
+{
+        for (int i = 0; i < n; ++i) {
+                const float *q = isects + 6 * (size_t)i;
+                v3 c = cone_trace_isect(s, vget(q), vget(q + 3), min_voxel);
+                out[3 * i + 0] = c.x;
+                out[3 * i + 1] = c.y;
+                out[3 * i + 2] = c.z;
+        }
+}
+
+static void put3(float *p, v3 v)
+{
+        p[0] = v.x;
+        p[1] = v.y;
+        p[2] = v.z;
+}
+
+void ora_hit_pieces(const ora_scene *s, const float *rays, int n,
+                    float *diffuse, float *albedo, float *illum)
+{
+        for (int i = 0; i < n; ++i) {
+                const float *r = rays + 8 * (size_t)i;
+                omarch m;
+                const v3 zero = mk(0, 0, 0);
+                int h = ray_march(s, r, &m);
+                if (diffuse)
+                        put3(diffuse + 3 * i, h ? shade_sample(s, r, 1, &m) : zero);
+                if (albedo)
+                        put3(albedo + 3 * i, h ? get_albedo(s, m.tri, m.is.hit) : zero);
+                if (illum)
+                        put3(illum + 3 * i, h && s->lm_illum ? compute_illum(s, m.leaf, neg(vget(r + 3))) : zero);
+        }
 }
 
 void ora_shade_trace(const ora_scene *s, const float *rays, int n, float res,

@@ -13,14 +13,13 @@
  *     from /root/reference into oracle/_ref (tests/golden/kat_*.npz).
  *   - The HDR writer is checked against the reference's stb_image_write.h
  *     compiled unmodified into oracle/_ref (tests/golden/hdr_*.npz).
- *   - Camera / AABB / octree build / traversal / shading depend on
- *     graphics_math.h, which this image's g++/libstdc++ cannot compile without
- *     editing the reference source (MSVC-only token pasting,
- *     graphics_math.h:264-319) and supplying C++17 std:: math names
- *     libstdc++ 11 lacks (graphics_math.h:579,1037).  Those functions are
- *     therefore a cited restatement whose end-to-end parity is
- *     "parity unpinned" against a running reference; their floating-point
- *     leaves (MT, SAT) are pinned as above.
+ *   - Camera / AABB / octree build / traversal / shading / light map / cone
+ *     trace are pinned bit-exactly against the reference's own camera.cc and
+ *     voxel_octree.cc, compiled unmodified by clang++ in MSVC-compatibility
+ *     mode into oracle/_ref/libvrtref_gi.so (oracle/Makefile,
+ *     tests/test_reference_gi_host.py, tests/golden/ref_gi_*.npz).  The
+ *     remaining caveat is the C library: glibc's libm here, the MSVC CRT in
+ *     the reference's own build.
  *
  * Citations: VRT/x = /root/reference/VoxelRayTrace20190722/x
  */
@@ -64,6 +63,10 @@ int ora_aabb_isect(const float box[6], const float ray[8]);
 /* travorder's std::sort of the 8 (ci, dist) Items and ray_march_isect's
  * std::min_element, on arbitrary inputs (VRT/voxel_octree.cc:91-93,122-125) */
 void ora_sort8(const float dist[8], int ord[8]);
+/* travorder (VRT/voxel_octree.cc:77-97) on a node of `box` whose children are
+ * split()'s (VRT/voxel_octree.cc:27-39); child (may be NULL): their boxes. */
+void ora_travorder(const float box[6], const float ray[8], int ord[8],
+                   float child[48]);
 int ora_first_min(const float *depth, int n);
 
 /* Scene: triangles as built by Triangle::Triangle (VRT/voxel_octree.cc:423-431).
@@ -81,6 +84,9 @@ void ora_scene_set_materials(ora_scene *s, int nmat, const int32_t *mat_tex,
 void ora_scene_destroy(ora_scene *s);
 /* info[0]=nodes [1]=internal [2]=leaves(all) [3]=nonempty leaves [4]=refs */
 void ora_scene_info(const ora_scene *s, int64_t info[5], float root_box[6]);
+/* Every node (oracle order): key = depth<<32 | ix | iy<<10 | iz<<20 at its
+ * depth (root depth 1), and its box {min, max}. */
+void ora_scene_boxes(const ora_scene *s, uint64_t *key, float *box);
 /* Non-empty leaves sorted by voxel key (ix | iy<<10 | iz<<20 at max depth):
  * vox[nl], cnt[nl], tris[refs] (concatenated lists, input order). */
 void ora_scene_leaves(const ora_scene *s, uint32_t *vox, uint32_t *cnt,
@@ -159,6 +165,15 @@ void ora_lightmap_nodes(const ora_scene *s, uint64_t *key, float *cov,
                         float *illum);
 /* min component of root.size() / powf(2, levels) (VRT/main.cc:69-70). */
 float ora_min_voxel(const ora_scene *s, int levels);
+/* gi::cone_trace(root, isect, min_voxel) (VRT/voxel_octree.cc:286-303) at n
+ * isects {hit[3], normal[3]} taken as they are, on the current light map. */
+void ora_cone_trace(const ora_scene *s, const float *isects, int n,
+                    float min_voxel, float *out);
+/* The pieces trace() and the light block take per hit (any may be NULL; +0 on
+ * a miss): Triangle::get_diffuse(isect, ray, (1,1,1)), get_albedo(isect) and
+ * leaf->compute_illum(-ray.d) on the current light map (+0 without one). */
+void ora_hit_pieces(const ora_scene *s, const float *rays, int n,
+                    float *diffuse, float *albedo, float *illum);
 /* trace(root, ray, 5, true) per ray (VRT/main.cc:10-30): sky on a miss,
  * else get_albedo * (cone_trace(root, isect, res) + leaf compute_illum(-d)). */
 void ora_shade_trace(const ora_scene *s, const float *rays, int n, float res,

@@ -3,6 +3,7 @@
 
     python tests/golden/make_golden.py          # everything
     python tests/golden/make_golden.py ingest   # ingest_ref.npz only
+    python tests/golden/make_golden.py ref_gi   # ref_gi_*.npz only
 
 * kat_raytri.npz / kat_tribox.npz / hdr_ref.npz -- outputs of the
   REFERENCE's own raytri.cc, tribox2.cc and stb_image_write.h, compiled
@@ -14,6 +15,16 @@
 * ingest_ref.npz -- tinyobj::LoadObj and stbi_load outputs of the
   REFERENCE (tiny_obj_loader.cc / stb_image.h compiled unmodified into
   oracle/_ref/libvrtref.so) on the tests/ingest_corpus.py inputs.
+* ref_gi_march.npz / ref_gi_light.npz / ref_gi_probes.npz -- outputs of the
+  REFERENCE's own camera.cc and voxel_octree.cc (compiled unmodified into
+  oracle/_ref/libvrtref_gi.so, called through oracle/ref_gi_glue.cc) on the
+  scene of scene_proxy.npz: the octree's leaves, a film's rays and a ray
+  batch with ray_march's ids, hit points, normals, get_diffuse and get_albedo;
+  the node records of two light maps; cone_trace, trace()'s colours and the
+  Film at every sample; gather_light's SGs and LightProbe::eval; a probe
+  scene's leaves and its marches with even_invisible on and off.  What is
+  recorded and how is in tests/ref_gi_record.py; run this section after
+  scene_proxy.npz exists.
 Only inputs and outputs are stored -- no reference source.
 """
 import os
@@ -304,7 +315,22 @@ def ingest_fixture():
     np.savez_compressed(os.path.join(HERE, "ingest_ref.npz"), **rec)
 
 
+def ref_gi_fixture():
+    """tests/ref_gi_record.py's fixtures from oracle/_ref/libvrtref_gi.so."""
+    import tempfile
+    if not po.reference_gi_available():
+        raise SystemExit("oracle/_ref/libvrtref_gi.so missing: run `make` where the reference and clang++ exist")
+    sys.path.insert(0, os.path.join(ROOT, "tests"))
+    import ref_gi_record
+    with tempfile.TemporaryDirectory() as td:
+        for f, size in ref_gi_record.save(td).items():
+            print(f, size)
+
+
 def main():
+    if sys.argv[1:] == ["ref_gi"]:
+        ref_gi_fixture()
+        return
     if not po.reference_available():
         raise SystemExit("oracle/_ref/libvrtref.so missing: run `make` where /root/reference exists")
     if sys.argv[1:] == ["ingest"]:
@@ -341,6 +367,7 @@ def main():
     seeds, draws, pts = pcg_std()
     np.savez_compressed(os.path.join(HERE, "pcg_std.npz"), seeds=seeds, draws=draws, points=pts)
     secondary_fixture(sd, 6, main_cam, (1.0, 1.0, 24, 16), 64, "proxy")
+    ref_gi_fixture()
     for f in sorted(os.listdir(HERE)):
         print(f, os.path.getsize(os.path.join(HERE, f)))
 
