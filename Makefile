@@ -18,7 +18,7 @@ CXXFLAGS := -O2 -fPIC -std=c++17 -ffp-contract=off -Iinclude -Wall -fvisibility=
 
 LIBS := -L/opt/rocm/lib -lrccl -lpthread
 HOSTOBJS := $(BLD)/vrt_host.o $(BLD)/vrt_legacy.o $(BLD)/vrt_multi.o $(BLD)/vrt_hdr.o $(BLD)/vrt_proxy.o $(BLD)/vrt_obj.o $(BLD)/vrt_tga.o
-OBJS := $(BLD)/vrt_kernels.o $(BLD)/vrt_build.o $(BLD)/vrt_digest.o $(HOSTOBJS) $(BLD)/vrt_build_id.o
+OBJS := $(BLD)/vrt_kernels.o $(BLD)/vrt_build.o $(BLD)/vrt_digest.o $(BLD)/vrt_sg.o $(HOSTOBJS) $(BLD)/vrt_build_id.o
 HDRS := include/vrt.h $(SRC)/vrt_math.h $(SRC)/vrt_internal.h $(SRC)/vrt_error.h
 
 all: $(PKG)/libvrt.so oracle
@@ -40,7 +40,12 @@ $(BLD)/vrt_build.o: $(SRC)/vrt_build.hip $(HDRS) | $(BLD)
 $(BLD)/vrt_digest.o: $(SRC)/vrt_digest.hip $(HDRS) | $(BLD)
 	$(HIPCC) $(HIPFLAGS) -c $< -o $@
 
-$(BLD)/vrt_host.o: $(SRC)/vrt_host.cpp $(HDRS) | $(BLD)
+# the SG algebra and the probes' irradiance (vrt_sg.h: the float operations
+# the host calls in vrt_host.cpp share with these kernels)
+$(BLD)/vrt_sg.o: $(SRC)/vrt_sg.hip $(SRC)/vrt_sg.h $(HDRS) | $(BLD)
+	$(HIPCC) $(HIPFLAGS) -c $< -o $@
+
+$(BLD)/vrt_host.o: $(SRC)/vrt_host.cpp $(SRC)/vrt_sg.h $(HDRS) | $(BLD)
 	$(HIPCC) $(HIPFLAGS) -c $< -o $@
 
 # the reference's primitives under their C++ (mangled) names; must not see
@@ -81,19 +86,19 @@ oracle:
 	$(MAKE) -C oracle
 
 # A/B variant of the kernels:  make variant NAME=v0 DEFS="-DVRT_CHAIN_ORDER=0"
-variant: $(HOSTOBJS) $(BLD)/vrt_build.o $(BLD)/vrt_digest.o | $(BLD)
+variant: $(HOSTOBJS) $(BLD)/vrt_build.o $(BLD)/vrt_digest.o $(BLD)/vrt_sg.o | $(BLD)
 	mkdir -p build/ab
 	$(HIPCC) $(HIPFLAGS) $(KFLAGS) $(DEFS) -c $(SRC)/vrt_kernels.hip -o build/ab/k_$(NAME).o
 	$(HIPCC) --offload-arch=$(ARCH) -shared -fPIC -o build/ab/libvrt_$(NAME).so \
-	  build/ab/k_$(NAME).o $(BLD)/vrt_build.o $(BLD)/vrt_digest.o $(HOSTOBJS) $(BLD)/vrt_build_id.o $(LIBS)
+	  build/ab/k_$(NAME).o $(BLD)/vrt_build.o $(BLD)/vrt_digest.o $(BLD)/vrt_sg.o $(HOSTOBJS) $(BLD)/vrt_build_id.o $(LIBS)
 
 # variant that also rebuilds the host side (for data-layout changes)
-fullvariant: $(BLD)/vrt_build.o $(BLD)/vrt_digest.o $(BLD)/vrt_legacy.o $(BLD)/vrt_multi.o $(BLD)/vrt_hdr.o $(BLD)/vrt_proxy.o $(BLD)/vrt_obj.o $(BLD)/vrt_tga.o | $(BLD)
+fullvariant: $(BLD)/vrt_build.o $(BLD)/vrt_digest.o $(BLD)/vrt_sg.o $(BLD)/vrt_legacy.o $(BLD)/vrt_multi.o $(BLD)/vrt_hdr.o $(BLD)/vrt_proxy.o $(BLD)/vrt_obj.o $(BLD)/vrt_tga.o | $(BLD)
 	mkdir -p build/ab
 	$(HIPCC) $(HIPFLAGS) $(KFLAGS) $(DEFS) -c $(SRC)/vrt_kernels.hip -o build/ab/k_$(NAME).o
 	$(HIPCC) $(HIPFLAGS) $(DEFS) -c $(SRC)/vrt_host.cpp -o build/ab/h_$(NAME).o
 	$(HIPCC) --offload-arch=$(ARCH) -shared -fPIC -o build/ab/libvrt_$(NAME).so \
-	  build/ab/k_$(NAME).o build/ab/h_$(NAME).o $(BLD)/vrt_build.o $(BLD)/vrt_digest.o $(BLD)/vrt_legacy.o $(BLD)/vrt_multi.o \
+	  build/ab/k_$(NAME).o build/ab/h_$(NAME).o $(BLD)/vrt_build.o $(BLD)/vrt_digest.o $(BLD)/vrt_sg.o $(BLD)/vrt_legacy.o $(BLD)/vrt_multi.o \
 	  $(BLD)/vrt_hdr.o $(BLD)/vrt_proxy.o $(BLD)/vrt_obj.o $(BLD)/vrt_tga.o $(BLD)/vrt_build_id.o $(LIBS)
 
 # ISA listing + register/occupancy report of the kernels (for DESIGN.md)

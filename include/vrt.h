@@ -873,6 +873,74 @@ int vrt_probe_eval_device(int device, const vrt_sg *d_sgs, int64_t n, const floa
 int vrt_probe_shade_hits_device(vrt_scene *s, const vrt_hit *d_hits, int64_t n, float *d_rgb, float *d_albedo,
                                 void *stream);
 
+/* ---- the SG algebra (VRT/voxel_octree.cc:497-528) --------------------------
+ * gi::SG's constructor, SG::integral, gi::prod and gi::inner_prod, batched:
+ * element i of every output comes from element i of the inputs.  Records are
+ * used as they are (nothing is re-normalised on input, as vrt_probe_eval).
+ * Everything is float32 with one rounding per operation in the reference's
+ * order: jql::dot a sequential sum from zero, jql::length = sqrtf(dot),
+ * `2 * jql::pi` formed first with jql::pi the float, SG::integral's
+ * unqualified exp the float expf.  Non-finite results are the reference's
+ * (sharpness 0 gives inf * 0 = NaN); a NaN's sign bit is not specified.
+ * n == 0 is VRT_OK and touches nothing; n < 0 or a NULL array is
+ * VRT_E_INVALID.  The host calls use the C library's expf. */
+/* SG{a, d, s}: out[i] = {a, d / length(d), s}.  a, d: 3n floats, s: n. */
+int vrt_sg_make(const float *a, const float *d, const float *s, int64_t n, vrt_sg *out);
+/* SG::integral: rgb[3i..] = 2 * pi * (a / s) * (1.0f - expf(-2.0f * s)) */
+int vrt_sg_integral(const vrt_sg *sgs, int64_t n, float *rgb /* 3n */);
+/* gi::prod: with d = (lhs.s * lhs.d + rhs.s * rhs.d) / lm, lm = lhs.s + rhs.s
+ * and dl = length(d): out[i] = SG{lhs.a * rhs.a * expf(lm * (dl - 1)), d,
+ * lm * dl} through the constructor (axis d / length(d)) */
+int vrt_sg_prod(const vrt_sg *lhs, const vrt_sg *rhs, int64_t n, vrt_sg *out);
+/* gi::inner_prod: with uml = length(lhs.s * lhs.d + rhs.s * rhs.d):
+ * rgb[3i..] = (2.0f * pi * (expf(uml - lhs.s - rhs.s) * lhs.a * rhs.a) *
+ * (1.0f - expf(-2.0f * uml))) / uml */
+int vrt_sg_inner_prod(const vrt_sg *lhs, const vrt_sg *rhs, int64_t n, float *rgb /* 3n */);
+/* The same over device arrays on `device`, enqueued on `stream` with no host
+ * synchronisation: the same float operations with the model's expf of the
+ * detected flavour (vrt_expf_flavour; -1: VRT_E_INVALID), so the host calls'
+ * bytes. */
+int vrt_sg_integral_device(int device, const vrt_sg *d_sgs, int64_t n, float *d_rgb, void *stream);
+int vrt_sg_prod_device(int device, const vrt_sg *d_lhs, const vrt_sg *d_rhs, int64_t n, vrt_sg *d_out,
+                       void *stream);
+int vrt_sg_inner_prod_device(int device, const vrt_sg *d_lhs, const vrt_sg *d_rhs, int64_t n, float *d_rgb,
+                             void *stream);
+
+/* ---- the light a scene's probes send to a point ---------------------------
+ * For element i, with p = isects[i].hit_p and the lobe q = SG{lobe_a,
+ * isects[i].normal, lobe_s} through the constructor (a zero normal gives a
+ * NaN axis, as the reference's would):
+ *  - p outside the root box (min <= p <= max on every axis; a NaN fails):
+ *    count = 0, rgb = +0.
+ *  - Otherwise the leaf of p: from the root, child 4 * (p.x > c.x) + 2 *
+ *    (p.y > c.y) + (p.z > c.z) with c = aabb.center() = (min + max) * .5f,
+ *    gi::cone_trace's descent (VRT/voxel_octree.cc:261-269) without its level
+ *    limit.  A leaf above max_depth or without probes: count = 0, rgb = +0.
+ *  - acc = 0; for each probe k of the leaf's probe list in list order
+ *    (vrt_scene_probe_leaves'), for its lobes j = 0..13 in order: acc +=
+ *    inner_prod(stored SG 14 k + j, q), componentwise; rgb = acc /
+ *    (float)count, count = the list's length: the plain mean, the shape of
+ *    gather_light's litness /= (float)size.
+ * The stored SGs are vrt_scene_probe_sgs'; no light map is needed.  lobe_a
+ * (float[3]) and lobe_s are the caller's: the two constants are the usual
+ * one-lobe fit of a clamped cosine.  count (n, may be NULL) receives the list
+ * lengths.  n == 0 is VRT_OK and touches nothing.  VRT_E_INVALID on a scene
+ * without probes, n < 0 or a NULL isects / lobe_a / rgb.
+ * The host-array call runs on the host, from the scene's host arrays and the
+ * C library's expf, on a device scene and on a host-only one alike (it first
+ * fetches the stored SGs if a device gather wrote them last).  The device call
+ * (device arrays; VRT_E_NODEVICE on a host-only scene, VRT_E_INVALID with
+ * expf flavour -1) is enqueued on `stream` with no host synchronisation,
+ * ordered behind the scene's work in flight as vrt_probe_shade_hits_device
+ * is, reads the stored SGs current in stream order, and gives the host
+ * call's bytes. */
+#define VRT_SG_COSINE_AMPLITUDE 1.17f
+#define VRT_SG_COSINE_SHARPNESS 2.133f
+int vrt_probe_irradiance(vrt_scene *s, const vrt_isect *isects, int64_t n, const float lobe_a[3], float lobe_s,
+                         float *rgb /* 3n */, int32_t *count /* n, may be NULL */);
+int vrt_probe_irradiance_device(vrt_scene *s, const vrt_isect *d_isects, int64_t n, const float lobe_a[3],
+                                float lobe_s, float *d_rgb, int32_t *d_count, void *stream);
+
 /* trace() frames of a probe scene (VRT/main.cc:10-30 with the probe block of
  * :104-105 in place): vrt_render_trace, vrt_render_trace_device and
  * vrt_trace_frame_device argument for argument, with the mixed march as the

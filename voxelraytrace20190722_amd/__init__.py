@@ -14,6 +14,8 @@ from .api import (  # noqa: F401
     unpack_tiles_device, pack_tiles_c_device, unpack_tiles_c_device, write_hdr, rgbe_device, write_hdr_device,
     SG, LightProbe, probe_points, probe_eval, PROBE_SGS, PROBE_DIRS, TEST_SMALL_PROBE_CHUNK,
     probe_eval_device, expf_flavour, expf_model, expf_selftest,
+    prod, inner_prod, sg_make, sg_integral, sg_prod, sg_inner_prod, sg_integral_device, sg_prod_device,
+    sg_inner_prod_device, SG_COSINE_AMPLITUDE, SG_COSINE_SHARPNESS,
     digest, DIGEST_ITEMS, TEST_MULTI_REFUSE_LAST, TEST_MULTI_DIVERGE,
 )
 
@@ -26,4 +28,6 @@ __all__ = [
     "tga_decode", "hdr_bytes_from_rgbe", "rgbe_device", "write_hdr_device", "build_id", "build_flag", "test_flags", "device_selftest_order", "set_test_flags",
     "device_selftest_chain", "SG", "LightProbe", "probe_points", "probe_eval",
     "probe_eval_device", "expf_flavour", "expf_model", "expf_selftest", "digest",
+    "prod", "inner_prod", "sg_make", "sg_integral", "sg_prod", "sg_inner_prod", "sg_integral_device", "sg_prod_device",
+    "sg_inner_prod_device", "SG_COSINE_AMPLITUDE", "SG_COSINE_SHARPNESS",
 ]

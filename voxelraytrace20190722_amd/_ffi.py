@@ -180,6 +180,15 @@ SIGNATURES = {
                                     C.POINTER(C.c_uint64), C.POINTER(C.c_uint32)]),
     "vrt_probe_eval_device": (C.c_int, [C.c_int, _P, C.c_int64, _P, C.c_int64, _P, _P]),
     "vrt_probe_shade_hits_device": (C.c_int, [_P, _P, C.c_int64, _P, _P, _P]),
+    "vrt_sg_make": (C.c_int, [f32p, f32p, f32p, C.c_int64, C.POINTER(SGRec)]),
+    "vrt_sg_integral": (C.c_int, [C.POINTER(SGRec), C.c_int64, f32p]),
+    "vrt_sg_prod": (C.c_int, [C.POINTER(SGRec), C.POINTER(SGRec), C.c_int64, C.POINTER(SGRec)]),
+    "vrt_sg_inner_prod": (C.c_int, [C.POINTER(SGRec), C.POINTER(SGRec), C.c_int64, f32p]),
+    "vrt_sg_integral_device": (C.c_int, [C.c_int, _P, C.c_int64, _P, _P]),
+    "vrt_sg_prod_device": (C.c_int, [C.c_int, _P, _P, C.c_int64, _P, _P]),
+    "vrt_sg_inner_prod_device": (C.c_int, [C.c_int, _P, _P, C.c_int64, _P, _P]),
+    "vrt_probe_irradiance": (C.c_int, [_P, C.POINTER(ISect), C.c_int64, f32p, C.c_float, f32p, i32p]),
+    "vrt_probe_irradiance_device": (C.c_int, [_P, _P, C.c_int64, f32p, C.c_float, _P, _P, _P]),
     "vrt_render_trace_probes": (C.c_int, [_P, C.POINTER(Camera), C.POINTER(Film), C.c_float, f32p, i32p, f32p]),
     "vrt_render_trace_probes_device": (C.c_int, [_P, C.POINTER(Camera), C.POINTER(Film), C.c_float, C.c_int,
                                                  C.c_int, C.c_int, _P, _P]),

@@ -18,6 +18,9 @@ from . import _ffi
 from ._ffi import VrtError, check, lib, ptr
 
 FLT_MAX = float(np.finfo(np.float32).max)
+# the usual one-lobe fit of a clamped cosine (VoxelOctree.probe_irradiance's default lobe)
+SG_COSINE_AMPLITUDE = 1.17   # include/vrt.h VRT_SG_COSINE_AMPLITUDE
+SG_COSINE_SHARPNESS = 2.133  # include/vrt.h VRT_SG_COSINE_SHARPNESS
 
 
 def to_radian(degree):
@@ -561,6 +564,37 @@ class VoxelOctree:
         vp = lambda q: None if q is None else C.c_void_p(q)
         check(lib().vrt_probe_shade_hits_device(self.h, C.c_void_p(d_hits_ptr), int(n), vp(d_rgb_ptr),
                                                 vp(d_albedo_ptr), vp(stream_ptr)), "vrt_probe_shade_hits_device")
+
+    def probe_irradiance(self, hit_p, normal, lobe_a=(SG_COSINE_AMPLITUDE,) * 3, lobe_s=SG_COSINE_SHARPNESS,
+                         counts=False):
+        """vrt_probe_irradiance: the light the scene's probes send to (n, 3)
+        points with (n, 3) normals -> (n, 3): the mean over the probes of the
+        point's leaf of the sum over their stored lobes of inner_prod(lobe,
+        SG{lobe_a, normal, lobe_s}); +0 where the leaf holds no probe.
+        counts=True also returns the (n,) int32 probe counts."""
+        hit_p, normal = np.asarray(hit_p, np.float32), np.asarray(normal, np.float32)
+        if hit_p.ndim != 2 or hit_p.shape[1] != 3 or normal.shape != hit_p.shape:
+            raise ValueError(f"hit_p and normal must both be (n, 3), got {hit_p.shape} and {normal.shape}")
+        isects = np.ascontiguousarray(np.concatenate([hit_p, normal], axis=1))
+        n = isects.shape[0]
+        la = _f3(lobe_a)
+        rgb = np.zeros((n, 3), np.float32)
+        cnt = np.zeros(n, np.int32) if counts else None
+        check(lib().vrt_probe_irradiance(self.h, isects.ctypes.data_as(C.POINTER(_ffi.ISect)), n, ptr(la, _ffi.f32p),
+                                         float(lobe_s), ptr(rgb, _ffi.f32p), ptr(cnt, _ffi.i32p)),
+              "vrt_probe_irradiance")
+        return (rgb, cnt) if counts else rgb
+
+    def probe_irradiance_device(self, d_isects_ptr, n, d_rgb_ptr, d_count_ptr=None,
+                                lobe_a=(SG_COSINE_AMPLITUDE,) * 3, lobe_s=SG_COSINE_SHARPNESS, stream_ptr=None):
+        """vrt_probe_irradiance_device: n vrt_isect {hit_p, normal} in, 3n
+        floats and (unless d_count_ptr is None) n int32 counts out, device
+        pointers, enqueued on the stream."""
+        vp = lambda q: None if q is None else C.c_void_p(q)
+        la = _f3(lobe_a)
+        check(lib().vrt_probe_irradiance_device(self.h, vp(d_isects_ptr), int(n), ptr(la, _ffi.f32p), float(lobe_s),
+                                                vp(d_rgb_ptr), vp(d_count_ptr), vp(stream_ptr)),
+              "vrt_probe_irradiance_device")
 
     def ray_march(self, rays, even_invisible=False):
         """Batched gi::ray_march over (n, 8) rays {o, d, tmin, tmax} (d
@@ -1358,12 +1392,110 @@ def expf_selftest(first_bits, count, stride=1, flavour=None, device=-1):
     return bad.value, (first.value if bad.value else None)
 
 
+# ---- the SG algebra (VRT/voxel_octree.cc:497-528), batched ----
+def _sg_recs(sgs, what="sgs"):
+    """(n, 7) float32 records {a, d, s}, C-contiguous."""
+    sgs = np.asarray(sgs, np.float32)
+    if sgs.ndim != 2 or sgs.shape[1] != 7:
+        raise ValueError(f"{what} must be (n, 7) {{a, d, s}}, got {sgs.shape}")
+    return np.ascontiguousarray(sgs)
+
+
+def _sg_pair(lhs, rhs):
+    lhs, rhs = _sg_recs(lhs, "lhs"), _sg_recs(rhs, "rhs")
+    if lhs.shape != rhs.shape:
+        raise ValueError(f"lhs and rhs must have the same length, got {lhs.shape[0]} and {rhs.shape[0]}")
+    return lhs, rhs
+
+
+def _sgp(a):
+    return a.ctypes.data_as(C.POINTER(_ffi.SGRec))
+
+
+def sg_make(a, d, s):
+    """gi::SG's constructor (vrt_sg_make): a, d (n, 3), s (n,) -> (n, 7)
+    records {a, d / length(d), s}."""
+    a, d = np.asarray(a, np.float32), np.asarray(d, np.float32)
+    s = np.ascontiguousarray(np.asarray(s, np.float32).reshape(-1))
+    if a.ndim != 2 or a.shape[1] != 3 or d.shape != a.shape or s.shape[0] != a.shape[0]:
+        raise ValueError(f"a, d must be (n, 3) and s (n,), got {a.shape}, {d.shape}, {s.shape}")
+    a, d = np.ascontiguousarray(a), np.ascontiguousarray(d)
+    out = np.zeros((a.shape[0], 7), np.float32)
+    check(lib().vrt_sg_make(ptr(a, _ffi.f32p), ptr(d, _ffi.f32p), ptr(s, _ffi.f32p), a.shape[0], _sgp(out)),
+          "vrt_sg_make")
+    return out
+
+
+def sg_integral(sgs):
+    """SG::integral (vrt_sg_integral): (n, 7) records -> (n, 3)."""
+    sgs = _sg_recs(sgs)
+    rgb = np.zeros((sgs.shape[0], 3), np.float32)
+    check(lib().vrt_sg_integral(_sgp(sgs), sgs.shape[0], ptr(rgb, _ffi.f32p)), "vrt_sg_integral")
+    return rgb
+
+
+def sg_prod(lhs, rhs):
+    """gi::prod (vrt_sg_prod), pairwise: (n, 7), (n, 7) -> (n, 7)."""
+    lhs, rhs = _sg_pair(lhs, rhs)
+    out = np.zeros_like(lhs)
+    check(lib().vrt_sg_prod(_sgp(lhs), _sgp(rhs), lhs.shape[0], _sgp(out)), "vrt_sg_prod")
+    return out
+
+
+def sg_inner_prod(lhs, rhs):
+    """gi::inner_prod (vrt_sg_inner_prod), pairwise: (n, 7), (n, 7) -> (n, 3)."""
+    lhs, rhs = _sg_pair(lhs, rhs)
+    rgb = np.zeros((lhs.shape[0], 3), np.float32)
+    check(lib().vrt_sg_inner_prod(_sgp(lhs), _sgp(rhs), lhs.shape[0], ptr(rgb, _ffi.f32p)), "vrt_sg_inner_prod")
+    return rgb
+
+
+def _vp(q):
+    return None if q is None else C.c_void_p(q)
+
+
+def sg_integral_device(d_sgs_ptr, n, d_rgb_ptr, device=0, stream_ptr=None):
+    """vrt_sg_integral_device: n vrt_sg records in, 3n floats out (device
+    pointers), enqueued on the stream."""
+    check(lib().vrt_sg_integral_device(int(device), _vp(d_sgs_ptr), int(n), _vp(d_rgb_ptr), _vp(stream_ptr)),
+          "vrt_sg_integral_device")
+
+
+def sg_prod_device(d_lhs_ptr, d_rhs_ptr, n, d_out_ptr, device=0, stream_ptr=None):
+    """vrt_sg_prod_device: n + n vrt_sg records in, n out (device pointers)."""
+    check(lib().vrt_sg_prod_device(int(device), _vp(d_lhs_ptr), _vp(d_rhs_ptr), int(n), _vp(d_out_ptr),
+                                   _vp(stream_ptr)), "vrt_sg_prod_device")
+
+
+def sg_inner_prod_device(d_lhs_ptr, d_rhs_ptr, n, d_rgb_ptr, device=0, stream_ptr=None):
+    """vrt_sg_inner_prod_device: n + n vrt_sg records in, 3n floats out
+    (device pointers)."""
+    check(lib().vrt_sg_inner_prod_device(int(device), _vp(d_lhs_ptr), _vp(d_rhs_ptr), int(n), _vp(d_rgb_ptr),
+                                         _vp(stream_ptr)), "vrt_sg_inner_prod_device")
+
+
 class SG:
     """gi::SG (VRT/voxel_octree.cc:497-508): amplitude a, axis d (normalised
     by the library when it comes from a gather), sharpness s."""
 
     def __init__(self, a, d, s):
         self.a, self.d, self.s = _f3(a), _f3(d), np.float32(s)
+
+    def _rec(self):
+        return np.concatenate([self.a, self.d, [self.s]]).astype(np.float32)[None, :]
+
+    @classmethod
+    def _of(cls, rec):
+        return cls(rec[0:3], rec[3:6], rec[6])
+
+    @classmethod
+    def make(cls, a, d, s):
+        """The reference's constructor SG{a, d, s}: d normalised (vrt_sg_make)."""
+        return cls._of(sg_make(_f3(a)[None, :], _f3(d)[None, :], [s])[0])
+
+    def integral(self):
+        """SG::integral (VRT/voxel_octree.cc:509-513) -> (3,)."""
+        return sg_integral(self._rec())[0]
 
     def eval(self, dir):
         """a * expf(s * (dot(dir, d) - 1)): one lobe through vrt_probe_eval
@@ -1372,6 +1504,16 @@ class SG:
                "s": np.zeros((1, PROBE_SGS), np.float32)}
         sgs["a"][0, 0], sgs["d"][0, 0], sgs["s"][0, 0] = self.a, self.d, self.s
         return probe_eval(sgs, _f3(dir)[None, :])[0, 0]
+
+
+def prod(lhs, rhs):
+    """gi::prod(lhs, rhs) (VRT/voxel_octree.cc:514-521) -> SG."""
+    return SG._of(sg_prod(lhs._rec(), rhs._rec())[0])
+
+
+def inner_prod(lhs, rhs):
+    """gi::inner_prod(lhs, rhs) (VRT/voxel_octree.cc:522-528) -> (3,)."""
+    return sg_inner_prod(lhs._rec(), rhs._rec())[0]
 
 
 class LightProbe:

@@ -11,6 +11,7 @@
 #include "../../include/vrt.h"
 #include "vrt_error.h"
 #include "vrt_internal.h"
+#include "vrt_sg.h"
 
 #include <algorithm>
 #include <atomic>
@@ -3872,6 +3873,194 @@ extern "C" int vrt_probe_shade_hits_device(vrt_scene *s, const vrt_hit *d_hits, 
                                                      d_rgb, d_albedo, st);
         if (e != hipSuccess)
                 return fail(VRT_E_DEVICE, "probe shading launch failed: %s", hipGetErrorString(e));
+        return ts_release(s, set, st);
+}
+
+// ---- the SG algebra and the probes' irradiance (vrt_sg.h) -------------------
+// the host calls' expf: the C library's
+struct LibmExp {
+        float operator()(float x) const { return expf(x); }
+};
+
+// n and the arrays of a batched SG call: VRT_OK with *empty set for n == 0
+static int sg_args(int64_t n, bool arrays, bool *empty)
+{
+        static_assert(sizeof(vrt_sg) == 28 && sizeof(vrt_isect) == 24, "vrt_sg / vrt_isect layout");
+        *empty = n == 0;
+        if (n < 0)
+                return fail(VRT_E_INVALID, "bad argument: n = %lld", (long long)n);
+        if (n > 0 && !arrays)
+                return fail(VRT_E_INVALID, "null argument");
+        return VRT_OK;
+}
+
+static const float *sg_f(const vrt_sg *p) { return reinterpret_cast<const float *>(p); }
+static float *sg_f(vrt_sg *p) { return reinterpret_cast<float *>(p); }
+
+extern "C" int vrt_sg_make(const float *a, const float *d, const float *s, int64_t n, vrt_sg *out)
+{
+        bool empty;
+        if (int rc = sg_args(n, a && d && s && out, &empty); rc || empty)
+                return rc;
+        for (int64_t i = 0; i < n; ++i)
+                sg_store(sg_f(out) + 7 * i, sg_make(mk3(a[3 * i], a[3 * i + 1], a[3 * i + 2]),
+                                                    mk3(d[3 * i], d[3 * i + 1], d[3 * i + 2]), s[i]));
+        return VRT_OK;
+}
+
+extern "C" int vrt_sg_integral(const vrt_sg *sgs, int64_t n, float *rgb)
+{
+        bool empty;
+        if (int rc = sg_args(n, sgs && rgb, &empty); rc || empty)
+                return rc;
+        for (int64_t i = 0; i < n; ++i)
+                f3_store(rgb + 3 * i, sg_integral(sg_load(sg_f(sgs) + 7 * i), LibmExp{}));
+        return VRT_OK;
+}
+
+extern "C" int vrt_sg_prod(const vrt_sg *lhs, const vrt_sg *rhs, int64_t n, vrt_sg *out)
+{
+        bool empty;
+        if (int rc = sg_args(n, lhs && rhs && out, &empty); rc || empty)
+                return rc;
+        for (int64_t i = 0; i < n; ++i)
+                sg_store(sg_f(out) + 7 * i,
+                         sg_prod(sg_load(sg_f(lhs) + 7 * i), sg_load(sg_f(rhs) + 7 * i), LibmExp{}));
+        return VRT_OK;
+}
+
+extern "C" int vrt_sg_inner_prod(const vrt_sg *lhs, const vrt_sg *rhs, int64_t n, float *rgb)
+{
+        bool empty;
+        if (int rc = sg_args(n, lhs && rhs && rgb, &empty); rc || empty)
+                return rc;
+        for (int64_t i = 0; i < n; ++i)
+                f3_store(rgb + 3 * i,
+                         sg_inner_prod(sg_load(sg_f(lhs) + 7 * i), sg_load(sg_f(rhs) + 7 * i), LibmExp{}));
+        return VRT_OK;
+}
+
+// what the three device calls share: arguments, the expf flavour, the device
+static int sg_device_begin(const char *what, int device, int64_t n, bool arrays, int *fused, bool *empty)
+{
+        if (int rc = sg_args(n, arrays, empty); rc || *empty)
+                return rc;
+        if (int rc = device_expf(what, fused))
+                return rc;
+        if (int rc = check_device(device))
+                return rc;
+        HIPCHK(hipSetDevice(device));
+        return VRT_OK;
+}
+
+extern "C" int vrt_sg_integral_device(int device, const vrt_sg *d_sgs, int64_t n, float *d_rgb, void *stream)
+{
+        int fused;
+        bool empty;
+        if (int rc = sg_device_begin("vrt_sg_integral_device", device, n, d_sgs && d_rgb, &fused, &empty); rc || empty)
+                return rc;
+        HIPCHK(launch_sg_integral(sg_f(d_sgs), n, fused, d_rgb, static_cast<hipStream_t>(stream)));
+        return VRT_OK;
+}
+
+extern "C" int vrt_sg_prod_device(int device, const vrt_sg *d_lhs, const vrt_sg *d_rhs, int64_t n, vrt_sg *d_out,
+                                  void *stream)
+{
+        int fused;
+        bool empty;
+        if (int rc = sg_device_begin("vrt_sg_prod_device", device, n, d_lhs && d_rhs && d_out, &fused, &empty);
+            rc || empty)
+                return rc;
+        HIPCHK(launch_sg_prod(sg_f(d_lhs), sg_f(d_rhs), n, fused, sg_f(d_out), static_cast<hipStream_t>(stream)));
+        return VRT_OK;
+}
+
+extern "C" int vrt_sg_inner_prod_device(int device, const vrt_sg *d_lhs, const vrt_sg *d_rhs, int64_t n,
+                                        float *d_rgb, void *stream)
+{
+        int fused;
+        bool empty;
+        if (int rc = sg_device_begin("vrt_sg_inner_prod_device", device, n, d_lhs && d_rhs && d_rgb, &fused, &empty);
+            rc || empty)
+                return rc;
+        HIPCHK(launch_sg_inner_prod(sg_f(d_lhs), sg_f(d_rhs), n, fused, d_rgb, static_cast<hipStream_t>(stream)));
+        return VRT_OK;
+}
+
+// the arguments of both irradiance calls
+static int irradiance_args(const vrt_scene *s, const vrt_isect *isects, int64_t n, const float *lobe_a,
+                           const float *rgb, bool *empty)
+{
+        if (!s)
+                return fail(VRT_E_INVALID, "null argument");
+        if (s->probes.empty())
+                return fail(VRT_E_INVALID, "the scene has no probes (vrt_scene_create_probes)");
+        return sg_args(n, isects && lobe_a && rgb, empty);
+}
+
+// On the host from the scene's host arrays, whatever the scene's device is.
+extern "C" int vrt_probe_irradiance(vrt_scene *s, const vrt_isect *isects, int64_t n, const float lobe_a[3],
+                                    float lobe_s, float *rgb, int32_t *count)
+{
+        bool empty;
+        if (int rc = irradiance_args(s, isects, n, lobe_a, rgb, &empty); rc || empty)
+                return rc;
+        std::lock_guard<std::mutex> lk(s->mu);
+        if (int rc = fetch_probe_sgs(s))  // a device gather may hold the latest
+                return rc;
+        const f3 la = mk3(lobe_a[0], lobe_a[1], lobe_a[2]);
+        const float *sgs = sg_f(s->probe_sgs.data());
+        const float *isf = reinterpret_cast<const float *>(isects);
+        const unsigned h = std::thread::hardware_concurrency();
+        const int nt = (int)std::min<int64_t>(std::min(16u, std::max(1u, h)), std::max<int64_t>(1, n >> 12));
+        auto work = [&](int64_t b, int64_t e) {
+                for (int64_t i = b; i < e; ++i) {
+                        f3 c;
+                        const int32_t k = probe_irradiance_one(s->nodes.data(), s->pnode.data(), s->pref.data(), sgs,
+                                                               isf + 6 * i, la, lobe_s, LibmExp{}, &c);
+                        f3_store(rgb + 3 * i, c);
+                        if (count)
+                                count[i] = k;
+                }
+        };
+        if (nt <= 1) {
+                work(0, n);
+                return VRT_OK;
+        }
+        std::vector<std::thread> th;
+        for (int t = 0; t < nt; ++t)
+                th.emplace_back(work, n * t / nt, n * (t + 1) / nt);
+        for (auto &x : th)
+                x.join();
+        return VRT_OK;
+}
+
+extern "C" int vrt_probe_irradiance_device(vrt_scene *s, const vrt_isect *d_isects, int64_t n, const float lobe_a[3],
+                                           float lobe_s, float *d_rgb, int32_t *d_count, void *stream)
+{
+        bool empty;
+        if (int rc = irradiance_args(s, d_isects, n, lobe_a, d_rgb, &empty); rc || empty)
+                return rc;
+        if (need_device(s))
+                return VRT_E_NODEVICE;
+        int fused;
+        if (int rc = device_expf("vrt_probe_irradiance_device", &fused))
+                return rc;
+        std::lock_guard<std::mutex> lk(s->mu);
+        HIPCHK(hipSetDevice(s->device));
+        hipStream_t st = static_cast<hipStream_t>(stream);
+        // a reader of the device SGs: behind their writers (a frame's gather)
+        // through the trace sets' events, as vrt_probe_shade_hits_device is
+        const int set = s->lm_cur >= 0 ? s->lm_cur : 0;
+        for (int k = 0; k < 2; ++k)
+                if (int rc = ts_acquire(s, k, st))
+                        return rc;
+        (void)hipGetLastError();
+        const hipError_t e = launch_probe_irradiance(s->dev.nodes, s->pdev, s->d_sgs,
+                                                     reinterpret_cast<const float *>(d_isects), n, lobe_a, lobe_s,
+                                                     fused, d_rgb, d_count, st);
+        if (e != hipSuccess)
+                return fail(VRT_E_DEVICE, "probe irradiance launch failed: %s", hipGetErrorString(e));
         return ts_release(s, set, st);
 }
 
